@@ -76,6 +76,19 @@ def build(force: bool = False) -> pathlib.Path:
     return SO
 
 
+REF_DIR = ORACLE_DIR / "_ref"
+
+
+def build_ref() -> pathlib.Path:
+    """oracle/reference.mk: the reference's declarations and callers compiled against the C++ shims into oracle/_ref/
+    (tests/test_shims_vs_reference.py).  Nothing without the reference checkout; what does not compile leaves its log
+    there for the test to report, so a failure here does not fail the build."""
+    r = subprocess.run(["make", "-k", "-C", str(ORACLE_DIR), "-f", "reference.mk"], capture_output=True, text=True)
+    if r.returncode != 0:
+        print(f"oracle/reference.mk: not everything compiled (tests/test_shims_vs_reference.py reports it)\n{r.stdout[-2000:]}")
+    return REF_DIR
+
+
 _lib = None
 
 

@@ -56,7 +56,7 @@ def test_bench_gpus_2_starts_two_ranks_and_reports_the_sharded_legs():
     import json
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     env.pop("WORLD_SIZE", None), env.pop("RANK", None), env.pop("LOCAL_RANK", None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "64",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--batch", "64",
            "--no-bruteforce", "--no-single-stream"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=1400, env=env, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -87,7 +87,7 @@ def test_bench_rccl_process_group_of_one():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="2")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--backend", "nccl", "--dist-at-one-rank", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--gpus", "1", "--backend", "nccl", "--dist-at-one-rank", "--steps", "2", "--warmup", "1",
            "--batch", "64", "--no-bruteforce", "--no-single-stream", "--no-cpu-baseline", "--collective-timeout", "120"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=800, env=env, cwd=str(ROOT))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r06; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-ONE="--pipeline 1 --no-bruteforce --no-single-stream --no-ba --no-cpu-baseline"   # ONE regime per kernel
+ONE="--full --pipeline 1 --no-bruteforce --no-single-stream --no-ba --no-cpu-baseline"   # ONE regime per kernel
 for what in "$@"; do case $what in
 trace)
   # the tracked step, one batch in flight: every extraction / tracking kernel has one regime
@@ -50,7 +50,7 @@ pose)
   bash $R/tools/pmc_probe.sh k_pose_only $R/tools/pose_probe.py 2>&1 | grep -v "^W2\|^E2\|amdgpu.ids" > $O/r06_pmc_pose_only.txt
   rm -rf $R/gpurun_out/pmcp ;;
 bench)
-  cd $R && python3 bench.py > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r06_bench.json
+  cd $R && python3 bench.py --full > $O/bench.log 2>&1; tail -1 $O/bench.log > $O/r06_bench.json
   for f in orb match guided tracker ba chol pose_graph loop; do echo "== $f.hip"; fl=-ffp-contract=off; case $f in ba|chol|pose_graph) fl=-ffp-contract=fast;; esac; python3 $R/tools/kernel_resources.py $R/vo_slam_test_amd/csrc/$f.hip $fl -I$R/vo_slam_test_amd/csrc; done > $O/r06_kernel_resources.txt 2>&1 ;;
 esac; done
 ls -la $O
