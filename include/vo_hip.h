@@ -390,6 +390,43 @@ int vo_vocab_load(const char *path, vo_vocab **out, int *n_nodes, int *n_words, 
 int vo_bow_score(int n_query, const int32_t *query_words, const double *query_values, int n_candidates,
                  const int32_t *cand_start, const int32_t *cand_words, const double *cand_values, double *scores);
 
+/* cv::solvePnPRansac(pts3d, pts2d, K, noArray(), rvec, tvec, false, iterations, reproj_error, confidence, inliers,
+ * SOLVEPNP_EPNP) as VisualOdometry::poseEstimateByPnP calls it (visualOdometry.cpp:778-830: 100, 8.0, 0.99), for a ragged
+ * batch: problem p owns correspondences offsets[p] .. offsets[p+1] of pts3d [.][3] (MapPoint::getPose() as float) and
+ * pts2d [.][2] (unKeypoints_ pixels); cam4 = fx, fy, cx, cy (the float K), no distortion.  Contract:
+ * cv::RNG((uint64)-1) per problem + getSubset 5-tuples, EPnP in FP64 per tuple, float reprojection gate
+ * err <= (float)(reproj_error^2), the ordered RANSAC loop with RANSACUpdateNumIters, then EPnP refitted on the winner's
+ * inliers (the mask is not recomputed after the refit).  n == 5: one EPnP on all five, all inliers.  n < 5: failure
+ * (deviation: the reference runs P3P at n == 4 and throws below).
+ * Outputs per problem: Tcw12 [12] (R | t, 3 x 4 row-major; zero on failure), pose6 [6] = se3 log of it (host form only,
+ * may be NULL), n_inliers, status (1 found, 0 not); inlier [offsets[P]] the mask.  diag (NULL, or any member NULL):
+ * samples [P][iterations][5], counts [P][iterations], hyp_Tcw12 [P][iterations][12] of every hypothesis (including those
+ * past the final niters; zero for n <= 5), best_iter [P] (-1: none / n == 5), final_niters [P].
+ * Limits: P <= VO_PNP_MAX_PROBLEMS, iterations <= VO_PNP_MAX_ITERATIONS, P x iterations <= VO_PNP_MAX_HYPOTHESES, and (host
+ * form, checked) n <= VO_PNP_MAX_POINTS per problem; beyond them VO_ERR_CAPACITY, nothing truncated.
+ * The _dev form takes device arrays (diag members too) and enqueues on hip_stream (NULL: the legacy stream) without host
+ * synchronisation or allocation; its intermediates live in the caller's device `workspace` of at least
+ * vo_pnp_workspace_bytes(n_problems, iterations) bytes (else VO_ERR_CAPACITY), which must not be in use by another call
+ * until this one has completed on hip_stream -- calls on different streams take different workspaces.  Its offsets are
+ * not inspected on the host (the kernels stage a problem's correspondences in chunks and take any size).  The host form
+ * is synchronous and keeps its own buffers.
+ * Degenerate sets: CC^-1 of the barycentric coordinates is the pseudo-inverse cvInvert(CV_SVD) forms (coplanar or
+ * coincident points give finite coordinates); a refit whose pose is not finite fails the problem (status 0, no
+ * inliers) -- a deviation: OpenCV would return its non-finite pose. */
+enum { VO_PNP_MAX_PROBLEMS = 65536, VO_PNP_MAX_ITERATIONS = 1000, VO_PNP_MAX_HYPOTHESES = 1 << 21, VO_PNP_MAX_POINTS = 1 << 20 };
+typedef struct {
+  int32_t *samples, *counts;
+  double *hyp_Tcw12;
+  int32_t *best_iter, *final_niters;
+} vo_pnp_diag;
+int vo_pnp_ransac(int n_problems, const int32_t *offsets, const float *pts3d, const float *pts2d, const float cam4[4],
+                  int iterations, float reproj_error, double confidence, double *Tcw12, double *pose6, uint8_t *inlier,
+                  int32_t *n_inliers, int32_t *status, const vo_pnp_diag *diag);
+size_t vo_pnp_workspace_bytes(int n_problems, int iterations); /* 0 for invalid arguments */
+int vo_pnp_ransac_dev(int n_problems, const int32_t *offsets, const float *pts3d, const float *pts2d, const float cam4[4],
+                      int iterations, float reproj_error, double confidence, double *Tcw12, uint8_t *inlier, int32_t *n_inliers,
+                      int32_t *status, const vo_pnp_diag *diag, void *workspace, size_t workspace_bytes, void *hip_stream);
+
 /* Sim3Solver (src/sim3Solver.cpp): every RANSAC hypothesis of Sim3Solver::iterate in one launch -- Horn's
  * closed form (computeSim3 :179-252) for the three sampled correspondences triplets[3k..3k+2] and
  * checkInliers (:254-280) over all n correspondences.  The random triplets come from the caller (the
@@ -563,8 +600,9 @@ int vo_track_scatter_gather_dev(vo_frames *h, int slot0, int n_frames, const int
  * device for the frames that need it (a per-frame flag, a second candidate / replay pass over the flagged frames only).
  * Status bits VO_TRACK_FEW_MATCHES / VO_TRACK_FEW_INLIERS tell the caller that the reference would have left
  * trackWithMotion (:247, :253); the route it takes then is vo_tracker_track_ref_keyframe below (trackRefKeyFrame,
- * :256-277).  Not covered: relocalisation (:307-402, PnP RANSAC over BoW candidates -- control plane around
- * vo_match_bow / vo_match_frame_keyframe / vo_pose_only_solve), and the map-side steps between the two stages:
+ * :256-277).  Relocalisation (:307-402) has its PnP RANSAC in vo_pnp_ransac / _dev; its control plane (candidates,
+ * gates, guided re-searches) stays caller code around vo_match_bow / vo_pnp_ransac / vo_match_frame_keyframe /
+ * vo_pose_only_solve.  Not covered either: the map-side steps between the two stages:
  * trackLocalMap derives localKeyframes_ / localMappoints_ from frame_curr_->mappoints_ AFTER the first stage's culling
  * (updateLocalKeyFrames / updateLocalMapPoints, :286-291), whereas this call takes the local map BEFORE it starts.  A
  * caller that needs the reference's order runs the two stages as two calls: vo_tracker_track with an empty local map

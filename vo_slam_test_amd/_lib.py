@@ -43,7 +43,7 @@ SYMBOLS = [
     "vo_hamming_matrix_dev", "vo_hamming_matrix_batch_dev", "vo_hamming_matrix", "vo_median_descriptor",
     "vo_frames_create", "vo_frames_destroy", "vo_frames_capacity", "vo_frames_set_camera", "vo_frames_build_dev",
     "vo_frames_upload", "vo_frames_construct", "vo_frames_download", "vo_frames_features_in_area", "vo_match_guided_dev", "vo_match_guided_status",
-    "vo_vocab_load", "vo_bow_score", "vo_sim3_ransac_eval", "vo_triangulate", "vo_rgb_to_gray", "vo_rgb_to_gray_dev",
+    "vo_vocab_load", "vo_bow_score", "vo_pnp_ransac", "vo_pnp_ransac_dev", "vo_pnp_workspace_bytes", "vo_sim3_ransac_eval", "vo_triangulate", "vo_rgb_to_gray", "vo_rgb_to_gray_dev",
     "vo_dataset_open", "vo_dataset_size", "vo_dataset_entry", "vo_dataset_close", "vo_png_info", "vo_png_read",
     "vo_trajectory_write", "vo_tracking_time_stats",
     "vo_track_project_dev", "vo_track_scatter_dev", "vo_track_gather_dev", "vo_track_scatter_gather_dev", "vo_pose_only_solve_ranges_dev",
@@ -86,6 +86,7 @@ def lib():
     L.vo_version.restype = C.c_char_p
     L.vo_release_thread_scratch.restype = C.c_size_t
     L.vo_orb_scale_factor.restype = C.c_float
+    L.vo_pnp_workspace_bytes.restype = C.c_size_t
     for name in SYMBOLS:
         f = getattr(L, name, None)
         if f is not None and f.restype is C.c_int:
@@ -1101,6 +1102,65 @@ def se3_log(R, t):
     Rf, tf = np.ascontiguousarray(R, np.float64).reshape(-1), np.ascontiguousarray(t, np.float64)
     check(lib().vo_se3_log(_p(Rf), _p(tf), _p(xi)))
     return xi
+
+
+class PnpDiag(C.Structure):
+    _fields_ = [("samples", C.c_void_p), ("counts", C.c_void_p), ("hyp_Tcw12", C.c_void_p), ("best_iter", C.c_void_p),
+                ("final_niters", C.c_void_p)]
+
+
+def pnp_ransac(problems, cam4, iterations=100, reproj_error=8.0, confidence=0.99, diagnostics=False):
+    """cv::solvePnPRansac(..., SOLVEPNP_EPNP) of poseEstimateByPnP (visualOdometry.cpp:778-830) for a batch of problems
+    [(pts3d [n, 3], pts2d [n, 2]), ...] (float32) in one call.  Returns dict: Tcw [P, 3, 4], pose6 [P, 6] (se3),
+    n_inliers [P], status [P] (1 found), inliers [list of bool [n]]; with diagnostics also samples [P, it, 5],
+    counts [P, it], hyp_Tcw [P, it, 3, 4], best_iter [P], final_niters [P]."""
+    P = len(problems)
+    ns = [len(np.asarray(a).reshape(-1, 3)) for a, _ in problems]
+    off = np.zeros(P + 1, np.int32)
+    off[1:] = np.cumsum(ns)
+    N = int(off[-1])
+    p3 = np.ascontiguousarray(np.concatenate([np.asarray(a, np.float32).reshape(-1, 3) for a, _ in problems]) if N else np.zeros((0, 3), np.float32))
+    p2 = np.ascontiguousarray(np.concatenate([np.asarray(b, np.float32).reshape(-1, 2) for _, b in problems]) if N else np.zeros((0, 2), np.float32))
+    cam = np.ascontiguousarray(cam4, np.float32)[:4].copy()
+    T, x6 = np.zeros((max(P, 1), 12)), np.zeros((max(P, 1), 6))
+    mask, ninl, st = np.zeros(max(N, 1), np.uint8), np.zeros(max(P, 1), np.int32), np.zeros(max(P, 1), np.int32)
+    out = {}
+    d = None
+    if diagnostics:
+        it = int(iterations)
+        out.update(samples=np.zeros((P, it, 5), np.int32), counts=np.zeros((P, it), np.int32), hyp_Tcw=np.zeros((P, it, 3, 4)),
+                   best_iter=np.zeros(P, np.int32), final_niters=np.zeros(P, np.int32))
+        d = PnpDiag(*(out[k].ctypes.data for k in ("samples", "counts", "hyp_Tcw", "best_iter", "final_niters")))
+    check(lib().vo_pnp_ransac(P, _p(off), _p(p3), _p(p2), _p(cam), int(iterations), C.c_float(reproj_error), C.c_double(confidence),
+                              _p(T), _p(x6), _p(mask), _p(ninl), _p(st), C.byref(d) if d is not None else None), "vo_pnp_ransac")
+    out.update(Tcw=T[:P].reshape(P, 3, 4), pose6=x6[:P], n_inliers=ninl[:P], status=st[:P],
+               inliers=[mask[off[p]:off[p + 1]].astype(bool) for p in range(P)])
+    return out
+
+
+def pnp_workspace_bytes(n_problems, iterations=100):
+    return int(lib().vo_pnp_workspace_bytes(int(n_problems), int(iterations)))
+
+
+def pnp_ransac_dev(n_problems, offsets, pts3d, pts2d, cam4, Tcw12, inlier, n_inliers, status, iterations=100, reproj_error=8.0,
+                   confidence=0.99, diag=None, workspace=None, stream=0):
+    """vo_pnp_ransac_dev on device tensors (offsets int32 [P+1], pts3d float32 [N, 3], pts2d float32 [N, 2]; outputs Tcw12
+    float64 [P, 12], inlier uint8 [N], n_inliers / status int32 [P]); diag: dict of device tensors keyed as PnpDiag.
+    workspace: a device uint8 tensor of at least pnp_workspace_bytes(P, iterations) bytes, not shared with a call still in
+    flight on another stream (None: one is allocated for this call on the current device)."""
+    cam = np.ascontiguousarray(cam4, np.float32)[:4].copy()
+    d = None
+    if diag is not None:
+        d = PnpDiag(*(diag[k].data_ptr() if diag.get(k) is not None else None
+                      for k in ("samples", "counts", "hyp_Tcw12", "best_iter", "final_niters")))
+    if workspace is None:
+        import torch
+        workspace = torch.empty(max(pnp_workspace_bytes(n_problems, iterations), 1), dtype=torch.uint8, device=Tcw12.device)
+    check(lib().vo_pnp_ransac_dev(int(n_problems), _p(offsets), _p(pts3d), _p(pts2d), _p(cam), int(iterations), C.c_float(reproj_error),
+                                  C.c_double(confidence), _p(Tcw12), _p(inlier), _p(n_inliers), _p(status),
+                                  C.byref(d) if d is not None else None, _p(workspace), C.c_size_t(workspace.numel()),
+                                  _p(stream)), "vo_pnp_ransac_dev")
+    return workspace
 
 
 # ----------------------------------------------------------------------------- loop closing / local mapping / harness I/O
