@@ -410,6 +410,8 @@ int vo_bow_score(int n_query, const int32_t *query_words, const double *query_va
  * until this one has completed on hip_stream -- calls on different streams take different workspaces.  Its offsets are
  * not inspected on the host (the kernels stage a problem's correspondences in chunks and take any size).  The host form
  * is synchronous and keeps its own buffers.
+ * Every output of a problem (and its diag entries) is the same bit for bit whatever its position in the batch and
+ * whatever other problems share the call.
  * Degenerate sets: CC^-1 of the barycentric coordinates is the pseudo-inverse cvInvert(CV_SVD) forms (coplanar or
  * coincident points give finite coordinates); a refit whose pose is not finite fails the problem (status 0, no
  * inliers) -- a deviation: OpenCV would return its non-finite pose. */

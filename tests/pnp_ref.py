@@ -207,6 +207,28 @@ def reproj_err(R, t, pts3d, pts2d, cam4) -> np.ndarray:
         return dx * dx + dy * dy
 
 
+def inlier_counts(hyp, pts3d, pts2d, cam4, reproj_error=8.0, chunk=4) -> np.ndarray:
+    """reproj_err <= the float gate, counted per hypothesis, `chunk` hypotheses at a time (memory bounded by chunk x n).
+    hyp [H, 3, 4] -> int64 [H]"""
+    th2 = np.float32(float(np.float32(reproj_error)) ** 2)
+    hyp = np.asarray(hyp, np.float64)
+    out = np.zeros(len(hyp), np.int64)
+    for h0 in range(0, len(hyp), chunk):
+        hc = hyp[h0:h0 + chunk]
+        out[h0:h0 + chunk] = (reproj_err(hc[:, :, :3], hc[:, :, 3], pts3d, pts2d, cam4) <= th2).sum(axis=1)
+    return out
+
+
+def ransac_hypotheses(pts3d, pts2d, cam4, iterations) -> np.ndarray:
+    """the RANSAC hypotheses [iterations, 3, 4] of a problem with n > 5 (EPnP on samples(n, iterations)); iteration k's
+    depends on n alone, so a prefix of a longer run is the run with fewer iterations"""
+    p3 = np.asarray(pts3d, np.float32).reshape(-1, 3).astype(np.float64)
+    p2 = np.asarray(pts2d, np.float32).reshape(-1, 2).astype(np.float64)
+    S = samples(len(p3), int(iterations))
+    R, t = epnp(p3[S], p2[S], cam4)
+    return np.concatenate([R, t[:, :, None]], axis=2)
+
+
 def pnp_ransac(pts3d, pts2d, cam4, iterations=100, reproj_error=8.0, confidence=0.99, hypotheses=None):
     """The contract for one problem -> dict(status, Tcw [3, 4], inliers bool [n], n_inliers, samples, counts, hyp_Tcw,
     best_iter, final_niters).  hypotheses: [iterations, 3, 4] to replay given poses instead of solving them (the test
@@ -230,9 +252,7 @@ def pnp_ransac(pts3d, pts2d, cam4, iterations=100, reproj_error=8.0, confidence=
             hyp = np.concatenate([R, t[:, :, None]], axis=2)
         else:
             hyp = np.asarray(hypotheses, np.float64)
-        err = reproj_err(hyp[:, :, :3], hyp[:, :, 3], p3, p2, cam4)
-        inl = err <= th2
-        counts = inl.sum(axis=1).astype(np.int32)
+        counts = inlier_counts(hyp, p3, p2, cam4, reproj_error).astype(np.int32)
         best, max_good = -1, 0
         it = 0
         while it < niters:
@@ -244,7 +264,7 @@ def pnp_ransac(pts3d, pts2d, cam4, iterations=100, reproj_error=8.0, confidence=
         out.update(samples=S, counts=counts, hyp_Tcw=hyp, best_iter=best, final_niters=niters)
         if best < 0:
             return out
-        mask = inl[best]
+        mask = reproj_err(hyp[best, :, :3], hyp[best, :, 3], p3, p2, cam4) <= th2
     R, t = epnp(p3.astype(np.float64)[mask][None], p2.astype(np.float64)[mask][None], cam4)
     if not (np.isfinite(R).all() and np.isfinite(t).all()):  # a refit that is not finite fails the problem
         out.update(inliers=np.zeros(n, bool))
@@ -280,3 +300,86 @@ def make_problem(rng, n, outlier_frac=0.3, noise=0.5, cam4=CAM4, W=640, H=480):
     out = rng.random(n) < outlier_frac
     uv[out] = np.stack([rng.uniform(0, W, out.sum()), rng.uniform(0, H, out.sum())], axis=1)
     return pw.astype(np.float32), uv.astype(np.float32), R, t, out
+
+
+# the geometry of relocalisation, which make_problem never reaches: any heading, far from the world origin, near and far
+# points, fx != fy, an off-centre principal point, a second camera
+CAM_VGA = np.array([521.7, 498.3, 301.9, 263.4], np.float32)  # 640 x 480, fx != fy, principal point off-centre
+CAM_HD = np.array([903.6, 911.2, 652.8, 351.5], np.float32)   # 1280 x 720
+WIDE_CAMS = ((CAM_VGA, 640, 480), (CAM_HD, 1280, 720))
+
+
+def rotation(axis, angle) -> np.ndarray:
+    k = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + math.sin(angle) * Kx + (1 - math.cos(angle)) * Kx @ Kx
+
+
+def random_pose_wide(rng, near_pi=False, centre=(10.0, 1000.0)):
+    """Tcw of any heading: rotation angle uniform in [0, pi - 1e-3], or within 1e-3 of pi (near_pi); camera centre
+    |C| in `centre` metres from the world origin (t = -R C)"""
+    th = rng.uniform(math.pi - 1e-3, math.pi) if near_pi else rng.uniform(0.0, math.pi - 1e-3)
+    R = rotation(rng.normal(size=3), th)
+    d = rng.normal(size=3)
+    C = d / np.linalg.norm(d) * rng.uniform(*centre)
+    return R, -R @ C
+
+
+def project(p3, R, t, cam4) -> np.ndarray:
+    """the pixels of float32 world points under (R, t) in double, rounded once to float32 (noise-free data: their only
+    error is that rounding)"""
+    fu, fv, uc, vc = (float(c) for c in cam4[:4])
+    pc = np.asarray(p3, np.float32).astype(np.float64) @ R.T + t
+    return np.stack([fu * pc[:, 0] / pc[:, 2] + uc, fv * pc[:, 1] / pc[:, 2] + vc], axis=1).astype(np.float32)
+
+
+def make_problem_wide(rng, n, outlier_frac=0.3, noise=0.5, cam4=CAM_VGA, W=640, H=480, near_pi=False, centre=(10.0, 1000.0),
+                      depth=(0.2, 80.0)):
+    """make_problem on relocalisation geometry (random_pose_wide; depths log-uniform in `depth`).  noise == 0 and
+    outlier_frac == 0: the pixels are project() of the float32 world points, exact up to one float32 rounding"""
+    fu, fv, uc, vc = (float(c) for c in cam4[:4])
+    R, t = random_pose_wide(rng, near_pi, centre)
+    u, v = rng.uniform(0, W, n), rng.uniform(0, H, n)
+    z = np.exp(rng.uniform(math.log(depth[0]), math.log(depth[1]), n))
+    pc = np.stack([(u - uc) / fu * z, (v - vc) / fv * z, z], axis=1)
+    pw = ((pc - t) @ R).astype(np.float32)
+    out = rng.random(n) < outlier_frac
+    if noise == 0 and not out.any():
+        return pw, project(pw, R, t, cam4), R, t, out
+    uv = project(pw, R, t, cam4).astype(np.float64) + rng.normal(0, noise, (n, 2))
+    uv[out] = np.stack([rng.uniform(0, W, out.sum()), rng.uniform(0, H, out.sum())], axis=1)
+    return pw, uv.astype(np.float32), R, t, out
+
+
+def rounding_pose_bound(p3, R, t, cam4, safety=4.0):
+    """A bound on |R_est - R|max and |t_est - t|max for EPnP on noise-free data whose pixels carry only their float32
+    rounding (project()).  Derivation, to first order in the pixel error e (2n-vector):
+      * |e_i| <= half an ulp of the pixel coordinate, so |e|_2 <= sqrt(2n) h, h = max over the pixels of ulp / 2;
+      * the pose perturbation x = (w, dt') with R' = exp([w]x) R, pc' = pc + w x pc + dt' moves the pixels by J x, J the
+        2n x 6 Jacobian of (fu X/Z + uc, fv Y/Z + vc) at the true pose; the reprojection least squares gives
+        |x|_2 <= |e|_2 / sigma_min(J);
+      * EPnP minimises an algebraic error, the reprojection residual of point i scaled by its depth Z_i: a weighted least
+        squares, whose sensitivity is at most cond(W) = Z_max / Z_min times the unweighted one;
+      * `safety` covers EPnP's linearisation (an unconstrained 12-vector, then betas and Procrustes) against the
+        constrained 6-parameter fit above, and the second-order terms.
+    Then |R' - R|max <= |w|_2 and t' - t = dt' - w x t, so |t' - t|max <= |x|_2 (1 + |t|_2).  -> (bound_R, bound_t)
+    This is a worst case and it is loose: on the fixtures of test_wide_geometry_noise_free it lies 1e3 to 1e5 times
+    above EPnP's actual error (sqrt(2n) h takes every pixel at its largest rounding, Z_max / Z_min the worst weighting,
+    and `safety` multiplies both).  So it catches a pose that is wrong, not one that is imprecise; the kernels'
+    precision is pinned by their 1e-8 agreement with epnp()."""
+    fu, fv = float(cam4[0]), float(cam4[1])
+    pc = np.asarray(p3, np.float32).astype(np.float64) @ R.T + t
+    X, Y, Z = pc[:, 0], pc[:, 1], pc[:, 2]
+    px = project(p3, R, t, cam4)
+    h = float(np.spacing(np.abs(px)).max()) / 2
+    du = np.stack([fu / Z, 0 * Z, -fu * X / Z ** 2], axis=1)  # d(u)/d(pc)
+    dv = np.stack([0 * Z, fv / Z, -fv * Y / Z ** 2], axis=1)
+    cx = np.zeros((len(Z), 3, 3))  # d(w x pc)/dw = -[pc]x
+    cx[:, 0, 1], cx[:, 0, 2], cx[:, 1, 2] = Z, -Y, X
+    cx[:, 1, 0], cx[:, 2, 0], cx[:, 2, 1] = -Z, Y, -X
+    J = np.zeros((2 * len(Z), 6))
+    J[0::2, :3], J[1::2, :3] = np.einsum("ik,ikj->ij", du, cx), np.einsum("ik,ikj->ij", dv, cx)
+    J[0::2, 3:], J[1::2, 3:] = du, dv
+    smin = np.linalg.svd(J, compute_uv=False)[-1]
+    x = safety * (Z.max() / Z.min()) * math.sqrt(J.shape[0]) * h / smin
+    return x, x * (1.0 + float(np.linalg.norm(t)))

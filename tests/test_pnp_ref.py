@@ -148,3 +148,72 @@ def test_degenerate_sets_give_finite_poses_or_fail():
             assert np.isfinite(r["Tcw"]).all() and r["n_inliers"] == r["inliers"].sum() > 4
         else:
             assert r["n_inliers"] == 0 and not r["inliers"].any()
+
+
+@pytest.mark.parametrize("cam_i", [0, 1])
+def test_epnp_wide_geometry_recovers_the_pose(cam_i):
+    """any heading (within 1e-3 of pi too), 10-1000 m from the origin, depths 0.2-80 m, fx != fy, off-centre principal
+    points: noise-free data recover the true pose within the float32 pixel-rounding bound of rounding_pose_bound"""
+    rng = np.random.default_rng(200 + cam_i)
+    cam, W, H = pr.WIDE_CAMS[cam_i]
+    for i, m in enumerate((5, 6, 7, 12, 40, 300, 2000)):
+        for near_pi in (False, True):
+            p3, p2, R, t, _ = pr.make_problem_wide(rng, m, outlier_frac=0.0, noise=0.0, cam4=cam, W=W, H=H, near_pi=near_pi)
+            Re, te = pr.epnp(p3.astype(np.float64)[None], p2.astype(np.float64)[None], cam)
+            bR, bt = pr.rounding_pose_bound(p3, R, t, cam)
+            assert np.abs(Re[0] - R).max() <= bR and np.abs(te[0] - t).max() <= bt, (m, near_pi)
+    # the generator's promises
+    R, t = pr.random_pose_wide(rng, near_pi=True)
+    assert math.acos(max(-1.0, min(1.0, (np.trace(R) - 1) / 2))) > math.pi - 2e-3 and 10 <= np.linalg.norm(R.T @ t) <= 1000
+
+
+def test_epnp_wide_geometry_lands_near_the_reprojection_minimum():
+    """any heading, far from the origin, both cameras, at the depths of make_problem (1-6 m).  (At depths of 0.2-80 m
+    EPnP's algebraic error, the pixel residual scaled by depth, is far from the reprojection minimum under 1 px of noise:
+    4-27 px RMS against 1 px.  That is EPnP, not the restatement; the noise-free test above covers that range.)"""
+    least_squares = pytest.importorskip("scipy.optimize").least_squares
+    rng = np.random.default_rng(17)
+    for i in range(6):
+        cam, W, H = pr.WIDE_CAMS[i % 2]
+        fu, fv, uc, vc = (float(c) for c in cam)
+        p3, p2, Rt, tt, _ = pr.make_problem_wide(rng, 200, outlier_frac=0.0, noise=1.0, cam4=cam, W=W, H=H, near_pi=i % 3 == 0,
+                                               depth=(1.0, 6.0))
+        R, t = pr.epnp(p3.astype(np.float64)[None], p2.astype(np.float64)[None], cam)
+        R, t = R[0], t[0]
+        X = p3.astype(np.float64)
+
+        def resid(x, R0=Rt, t0=tt):  # the pose as a small rotation and translation about the true one
+            pc = X @ (pr.rotation(x[:3], np.linalg.norm(x[:3])) if np.linalg.norm(x[:3]) > 0 else np.eye(3)).dot(R0).T + t0 + x[3:]
+            return np.concatenate([fu * pc[:, 0] / pc[:, 2] + uc - p2[:, 0], fv * pc[:, 1] / pc[:, 2] + vc - p2[:, 1]])
+
+        sol = least_squares(resid, np.zeros(6), method="lm", xtol=1e-15, ftol=1e-15)
+        w = sol.x[:3]
+        Rm = (pr.rotation(w, np.linalg.norm(w)) if np.linalg.norm(w) > 0 else np.eye(3)) @ Rt
+        tm = tt + sol.x[3:]
+        tscale = max(1.0, float(np.linalg.norm(tt)))
+        assert np.abs(R - Rm).max() < 5e-3 and np.abs(t - tm).max() < 5e-3 * tscale, i
+        pc = X @ R.T + t
+        r = np.concatenate([fu * pc[:, 0] / pc[:, 2] + uc - p2[:, 0], fv * pc[:, 1] / pc[:, 2] + vc - p2[:, 1]])
+        assert np.sqrt(np.mean(r ** 2)) <= 1.1 * np.sqrt(np.mean(sol.fun ** 2)), i  # (the 1280 x 720 camera: up to 1.055)
+
+
+def test_ransac_wide_geometry_finds_the_pose_through_outliers():
+    rng = np.random.default_rng(19)
+    for i in range(4):
+        cam, W, H = pr.WIDE_CAMS[i % 2]
+        p3, p2, R, t, out = pr.make_problem_wide(rng, 300, outlier_frac=0.3, noise=0.5, cam4=cam, W=W, H=H, near_pi=i % 2 == 1)
+        res = pr.pnp_ransac(p3, p2, cam)
+        assert res["status"] == 1
+        assert np.abs(res["Tcw"][:, :3] - R).max() < 1e-2 and np.abs(res["Tcw"][:, 3] - t).max() < 1e-2 * max(1.0, np.linalg.norm(t))
+        assert res["inliers"][~out].mean() > 0.9
+
+
+def test_chunked_counts_equal_the_full_replay():
+    rng = np.random.default_rng(23)
+    p3, p2, *_ = pr.make_problem(rng, 3000)
+    hyp = pr.ransac_hypotheses(p3, p2, pr.CAM4, 37)
+    for g in (0.5, 8.0, 30.0):
+        full = (pr.reproj_err(hyp[:, :, :3], hyp[:, :, 3], p3, p2, pr.CAM4) <= np.float32(np.float32(g) ** 2)).sum(axis=1)
+        assert np.array_equal(pr.inlier_counts(hyp, p3, p2, pr.CAM4, g, chunk=5), full)
+    ref = pr.pnp_ransac(p3, p2, pr.CAM4, iterations=37)
+    assert np.array_equal(pr.pnp_ransac(p3, p2, pr.CAM4, iterations=37, hypotheses=hyp)["counts"], ref["counts"])

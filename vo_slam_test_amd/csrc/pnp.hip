@@ -350,9 +350,13 @@ __device__ void epnp_group(const PtSet &S, bool active, EpnpShared &sh, int lane
   for (int e = lane; e < 144; e += kGroup) sh.V[e] = (e / 12 == e % 12) ? 1.0 : 0.0;
   __syncthreads();
   // parallel-ordered cyclic Jacobi: per round 6 disjoint rotations (lanes 0..5 compute the angles), then each lane
-  // rewrites 9 elements of A (A' = J^T A J, columns then rows) and 9 of V (V' = V J)
+  // rewrites 9 elements of A (A' = J^T A J, columns then rows) and 9 of V (V' = V J).  A group stops rotating at the
+  // first sweep whose convergence test it passes and leaves A and V untouched from then on, while it keeps reaching the
+  // barriers until every group of the workgroup is done: a solve's bits do not depend on which solves share its
+  // workgroup (its position in the batch, its neighbours' convergence)
+  bool done = !active;
   for (int sweep = 0; sweep < kMaxSweeps; sweep++) {
-    // convergence: off-diagonal mass below 1e-30 of the diagonal's, in every group of the workgroup
+    // convergence: off-diagonal mass below 1e-30 of the diagonal's (the butterfly gives every lane the same sums)
     double off = 0, dg = 0;
     for (int e = lane; e < 144; e += kGroup) {
       const double x = sh.A[e] * sh.A[e];
@@ -362,8 +366,8 @@ __device__ void epnp_group(const PtSet &S, bool active, EpnpShared &sh, int lane
         off += x;
     }
     for (int o = kGroup / 2; o >= 1; o >>= 1) off += __shfl_xor(off, o, kGroup), dg += __shfl_xor(dg, o, kGroup);
-    const int more = active && off > 1e-30 * dg;
-    if (!__syncthreads_or(more)) break;
+    done = done || !(off > 1e-30 * dg);
+    if (!__syncthreads_or(!done)) break;
     for (int r = 0; r < 11; r++) {
       if (lane < 6) {
         int p, q;
@@ -395,7 +399,8 @@ __device__ void epnp_group(const PtSet &S, bool active, EpnpShared &sh, int lane
         nv[m] = fj ? cj * sh.V[12 * i + j] - sj * sh.V[12 * i + pj] : sj * sh.V[12 * i + pj] + cj * sh.V[12 * i + j];
       }
       __syncthreads();
-      for (int m = 0; m < 9; m++) sh.A[lane + kGroup * m] = na[m], sh.V[lane + kGroup * m] = nv[m];
+      if (!done)  // (only the write-back is guarded: a guard on the loops above costs the kernel scratch)
+        for (int m = 0; m < 9; m++) sh.A[lane + kGroup * m] = na[m], sh.V[lane + kGroup * m] = nv[m];
       __syncthreads();
     }
   }
