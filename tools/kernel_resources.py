@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """VGPR / scratch / LDS / occupancy per kernel of one HIP source
 (hipcc -Rpass-analysis=kernel-resource-usage).
-usage: tools/kernel_resources.py vo_slam_test_amd/csrc/ba.hip [extra hipcc flags]"""
+usage: tools/kernel_resources.py vo_slam_test_amd/csrc/ba.hip [extra hipcc flags]   (any unit: pose_only.hip, sim3.hip, chol.hip, ...)"""
 import re, subprocess, sys
 src, extra = sys.argv[1], sys.argv[2:]
 cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", *extra,

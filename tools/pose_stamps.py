@@ -1,5 +1,5 @@
-"""Developer tool (GPU box): where the cycles of a pose-only LM iteration go.  Needs a -DVO_POSE_STAMPS build of csrc/ba.hip
-(tools/build_variant_src.sh stamps ba vo_slam_test_amd/csrc/ba.hip -DVO_POSE_STAMPS; VO_HIP_LIB=.../libvo_stamps.so): the
+"""Developer tool (GPU box): where the cycles of a pose-only LM iteration go.  Needs a -DVO_POSE_STAMPS build of csrc/pose_only.hip
+(tools/build_variant_src.sh stamps pose_only vo_slam_test_amd/csrc/pose_only.hip -DVO_POSE_STAMPS; VO_HIP_LIB=.../libvo_stamps.so): the
 summary fields then carry shader-clock cycles per phase, summed over the iterations of a round.
 usage: VO_HIP_LIB=vo_slam_test_amd/_variants/libvo_stamps.so python tools/pose_stamps.py [n_frames]"""
 import ctypes, pathlib, sys

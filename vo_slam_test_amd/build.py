@@ -26,6 +26,8 @@ SOURCES = [
     ("track.hip", ["-ffp-contract=off"]),
     ("tracker.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-ffp-contract=fast"]),
+    ("pose_only.hip", ["-ffp-contract=fast"]),
+    ("sim3.hip", ["-ffp-contract=fast"]),
     ("pose_graph.hip", ["-ffp-contract=fast"]),
     ("chol.hip", ["-ffp-contract=fast"]),
     ("loop.hip", ["-ffp-contract=off"]),

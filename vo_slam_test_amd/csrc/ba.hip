@@ -1,7 +1,9 @@
-// ba.hip -- pose-only and local bundle adjustment on gfx950 (MI355X), FP64.
-// Replaces myslam::Optimizer::solvePoseOnlySE3 / solveLocalBAPoseAndPoint (reference
-// src/optimizer_ceres.cpp:157-314, 446-808) together with the Ceres solve they delegate to
-// (TrustRegionMinimizer + LevenbergMarquardtStrategy + DENSE_SCHUR; contract in DESIGN.md).
+// ba.hip -- local bundle adjustment on gfx950 (MI355X), FP64: LDS-sized problems, the large / sharded path of a global
+// bundle adjustment, the vo_ba handle and every vo_ba_* entry point.
+// Replaces myslam::Optimizer::solveLocalBAPoseAndPoint (reference src/optimizer_ceres.cpp:446-808) together with the
+// Ceres solve it delegates to (TrustRegionMinimizer + LevenbergMarquardtStrategy + DENSE_SCHUR; contract in DESIGN.md).
+// The pose-only solver is pose_only.hip, the Sim3 refinement sim3.hip; the reductions and the hand-off they share with
+// this file are wave_ops.h.
 //
 // Device-resident LM: every iteration is a fixed sequence of kernels whose control decisions
 // (accept / reject, radius, convergence) live in a small state struct in HBM, so the host never
@@ -20,9 +22,9 @@
 //   k_ba_reduce2 / k_ba_update  (sharded) second payload and trust-region bookkeeping
 #include "ba_math.h"
 #include "vo_common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <map>
 #include <numeric>
@@ -33,965 +35,6 @@ namespace {
 
 using namespace vo;
 using namespace vo::ba;
-
-// ============================================================================================
-// block reductions (fixed order => deterministic)
-// ============================================================================================
-// 64-lane sum, same value in every lane.  The four in-row steps are DPP moves of the two 32-bit halves (no LDS
-// crossbar, a fraction of a ds_bpermute's latency); the cross-row steps use v_readlane of the row sums.  Fixed order.
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)u, CTRL, 0xf, 0xf, false);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(u >> 32), CTRL, 0xf, 0xf, false);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double readlane_f64(double v, int l) {
-  const unsigned long long u = __double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)u, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(u >> 32), l);
-  return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-__device__ __forceinline__ double wave_sum(double v) {
-  v += dpp_f64<0xB1>(v);   // quad_perm [1,0,3,2]
-  v += dpp_f64<0x4E>(v);   // quad_perm [2,3,0,1]
-  v += dpp_f64<0x141>(v);  // row_half_mirror
-  v += dpp_f64<0x140>(v);  // row_mirror: every lane holds its row's sum
-  return (readlane_f64(v, 0) + readlane_f64(v, 16)) + (readlane_f64(v, 32) + readlane_f64(v, 48));
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  return v;
-}
-#ifdef VO_BA_STAMPS
-// time stamp that cannot move above the computation of `dep`
-__device__ __forceinline__ unsigned long long stamp_after(double &dep) {
-  unsigned long long t;
-  asm volatile("s_memrealtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t), "+v"(dep)::"memory");
-  return t;
-}
-#endif
-template <int N, int NW = 0>  // NW: wavefronts per block when known at compile time (0: blockDim.x / 64)
-__device__ __forceinline__ void block_sum(double (&v)[N], double *lds /*>= nw*N*/) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < N; i++) v[i] = wave_sum(v[i]);
-  const int nw = NW ? NW : (int)(blockDim.x >> 6);
-  if (nw == 1) return;  // one wavefront: the wave sum is the block sum (no LDS, no barrier)
-  __syncthreads();
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < N; i++) lds[wave * N + i] = v[i];
-  }
-  __syncthreads();
-  // all partials are read in one batch and summed in wave order (a runtime loop over the waves waits for LDS once
-  // per term: 4 us for 27 sums)
-  if (NW == 8 || (NW == 0 && nw == 8)) {
-    double p[8][N];
-#pragma unroll
-    for (int w = 0; w < 8; w++)
-#pragma unroll
-      for (int i = 0; i < N; i++) p[w][i] = lds[w * N + i];
-#pragma unroll
-    for (int i = 0; i < N; i++)
-      v[i] = (((((((0.0 + p[0][i]) + p[1][i]) + p[2][i]) + p[3][i]) + p[4][i]) + p[5][i]) + p[6][i]) + p[7][i];
-    return;
-  }
-  if (NW == 2 || (NW == 0 && nw == 2)) {
-    double p[2][N];
-#pragma unroll
-    for (int w = 0; w < 2; w++)
-#pragma unroll
-      for (int i = 0; i < N; i++) p[w][i] = lds[w * N + i];
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] = (0.0 + p[0][i]) + p[1][i];
-    return;
-  }
-  if (NW == 4 || (NW == 0 && nw == 4)) {
-    double p[4][N];
-#pragma unroll
-    for (int w = 0; w < 4; w++)
-#pragma unroll
-      for (int i = 0; i < N; i++) p[w][i] = lds[w * N + i];
-#pragma unroll
-    for (int i = 0; i < N; i++) v[i] = (((0.0 + p[0][i]) + p[1][i]) + p[2][i]) + p[3][i];
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double s = 0;
-    for (int w = 0; w < nw; w++) s += lds[w * N + i];
-    v[i] = s;
-  }
-}
-
-// Inter-workgroup hand-off ("last block reduces") without fences, MI355X guide Guideline 16 form
-// R1: EVERY handed-off byte is stored write-through (agent-scope relaxed atomic store = `sc1`) and
-// loaded with an agent-scope relaxed atomic load (`sc1`, bypasses this CU's L1); every storing wave
-// drains its stores (s_waitcnt vmcnt(0)), the block barriers, one lane takes a ticket with a relaxed
-// agent-scope add.  The block that draws the last ticket reads the others' data.  Placement
-// independent: per-XCD L2s are not coherent and a CU's L1 is never refreshed by other CUs.
-__device__ __forceinline__ void st_sc1(double *p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __double_as_longlong(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_sc1(const double *p) {
-  return __longlong_as_double(__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT));
-}
-__device__ __forceinline__ bool arrive_and_check_last(unsigned int *counter, unsigned int expected, int *s_flag) {
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int last = (t == expected - 1u);
-    if (last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // re-arm
-    *s_flag = last;
-  }
-  __syncthreads();
-  return *s_flag != 0;
-}
-
-// ============================================================================================
-// Pose-only BA: Optimizer::solvePoseOnlySE3 (optimizer_ceres.cpp:157-314), one workgroup per frame
-// ============================================================================================
-struct PoseLm {
-  double radius, decrease, x_cost, x_norm;
-  int iterations, accepted, termination;
-};
-
-// A frame's observations (global memory, explicit address space: generic pointers in a struct turn every access
-// into a flat load that waits for both counters).  Round 2 kept the first 768 of them in LDS in a compact form
-// (one wavefront per SIMD cannot hide the latency of a load it waits for right away); with every load of a pass issued
-// four trips ahead of its use the plain reads are as fast (0.284 against 0.286 ms per 1024 frames), and the 148 KB of
-// LDS per CU the cache took go to the extraction kernels that run next to the solve (tracked step 4.39 -> 4.14 ms).
-#define VO_GLOBAL __attribute__((address_space(1)))
-constexpr int kPoseNd = 4;  // trips of 64 observations per register set of the one-wavefront pass (5 / 6: spills, round 3)
-struct ObsView {
-  const VO_GLOBAL double *pts, *obs, *isg;
-  VO_GLOBAL uint8_t *outlier;  // the result, and the skip mask of a pass
-  __device__ __forceinline__ void get(int i, double (&p)[3], double &ou, double &ov, double &our, double &is) const {
-    p[0] = pts[3 * i], p[1] = pts[3 * i + 1], p[2] = pts[3 * i + 2];
-    ou = obs[3 * i], ov = obs[3 * i + 1], our = obs[3 * i + 2];
-    is = isg[i];
-  }
-};
-
-// One observation's contribution to H (upper 21), g (6) and the cost; unscaled, loss-corrected.
-//
-// The pose Jacobian of edge_eval factors as J = A [I | X]: A = d r / d pc (rows u [a 0 c], v [0 b d], uR [a 0 e]) and
-// X = -[pc]x, so with M = rho1 A^T A (3 x 3, M01 = 0) and m = rho1 A^T r
-//     H += [ M    M X   ]      g += [ m     ]
-//          [ .  X^T M X ]           [ X^T m ]
-// and every column of X has two non-zeros: 15 + 14 + 12 multiply-adds and 14 adds for H (the dense row products of the
-// 2-3 x 6 Jacobian: 60 + 15), the rotation half of J is never formed.
-__device__ __forceinline__ void pose_obs_term(const PoseCache &P, const double (&pw)[3], double ou, double ov, double our,
-                                              double is, const Cam &K, double hm, double hs, double (&acc)[28]) {
-  // R p + t as three multiply-add chains that start from t (trans_point adds t last: a multiply and an add more per row)
-  const double x = __builtin_fma(P.R[0], pw[0], __builtin_fma(P.R[1], pw[1], __builtin_fma(P.R[2], pw[2], P.t[0])));
-  const double y = __builtin_fma(P.R[3], pw[0], __builtin_fma(P.R[4], pw[1], __builtin_fma(P.R[5], pw[2], P.t[1])));
-  const double z = __builtin_fma(P.R[6], pw[0], __builtin_fma(P.R[7], pw[1], __builtin_fma(P.R[8], pw[2], P.t[2])));
-  const double invz = inv_fast(z), invz2 = invz * invz;
-  const bool stereo = !(our < 0);
-  const double uhat = K.fx * x * invz + K.cx;
-  const double r0 = (ou - uhat) * is;
-  const double r1 = (ov - (K.fy * y * invz + K.cy)) * is;
-  const double r2 = stereo ? (our - (uhat - K.bf * invz)) * is : 0.0;
-  const double a = -invz * K.fx, b = -invz * K.fy, c = x * invz2 * K.fx, d = y * invz2 * K.fy;  // Jp[0], [7], [2], [8]
-  const double a2 = stereo ? a : 0.0, e = stereo ? c - K.bf * invz2 : 0.0;                        // Jp[12], [14]
-  const double s = r0 * r0 + r1 * r1 + r2 * r2;
-  double rho0, rho1;
-  huber(stereo ? hs : hm, s, rho0, rho1);
-  acc[27] += 0.5 * rho0;
-  const double wa = rho1 * a, wa2 = rho1 * a2, wb = rho1 * b, wc = rho1 * c, wd = rho1 * d, we = rho1 * e;
-  const double M00 = __builtin_fma(wa, a, wa2 * a2), M02 = __builtin_fma(wa, c, wa2 * e), M11 = wb * b, M12 = wb * d;
-  const double M22 = __builtin_fma(wc, c, __builtin_fma(wd, d, we * e));
-  const double m0 = __builtin_fma(wa, r0, wa2 * r2), m1 = wb * r1, m2 = __builtin_fma(wc, r0, __builtin_fma(wd, r1, we * r2));
-  // M X, X = [[0 z -y] [-z 0 x] [y -x 0]]
-  const double X00 = y * M02, X10 = __builtin_fma(y, M12, -(z * M11)), X20 = __builtin_fma(y, M22, -(z * M12));
-  const double X01 = __builtin_fma(z, M00, -(x * M02)), X11 = -(x * M12), X21 = __builtin_fma(z, M02, -(x * M22));
-  const double X02 = -(y * M00), X12 = x * M11, X22 = __builtin_fma(x, M12, -(y * M02));
-  // packed upper triangle, row by row: (0,b) 0..5, (1,b) 6..10, (2,b) 11..14, (3,b) 15..17, (4,b) 18..19, (5,5) 20
-  acc[0] += M00, acc[2] += M02, acc[6] += M11, acc[7] += M12, acc[11] += M22;
-  acc[3] += X00, acc[4] += X01, acc[5] += X02;
-  acc[8] += X10, acc[9] += X11, acc[10] += X12;
-  acc[12] += X20, acc[13] += X21, acc[14] += X22;
-  // X^T (M X): column a of X against column b of M X
-  acc[15] = __builtin_fma(y, X20, __builtin_fma(-z, X10, acc[15]));
-  acc[16] = __builtin_fma(y, X21, __builtin_fma(-z, X11, acc[16]));
-  acc[17] = __builtin_fma(y, X22, __builtin_fma(-z, X12, acc[17]));
-  acc[18] = __builtin_fma(z, X01, __builtin_fma(-x, X21, acc[18]));
-  acc[19] = __builtin_fma(z, X02, __builtin_fma(-x, X22, acc[19]));
-  acc[20] = __builtin_fma(x, X12, __builtin_fma(-y, X02, acc[20]));
-  acc[21] += m0, acc[22] += m1, acc[23] += m2;
-  acc[24] = __builtin_fma(y, m2, __builtin_fma(-z, m1, acc[24]));
-  acc[25] = __builtin_fma(z, m0, __builtin_fma(-x, m2, acc[25]));
-  acc[26] = __builtin_fma(x, m1, __builtin_fma(-y, m0, acc[26]));
-}
-
-// A batch of observations of the one-wavefront form: ND trips of 64, in registers.
-struct PoseOb { double pw[3], ou, ov, our, is; unsigned skip; };
-// The loads take the wave-uniform bases from scalar registers and a 32-bit byte offset per lane (an int index costs
-// twelve 64-bit address operations per observation); unconditional, the raw flag byte included: a bool would be
-// compared, i.e. waited for, where it is loaded.
-__device__ __forceinline__ void pose_request(const ObsView &V, unsigned base, unsigned last, PoseOb (&o)[kPoseNd]) {
-  const unsigned lane = threadIdx.x;
-  const VO_GLOBAL char *bp = (const VO_GLOBAL char *)V.pts, *bo = (const VO_GLOBAL char *)V.obs, *bi = (const VO_GLOBAL char *)V.isg;
-  const VO_GLOBAL uint8_t *bs = V.outlier;
-#pragma unroll
-  for (int k = 0; k < kPoseNd; k++) {
-    const unsigned i = min(base + 64u * k + lane, last);  // past the end: a harmless re-read
-    const unsigned o24 = __umul24(i, 24u), o8 = i * 8u;  // (v_mul_lo_u32 is a quarter-rate instruction)
-    o[k].pw[0] = *(const VO_GLOBAL double *)(bp + o24), o[k].pw[1] = *(const VO_GLOBAL double *)(bp + o24 + 8);
-    o[k].pw[2] = *(const VO_GLOBAL double *)(bp + o24 + 16);
-    o[k].ou = *(const VO_GLOBAL double *)(bo + o24), o[k].ov = *(const VO_GLOBAL double *)(bo + o24 + 8);
-    o[k].our = *(const VO_GLOBAL double *)(bo + o24 + 16);
-    o[k].is = *(const VO_GLOBAL double *)(bi + o8);
-    o[k].skip = bs[i];
-  }
-}
-
-// One linearisation pass over the observations that are not flagged.  WAVE (one wavefront per frame, nothing else on
-// its SIMD to run while a load is in flight): observations travel in batches of four trips, one batch ahead of their
-// use, into two register sets that swap roles in a loop unrolled by two (no "next becomes current" copies: 14 moves
-// per observation).  `first` holds batch 0 on entry -- requested by the previous pass behind its last trip, so that it
-// travels during the reduction and the 6 x 6 solve (the observations of a round do not change; a pass that requests
-// its own first batch waits for it once per LM iteration) -- and again on exit.
-template <bool WAVE>
-__device__ __forceinline__ void pose_accumulate(const PoseCache &P, int n, const ObsView &V, const Cam &K, double hm, double hs,
-                                                double (&acc)[28], PoseOb (&first)[kPoseNd]) {
-#pragma unroll
-  for (int i = 0; i < 28; i++) acc[i] = 0;
-  if (WAVE) {
-    const unsigned lane = threadIdx.x, last = (unsigned)(n - 1);
-    constexpr int ND = kPoseNd;
-    auto eval = [&](unsigned base, const PoseOb (&o)[ND]) {
-#pragma unroll
-      for (int k = 0; k < ND; k++)
-        if (base + 64u * k + lane <= last && !o[k].skip) pose_obs_term(P, o[k].pw, o[k].ou, o[k].ov, o[k].our, o[k].is, K, hm, hs, acc);
-    };
-    PoseOb B[ND];
-#pragma unroll 1
-    for (unsigned base = 0; base <= last; base += 2 * ND * 64) {
-      pose_request(V, base + ND * 64, last, B);
-      eval(base, first);
-      const unsigned nb = base + 2 * ND * 64;
-      pose_request(V, nb > last ? 0u : nb, last, first);  // behind the last trip: batch 0 for the next pass (0.2275 -> 0.2235 ms)
-      eval(base + ND * 64, B);  // (a batch wholly past the end evaluates nothing: every lane fails the range test)
-    }
-    return;
-  }
-#pragma unroll 1
-  for (int i = threadIdx.x; i < n; i += (int)blockDim.x) {
-    if (V.outlier[i]) continue;
-    double pw[3], ou, ov, our, is;
-    V.get(i, pw, ou, ov, our, is);
-    pose_obs_term(P, pw, ou, ov, our, is, K, hm, hs, acc);
-  }
-}
-
-// 6 x 6 SPD solve on the packed lower triangle (row by row: 00 10 11 20 21 22 ...), in place; b := A^-1 b.  Fully
-// unrolled (every index a compile-time constant: the 21 + 6 + 6 values stay in registers); no divide and no square
-// root: per column one Newton-refined v_rsq_f64 (an ulp or two from 1 / sqrt(d), like the per-observation arithmetic),
-// the column and both substitutions multiply by it -- 6 reciprocal square roots instead of 6 IEEE square roots and 33 IEEE
-// divides (about 1000 of the 3600 instructions an LM iteration spent outside the observation loop).
-__device__ __forceinline__ constexpr int tri_l(int i, int j) { return i * (i + 1) / 2 + j; }            // j <= i
-__device__ __forceinline__ constexpr int tri_u(int a, int b) { return a * 6 - a * (a - 1) / 2 + (b - a); }  // a <= b
-__device__ __forceinline__ bool chol6_packed(double (&L)[21], double (&b)[6]) {
-  double ri[6];  // 1 / L[j][j]
-#pragma unroll
-  for (int j = 0; j < 6; j++) {
-    double d = L[tri_l(j, j)];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= L[tri_l(j, k)] * L[tri_l(j, k)];
-    if (!(d > 0.0)) return false;
-    ri[j] = rsqrt_fast(d);
-#pragma unroll
-    for (int i = j + 1; i < 6; i++) {
-      double t = L[tri_l(i, j)];
-#pragma unroll
-      for (int k = 0; k < j; k++) t -= L[tri_l(i, k)] * L[tri_l(j, k)];
-      L[tri_l(i, j)] = t * ri[j];
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double t = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) t -= L[tri_l(i, k)] * b[k];
-    b[i] = t * ri[i];
-  }
-#pragma unroll
-  for (int i = 5; i >= 0; i--) {
-    double t = b[i];
-#pragma unroll
-    for (int k = i + 1; k < 6; k++) t -= L[tri_l(k, i)] * b[k];
-    b[i] = t * ri[i];
-  }
-  return true;
-}
-
-__device__ __forceinline__ void wave_lds_sync() {  // LDS hand-off between lanes of one wavefront
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// 64 lanes x 28 partial sums -> 28 totals at dst (LDS), in a fixed order: a transpose through LDS instead of 28 x 6
-// DPP / readlane steps (about 110 instructions for what those did in 1000).  Layout: value-major, scratch[k][lane] at a
-// pitch of kPoseRedPitch doubles -- a lane's stores of one value land on consecutive doubles across the wavefront.
-//   ONE_PASS (the one-wavefront kernel, round 5): all 28 values in one trip: lane 2 v + h sums rows h, h + 2, ... of value v
-//   (32 loads in flight, a pairwise tree), the halves meet by one quad permute.  Pitch 66: the reads of a half-wave fall on
-//   banks 4 v + 4 j + 2 h (mod 64), all distinct.  One store / hand-off / load / hand-off chain per linearisation instead of two.
-//   Two passes of 14 values (the 256-thread form: four scratch areas must fit next to each other): lane 4 v + q sums rows
-//   q, q + 4, ..., two quad permutes; pitch 68: banks 8 v + 2 q + 8 j, distinct inside each half-wave (the lane-major
-//   [64][15] layout of round 3 read two-way conflicted: 49 % of the kernel's LDS cycles).
-// The hand-offs wait for LDS only where it matters: a wavefront-scope fence also waits for vmcnt(0).
-template <bool ONE_PASS>
-struct PoseRed {
-  static constexpr int kPitch = ONE_PASS ? 66 : 68;
-  static constexpr int kScratch = (ONE_PASS ? 28 : 14) * kPitch;
-};
-__device__ __forceinline__ void wave_lds_handoff() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // LDS only: the next pass's first batch stays in flight
-  __builtin_amdgcn_wave_barrier();
-}
-template <bool ONE_PASS>
-__device__ __forceinline__ void wave_reduce28(const double (&v)[28], double *scratch, double *dst) {
-  constexpr int P = PoseRed<ONE_PASS>::kPitch;
-  const int lane = threadIdx.x & 63;
-  if (ONE_PASS) {
-    const int vi = lane >> 1, h = lane & 1;
-#pragma unroll
-    for (int k = 0; k < 28; k++) scratch[k * P + lane] = v[k];
-    wave_lds_handoff();
-    double t = 0;
-    if (lane < 56) {
-      double u[32];
-#pragma unroll
-      for (int j = 0; j < 32; j++) u[j] = scratch[vi * P + 2 * j + h];
-#pragma unroll
-      for (int w = 16; w >= 1; w >>= 1)
-#pragma unroll
-        for (int j = 0; j < w; j++) u[j] += u[j + w];
-      t = u[0];
-    }
-    t += dpp_f64<0xB1>(t);  // quad_perm [1,0,3,2]
-    if (lane < 56 && h == 0) dst[vi] = t;
-    wave_lds_handoff();
-    return;
-  }
-  const int vi = lane >> 2, q = lane & 3;
-#pragma unroll
-  for (int c = 0; c < 2; c++) {
-#pragma unroll
-    for (int k = 0; k < 14; k++) scratch[k * P + lane] = v[14 * c + k];
-    wave_lds_handoff();
-    double t = 0;
-    if (lane < 56) {
-      // all sixteen loads in flight before the first add (a running sum over loads waits for LDS once per term),
-      // summed pairwise in a fixed order
-      double u[16];
-#pragma unroll
-      for (int j = 0; j < 16; j++) u[j] = scratch[vi * P + 4 * j + q];
-#pragma unroll
-      for (int w = 8; w >= 1; w >>= 1)
-#pragma unroll
-        for (int j = 0; j < w; j++) u[j] += u[j + w];
-      t = u[0];
-    }
-    t += dpp_f64<0xB1>(t);  // quad_perm [1,0,3,2]
-    t += dpp_f64<0x4E>(t);  // quad_perm [2,3,0,1]
-    if (lane < 56 && q == 0) dst[14 * c + vi] = t;
-    wave_lds_handoff();
-  }
-}
-
-// LDS doubles of a pose-only workgroup behind the observation cache: the reduction scratch, the linearisation at x
-// and at the candidate
-template <bool WAVE>
-struct PoseLds {
-  static constexpr int kScratch = PoseRed<WAVE>::kScratch;
-  static constexpr int kRed = WAVE ? kScratch : 4 * kScratch + 4 * 28;  // per-wave scratch, then the wave totals
-  double red[kRed];
-  double acc[28];   // linearisation at x: 21 + 6 + 1 sums, uniform over the workgroup
-  double cand[28];  // ... at the trial point
-};
-
-// -DVO_POSE_STAMPS (tools/pose_stamps.py): shader-clock cycles per phase of the LM loop, summed over the iterations and
-// handed back in the summary's fields (initial_cost = solve, final_cost = plus, final_radius = pass, reserved = reduction,
-// accepted = tests) -- a developer build, never the product.
-#ifdef VO_POSE_STAMPS
-#define POSE_STAMP(slot, dep)                                                                            \
-  do {                                                                                                   \
-    unsigned long long t_;                                                                               \
-    asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(t_), "+v"(dep)::"memory");                 \
-    if ((slot) >= 0) st_[(slot) < 0 ? 0 : (slot)] += t_ - tp_;                                           \
-    tp_ = t_;                                                                                            \
-  } while (0)
-#else
-#define POSE_STAMP(slot, dep) do { } while (0)
-#endif
-
-// Ceres-style LM on one 6-dof pose.  The linearisations -- 21 + 6 + 1 sums each -- live in LDS, not in registers: a
-// trial step accumulates the candidate's sums while the solve's temporaries are dead and vice versa (round 2 kept
-// two sets of 28 accumulators next to a 6 x 6 system in every lane: 256 VGPR + 251 AGPR).  Every thread carries the
-// (uniform) trust-region scalars in registers.
-template <bool WAVE>
-__device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, double hm, double hs, int max_it, PoseLds<WAVE> &S,
-                        vo_lm_summary *sum) {
-  // exp(x) is kept across the iterations (an accepted candidate's exp is the product se3_plus forms anyway) and the
-  // residuals are evaluated from it: rotation matrix from the unit quaternion, t = V * upsilon -- what
-  // se3TransPoint(x) computes through sin / cos of |omega|, up to rounding; no trigonometry per evaluation.
-  Se3 Tx = se3_exp<true>(x);
-#ifdef VO_POSE_STAMPS
-  unsigned long long st_[5] = {0, 0, 0, 0, 0}, tp_ = 0;
-#endif
-  bool in_loop_ = false;  // (stamps)
-  PoseOb first[kPoseNd];  // batch 0 of the next pass (one-wavefront form)
-  if (WAVE) pose_request(V, 0, (unsigned)(n - 1), first);
-  auto linearize = [&](const Se3 &T, double *dst) {  // sums of the linearisation at T -> dst (LDS)
-    double v[28];
-    pose_accumulate<WAVE>(pose_cache_se3(T), n, V, K, hm, hs, v, first);
-    POSE_STAMP(in_loop_ ? 2 : -1, v[27]);
-    if (WAVE) {
-      wave_reduce28<true>(v, S.red, dst);
-    } else {
-      // every wavefront reduces its lanes through its own scratch (the same transpose as the one-wavefront kernel: a
-      // tenth of the instructions of 28 DPP / readlane sums -- this path is the latency of ONE frame), then 28 threads add
-      // the wave totals in wave order
-      const int wave = threadIdx.x >> 6, nw = (int)blockDim.x >> 6;
-      constexpr int kS = PoseLds<WAVE>::kScratch;
-      double *tot = S.red + 4 * kS;
-      __syncthreads();  // the previous pass's totals have been read
-      wave_reduce28<false>(v, S.red + wave * kS, tot + wave * 28);
-      __syncthreads();
-      if (threadIdx.x < 28) {
-        double t = 0;
-        for (int w = 0; w < nw; w++) t += tot[w * 28 + threadIdx.x];
-        dst[threadIdx.x] = t;
-      }
-      __syncthreads();
-    }
-  };
-  // the linearisation at x and the one at the candidate swap roles when a step is accepted (no copy)
-  double *cur = S.acc, *cnd = S.cand;
-  linearize(Tx, cur);
-  double scale[6];
-#pragma unroll
-  for (int a = 0; a < 6; a++) scale[a] = 1.0 / (1.0 + sqrt(cur[tri_u(a, a)]));
-  // The trust-region scalars: radius and decrease with their reciprocals next to them (decrease is a power of two, so
-  // radius * inv_decrease is the quotient exactly; 1 / radius is refreshed when an accepted step changes the radius) --
-  // the damping of an iteration is six multiplications, not six IEEE divisions in front of the factorisation.
-  double radius = 1e4, inv_radius = 1e-4, decrease = 2.0, inv_decrease = 0.5, x_cost = cur[27];
-  const double initial_cost = x_cost;
-  auto norm6 = [](const double (&v)[6]) {
-    const double s2 = v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3] + v[4] * v[4] + v[5] * v[5];
-    return s2 > 1e-280 ? s2 * rsqrt_fast(s2) : 0.0;  // (|x| below 1e-140 counts as zero: the test adds 1e-8 to it)
-  };
-  double x_norm;
-  {
-    const double xv[6] = {x[0], x[1], x[2], x[3], x[4], x[5]};
-    x_norm = norm6(xv);
-  }
-  int iterations = 0, accepted = 0, termination = 0, invalid = 0;
-  bool last_ok = false;
-  for (int it = 1;; it++) {
-    if (it - 1 >= max_it) {
-      termination = 0;
-      break;
-    }
-    in_loop_ = true;
-    POSE_STAMP(-1, x_cost);
-    double h[27];  // one batch of LDS reads: the gradient test and the normal equations use the same values
-#pragma unroll
-    for (int i = 0; i < 27; i++) h[i] = cur[i];
-    if (last_ok) {
-      double gm = 0;
-#pragma unroll
-      for (int a = 0; a < 6; a++) gm = fmax(gm, fabs(h[21 + a]));
-      if (gm <= 1e-10) {
-        termination = 3;
-        break;
-      }
-    }
-    if (radius < 1e-32) {
-      termination = 4;
-      break;
-    }
-    iterations = it;
-    last_ok = false;
-    // scaled normal equations  H'' = S H S, g'' = S g ; LM diagonal from clamp(diag H'')/radius
-    double L[21], g[6], y[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-#pragma unroll
-      for (int b2 = 0; b2 <= a; b2++) L[tri_l(a, b2)] = h[tri_u(b2, a)] * scale[b2] * scale[a];
-      g[a] = h[21 + a] * scale[a];
-      y[a] = g[a];
-    }
-    double model = 0, delta[6];
-    {
-      // step^T H'' step from the undamped matrix, before the factorisation overwrites it
-      double Hs[21];
-#pragma unroll
-      for (int i = 0; i < 21; i++) Hs[i] = L[i];
-#pragma unroll
-      for (int a = 0; a < 6; a++) L[tri_l(a, a)] += fmin(fmax(L[tri_l(a, a)], 1e-6), 1e32) * inv_radius;
-      bool ok = chol6_packed(L, y);
-      if (ok) {
-        double gs = 0, sHs = 0;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-          if (!isfinite(y[a])) ok = false;
-#pragma unroll
-        for (int a = 0; a < 6; a++) {
-          gs -= g[a] * y[a];  // step = -y
-          double row = 0;
-#pragma unroll
-          for (int b2 = 0; b2 < 6; b2++) row += Hs[a >= b2 ? tri_l(a, b2) : tri_l(b2, a)] * y[b2];
-          sHs += y[a] * row;
-          delta[a] = -y[a] * scale[a];
-        }
-        model = -(gs + 0.5 * sHs);  // -m.(r + m/2) with m = J''step
-      }
-      if (!ok || !(model > 0.0)) {
-        if (++invalid >= 5) {
-          termination = 4;
-          break;
-        }
-        radius *= inv_decrease, inv_radius *= decrease;
-        decrease *= 2.0, inv_decrease *= 0.5;
-        continue;
-      }
-    }
-    invalid = 0;
-    POSE_STAMP(0, model);
-    double xc[6];
-    Se3 Tc;
-    se3_plus_keep(Tx, delta, xc, Tc);
-    POSE_STAMP(1, xc[0]);
-    // The candidate is linearised completely in the same pass (its cost is one of the 28 sums): an
-    // accepted step -- the common case -- then needs no second sweep over the observations.
-    linearize(Tc, cnd);
-    double cand = cnd[27];
-    POSE_STAMP(3, cand);
-    if (!isfinite(cand)) cand = 1.7976931348623157e308;
-    double sn = 0;
-#pragma unroll
-    for (int a = 0; a < 6; a++) sn += (x[a] - xc[a]) * (x[a] - xc[a]);
-    {
-      const double tol = 1e-8 * (x_norm + 1e-8);  // |step| <= tol, compared as squares (no square root)
-      if (sn <= tol * tol) {
-        termination = 2;
-        break;
-      }
-    }
-    const double change = x_cost - cand;
-    if (fabs(change) <= 1e-6 * x_cost) {
-      termination = 1;
-      break;
-    }
-    const double rel = change * inv_fast(model);
-    if (rel > 1e-3) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) x[a] = xc[a];
-      Tx = Tc;
-      x_norm = norm6(xc);
-      double *t = cur;
-      cur = cnd, cnd = t;  // the candidate's linearisation becomes the current one
-      x_cost = cand;
-      const double t2 = 2.0 * rel - 1.0;
-      radius = fmin(radius * inv_fast(fmax(1.0 / 3.0, 1.0 - t2 * t2 * t2)), 1e16);
-      inv_radius = inv_fast(radius);
-      decrease = 2.0, inv_decrease = 0.5;
-      accepted++;
-      last_ok = true;
-    } else {
-      radius *= inv_decrease, inv_radius *= decrease;
-      decrease *= 2.0, inv_decrease *= 0.5;
-    }
-    POSE_STAMP(4, radius);
-  }
-  if (sum && threadIdx.x == 0) {
-    sum->iterations = iterations;
-    sum->accepted = accepted;
-    sum->termination = termination;
-    sum->reserved = 0;
-    sum->initial_cost = initial_cost;
-    sum->final_cost = x_cost;
-    sum->final_radius = radius;
-#ifdef VO_POSE_STAMPS
-    sum->initial_cost = (double)st_[0], sum->final_cost = (double)st_[1], sum->final_radius = (double)st_[2];
-    sum->reserved = (int)st_[3], sum->accepted = (int)st_[4];
-#endif
-  }
-}
-
-// float chi2 test of optimizer_ceres.cpp:262-303 (Q-B2: deliberately float)
-__device__ __forceinline__ bool pose_chi2_outlier(const double pc[3], double ou, double ov, double our, float fx,
-                                                  float fy, float cx, float cy, float bf, double isg) {
-  const double x = pc[0], y = pc[1], z = pc[2];
-  const float invz = (float)(1.0f / z);
-  const float u = (float)(fx * x * invz + cx);
-  const float v = (float)(fy * y * invz + cy);
-  const float eu = (float)(u - ou), ev = (float)(v - ov);
-  const float e2 = eu * eu + ev * ev;
-  const float is2 = (float)(isg * isg);
-  if (our < 0) return !(e2 * is2 < 5.991f);
-  const float ur = u - bf * invz;
-  const float eur = (float)(ur - our);
-  return !((e2 + eur * eur) * is2 < 7.815f);
-}
-
-// ranges != 0: problem p owns observations [offsets[2p], offsets[2p] + offsets[2p+1]) (frames at a fixed stride,
-// vo_track_gather_dev); otherwise [offsets[p], offsets[p+1]).  WAVE: one wavefront per problem (batches); otherwise
-// 128 or 256 threads per problem (a few problems: the observations are shared out).
-template <bool WAVE>
-__global__ __launch_bounds__(WAVE ? 64 : 256) void k_pose_only(const int *offsets, const double *pts, const double *obs,
-                                                               const double *isg, const double *cam5, double *poses,
-                                                               uint8_t *outlier, int *n_inliers, vo_lm_summary *sums,
-                                                               int ranges) {
-  __shared__ PoseLds<WAVE> S;
-  __shared__ int s_cnt[4];
-  const int p = blockIdx.x;
-  if (threadIdx.x < 4) s_cnt[threadIdx.x] = 0;  // (workgroups of one wavefront leave three of the four slots unused)
-  const int o0 = ranges ? offsets[2 * p] : offsets[p], n = ranges ? offsets[2 * p + 1] : offsets[p + 1] - o0;
-  pts += 3 * (long long)o0, obs += 3 * (long long)o0, isg += o0, outlier += o0;
-  Cam K{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
-  const float fx = (float)K.fx, fy = (float)K.fy, cx = (float)K.cx, cy = (float)K.cy, bf = (float)K.bf;
-  double x0[6], x[6];
-  for (int a = 0; a < 6; a++) x0[a] = x[a] = poses[6 * p + a];
-  if (n <= 0) {  // :204-205
-    if (threadIdx.x == 0) n_inliers[p] = 0;
-    return;
-  }
-  const ObsView V{(const VO_GLOBAL double *)pts, (const VO_GLOBAL double *)obs, (const VO_GLOBAL double *)isg, (VO_GLOBAL uint8_t *)outlier};
-  const int stride = WAVE ? 64 : (int)blockDim.x;
-  for (int i = threadIdx.x; i < n; i += stride) outlier[i] = 0;
-  __syncthreads();
-  int inl = 0;
-  for (int round = 0; round < 2; round++) {
-    for (int a = 0; a < 6; a++) x[a] = x0[a];  // :215
-    const double hm = round == 0 ? (double)sqrtf(5.991f) : 0.0;
-    const double hs = round == 0 ? (double)sqrtf(7.815f) : 0.0;
-    pose_lm<WAVE>(x, n, V, K, hm, hs, 10, S, sums ? &sums[2 * p + round] : nullptr);
-    __syncthreads();
-    // classification with Tcw = exp(pose) (Sophus quaternion form, :256-257)
-    const Se3 T = se3_exp(x);
-    int local = 0;
-#pragma unroll 1
-    for (int i = threadIdx.x; i < n; i += stride) {
-      double rp[3], pc[3], pw[3], ou, ov, our, is;
-      V.get(i, pw, ou, ov, our, is);
-      quat_rotate(T.q, pw, rp);
-      pc[0] = rp[0] + T.t[0], pc[1] = rp[1] + T.t[1], pc[2] = rp[2] + T.t[2];
-      const bool out = pose_chi2_outlier(pc, ou, ov, our, fx, fy, cx, cy, bf, is);
-      outlier[i] = out ? 1 : 0;
-      local += out ? 0 : 1;
-    }
-    for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = local;
-    __syncthreads();
-    inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    __syncthreads();
-    if (inl < 10) {  // :306-307
-      if (round == 0 && sums && threadIdx.x == 0) memset(&sums[2 * p + 1], 0, sizeof(vo_lm_summary));
-      break;
-    }
-  }
-  if (threadIdx.x == 0) {
-    n_inliers[p] = inl;
-    for (int a = 0; a < 6; a++) poses[6 * p + a] = x[a];
-  }
-}
-
-// ============================================================================================
-// Sim3 optimisation of a loop candidate: Optimizer::solveLoopSim3 (optimizer_ceres.cpp:810-1030),
-// one workgroup per problem, same structure as k_pose_only.  NP = 6 (scale fixed, the only mode the
-// reference uses: loopClosing.cpp:15) or 7.
-// ============================================================================================
-struct Sim3Prob {
-  int n;
-  const double *Pm, *pc, *isc, *Pc, *pm, *ism;  // cam_match(3n), pix_curr(2n), 1/sigma, cam_curr(3n), pix_match(2n), 1/sigma
-  const uint8_t *skip;
-  double cam[4];
-  double huber;
-};
-
-template <int NP>
-__device__ void sim3_accumulate(const double x[7], const Sim3Prob &Q, bool want_jac,
-                                double (&acc)[NP * (NP + 1) / 2 + NP + 1]) {
-  constexpr int NH = NP * (NP + 1) / 2;
-#pragma unroll
-  for (int i = 0; i < NH + NP + 1; i++) acc[i] = 0;
-  const Sim3Frame F = sim3_frame(x, want_jac);
-  for (int i = threadIdx.x; i < Q.n; i += blockDim.x) {
-    if (Q.skip && Q.skip[i]) continue;
-    double r[4], J[28];
-    if (want_jac)
-      sim3_eval<true>(F, Q.Pm + 3 * i, Q.pc[2 * i], Q.pc[2 * i + 1], Q.isc[i], Q.Pc + 3 * i, Q.pm[2 * i], Q.pm[2 * i + 1],
-                      Q.ism[i], Q.cam, r, J);
-    else
-      sim3_eval<false>(F, Q.Pm + 3 * i, Q.pc[2 * i], Q.pc[2 * i + 1], Q.isc[i], Q.Pc + 3 * i, Q.pm[2 * i], Q.pm[2 * i + 1],
-                       Q.ism[i], Q.cam, r, nullptr);
-#pragma unroll
-    for (int blk = 0; blk < 2; blk++) {  // each 2-row block has its own loss (two AddResidualBlock calls, :888-895)
-      const double *rb = r + 2 * blk, *Jb = J + 14 * blk;
-      double rho0, rho1;
-      huber(Q.huber, rb[0] * rb[0] + rb[1] * rb[1], rho0, rho1);
-      acc[NH + NP] += 0.5 * rho0;
-      if (!want_jac) continue;
-      int t = 0;
-#pragma unroll
-      for (int a = 0; a < NP; a++) {
-#pragma unroll
-        for (int b = a; b < NP; b++) acc[t++] += rho1 * (Jb[a] * Jb[b] + Jb[7 + a] * Jb[7 + b]);
-        acc[NH + a] += rho1 * (Jb[a] * rb[0] + Jb[7 + a] * rb[1]);
-      }
-    }
-  }
-}
-
-template <int N>
-__device__ bool chol_solve_n(double (&A)[N][N], double (&b)[N]) {
-#pragma unroll
-  for (int j = 0; j < N; j++) {
-    double d = A[j][j];
-#pragma unroll
-    for (int k = 0; k < j; k++) d -= A[j][k] * A[j][k];
-    if (!(d > 0.0)) return false;
-    d = sqrt(d);
-    A[j][j] = d;
-#pragma unroll
-    for (int i = j + 1; i < N; i++) {
-      double v = A[i][j];
-#pragma unroll
-      for (int k = 0; k < j; k++) v -= A[i][k] * A[j][k];
-      A[i][j] = v / d;
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < N; i++) {
-    double v = b[i];
-#pragma unroll
-    for (int k = 0; k < i; k++) v -= A[i][k] * b[k];
-    b[i] = v / A[i][i];
-  }
-#pragma unroll
-  for (int i = N - 1; i >= 0; i--) {
-    double v = b[i];
-#pragma unroll
-    for (int k = i + 1; k < N; k++) v -= A[k][i] * b[k];
-    b[i] = v / A[i][i];
-  }
-  return true;
-}
-
-// Ceres-style LM (same contract as pose_lm) on the first NP entries of x with the plain additive update
-template <int NP>
-__device__ void sim3_lm(double x[7], const Sim3Prob &Q, int max_it, double *lds, vo_lm_summary *sum) {
-  constexpr int NH = NP * (NP + 1) / 2, NA = NH + NP + 1;
-  double acc[NA];
-  sim3_accumulate<NP>(x, Q, true, acc);
-  block_sum<NA>(acc, lds);
-  double scale[NP];
-  {
-    int t = 0;
-#pragma unroll
-    for (int a = 0; a < NP; a++) {
-      scale[a] = 1.0 / (1.0 + sqrt(acc[t]));
-      t += NP - a;
-    }
-  }
-  auto norm_free = [](const double *v) {
-    double q = 0;
-#pragma unroll
-    for (int a = 0; a < NP; a++) q += v[a] * v[a];
-    return sqrt(q);
-  };
-  double radius = 1e4, decrease = 2.0, x_cost = acc[NH + NP];
-  const double initial_cost = x_cost;
-  double x_norm = norm_free(x);
-  int iterations = 0, accepted = 0, termination = 0, invalid = 0;
-  bool last_ok = false;
-  for (int it = 1;; it++) {
-    if (it - 1 >= max_it) {
-      termination = 0;
-      break;
-    }
-    if (last_ok) {
-      double gm = 0;
-#pragma unroll
-      for (int a = 0; a < NP; a++) gm = fmax(gm, fabs(acc[NH + a]));
-      if (gm <= 1e-10) {
-        termination = 3;
-        break;
-      }
-    }
-    if (radius < 1e-32) {
-      termination = 4;
-      break;
-    }
-    iterations = it;
-    last_ok = false;
-    double A[NP][NP], Hs[NP][NP], g[NP], y[NP];
-    {
-      int t = 0;
-#pragma unroll
-      for (int a = 0; a < NP; a++)
-#pragma unroll
-        for (int b = a; b < NP; b++) {
-          const double v = acc[t++] * scale[a] * scale[b];
-          Hs[a][b] = Hs[b][a] = v;
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < NP; a++) {
-      g[a] = acc[NH + a] * scale[a];
-#pragma unroll
-      for (int b = 0; b < NP; b++) A[a][b] = Hs[a][b];
-      A[a][a] += fmin(fmax(Hs[a][a], 1e-6), 1e32) / radius;
-      y[a] = g[a];
-    }
-    bool ok = chol_solve_n<NP>(A, y);
-    double delta[7] = {0, 0, 0, 0, 0, 0, 0}, model = 0;
-    if (ok) {
-      double gs = 0, sHs = 0;
-#pragma unroll
-      for (int a = 0; a < NP; a++)
-        if (!isfinite(y[a])) ok = false;
-#pragma unroll
-      for (int a = 0; a < NP; a++) {
-        gs -= g[a] * y[a];
-        double row = 0;
-#pragma unroll
-        for (int b = 0; b < NP; b++) row -= Hs[a][b] * y[b];
-        sHs -= y[a] * row;
-        delta[a] = -y[a] * scale[a];
-      }
-      model = -(gs + 0.5 * sHs);
-    }
-    if (!ok || !(model > 0.0)) {
-      if (++invalid >= 5) {
-        termination = 4;
-        break;
-      }
-      radius /= decrease;
-      decrease *= 2.0;
-      continue;
-    }
-    invalid = 0;
-    double xc[7];
-#pragma unroll
-    for (int a = 0; a < 7; a++) xc[a] = x[a] + delta[a];
-    double cacc[NA];  // complete linearisation at the candidate (see pose_lm)
-    sim3_accumulate<NP>(xc, Q, true, cacc);
-    block_sum<NA>(cacc, lds);
-    double cand = cacc[NH + NP];
-    if (!isfinite(cand)) cand = 1.7976931348623157e308;
-    double sn = 0;
-#pragma unroll
-    for (int a = 0; a < NP; a++) sn += (x[a] - xc[a]) * (x[a] - xc[a]);
-    if (sqrt(sn) <= 1e-8 * (x_norm + 1e-8)) {
-      termination = 2;
-      break;
-    }
-    const double change = x_cost - cand;
-    if (fabs(change) <= 1e-6 * x_cost) {
-      termination = 1;
-      break;
-    }
-    const double rel = change / model;
-    if (rel > 1e-3) {
-#pragma unroll
-      for (int a = 0; a < 7; a++) x[a] = xc[a];
-      x_norm = norm_free(x);
-#pragma unroll
-      for (int i = 0; i < NA; i++) acc[i] = cacc[i];
-      x_cost = acc[NH + NP];
-      const double t2 = 2.0 * rel - 1.0;
-      radius = fmin(radius / fmax(1.0 / 3.0, 1.0 - t2 * t2 * t2), 1e16);
-      decrease = 2.0;
-      accepted++;
-      last_ok = true;
-    } else {
-      radius /= decrease;
-      decrease *= 2.0;
-    }
-  }
-  if (sum && threadIdx.x == 0) {
-    sum->iterations = iterations;
-    sum->accepted = accepted;
-    sum->termination = termination;
-    sum->reserved = 0;
-    sum->initial_cost = initial_cost;
-    sum->final_cost = x_cost;
-    sum->final_radius = radius;
-  }
-}
-
-template <int NP>
-__global__ __launch_bounds__(256) void k_sim3(const int *offsets, const double *Pm, const double *pc, const double *isc,
-                                              const double *Pc, const double *pm, const double *ism, const double *cam4,
-                                              double *poses, double *scales, uint8_t *outlier, int *n_inliers,
-                                              vo_lm_summary *sums) {
-  __shared__ double lds[4 * 36];
-  __shared__ int s_cnt[4];
-  const int p = blockIdx.x;
-  const int o0 = offsets[p], n = offsets[p + 1] - o0;
-  Sim3Prob Q;
-  Q.n = n, Q.Pm = Pm + 3 * (long long)o0, Q.pc = pc + 2 * (long long)o0, Q.isc = isc + o0;
-  Q.Pc = Pc + 3 * (long long)o0, Q.pm = pm + 2 * (long long)o0, Q.ism = ism + o0;
-  Q.skip = nullptr;
-  for (int a = 0; a < 4; a++) Q.cam[a] = cam4[a];
-  Q.huber = (double)sqrtf(10.0f);  // :880
-  outlier += o0;
-  double x[7], x_in[7];
-  for (int a = 0; a < 6; a++) x[a] = x_in[a] = poses[6 * p + a];
-  x[6] = x_in[6] = scales[p];
-  for (int i = threadIdx.x; i < n; i += blockDim.x) outlier[i] = 0;
-  __syncthreads();
-  if (sums && threadIdx.x == 0) {
-    vo_lm_summary z = {};
-    sums[2 * p] = z, sums[2 * p + 1] = z;
-  }
-  if (n > 0) sim3_lm<NP>(x, Q, 10, lds, sums ? &sums[2 * p] : nullptr);
-  auto classify = [&](bool keep_old) {  // returns the number of matches passing both chi2 tests now
-    const Sim3Frame F = sim3_frame(x, false);
-    int cnt = 0;
-    for (int i = threadIdx.x; i < n; i += blockDim.x) {
-      const bool o = sim3_outlier(F, Q.Pm + 3 * i, Q.pc[2 * i], Q.pc[2 * i + 1], Q.isc[i], Q.Pc + 3 * i, Q.pm[2 * i],
-                                  Q.pm[2 * i + 1], Q.ism[i], Q.cam);
-      if (o || !keep_old) outlier[i] = o ? 1 : 0;
-      cnt += o ? 0 : 1;
-    }
-#pragma unroll
-    for (int o2 = 32; o2 >= 1; o2 >>= 1) cnt += __shfl_xor(cnt, o2);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    return s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-  };
-  const int ok1 = classify(false);
-  int inliers = 0;
-  if (ok1 < 10) {  // :950-951 returns before Scm is written
-    for (int a = 0; a < 7; a++) x[a] = x_in[a];
-  } else {
-    Q.skip = outlier;  // problem 2: survivors only (:958-960); continues from problem 1's estimate
-    __syncthreads();
-    sim3_lm<NP>(x, Q, ok1 < n ? 10 : 5, lds, sums ? &sums[2 * p + 1] : nullptr);
-    __syncthreads();
-    inliers = classify(true);  // :996-1022 tests every match again
-  }
-  if (threadIdx.x == 0) {
-    for (int a = 0; a < 6; a++) poses[6 * p + a] = x[a];
-    scales[p] = x[6];
-    n_inliers[p] = inliers;
-    if (sums) sums[2 * p].reserved = ok1 < 10 ? 1 : 2;  // phase reached: the shim writes Scm only after phase 2
-  }
-}
 
 // ============================================================================================
 // Local BA
@@ -2979,9 +2022,6 @@ __global__ __launch_bounds__(256) void k_ba_setup(BaDev B, int set_active, uint8
 // ============================================================================================
 // host
 // ============================================================================================
-// process-wide developer knobs (vo_set_option)
-static std::atomic<int> g_opt_ba_graph{0}, g_opt_pose_block{0}, g_opt_pairs_kernel{0};
-
 // A host array that lives either in its own vector or -- the sorted edge arrays of an LDS-sized problem -- directly in the
 // page-locked block build_device uploads from (ba_fill_problem writes them once, where the DMA reads them: at config 3 the
 // intermediate copy of 1.1 MB was ~0.05 ms of every vo_ba_reset -> vo_ba_local_ba call).
@@ -3562,7 +2602,7 @@ int launch_linearize_large(vo_ba *h) {
   hipLaunchKernelGGL(k_ba_cams_large, dim3(std::max(1, h->nf * D.n_cchunks)), dim3(kCamChunk), 0, st, D);
   hipLaunchKernelGGL(k_ba_zero_large, dim3(D.n_ltiles + 8), dim3(256), 0, st, D);
   if (D.n_pairs > 0) {  // n_pairs: a multiple of 32
-    if (g_opt_pairs_kernel.load(std::memory_order_relaxed) == 0)
+    if (opt_pairs_kernel() == 0)
       hipLaunchKernelGGL(k_ba_pairs_lds, dim3(D.n_pairs / 4), dim3(256), 0, st, D);
     else
       hipLaunchKernelGGL(k_ba_pairs, dim3(D.n_pairs / 4), dim3(256), 0, st, D);
@@ -3707,8 +2747,8 @@ int run_lm_eager(vo_ba *h, int max_it) {
 int run_lm(vo_ba *h, int max_it) {
   // Measured on MI355X / ROCm 7.2: replaying a 30-45 node graph costs ~100-200 us of host time before
   // the first node starts, while eager launches (~4 us each) stay ahead of ~20 us kernels.  Graph
-  // replay is therefore opt-in (vo_set_option(VO_OPT_BA_GRAPH, 1)), for hosts whose launch path is the bottleneck.
-  const bool use_graph = g_opt_ba_graph.load(std::memory_order_relaxed) != 0;
+  // replay is therefore opt-in (option VO_OPT_BA_GRAPH = 1), for hosts whose launch path is the bottleneck.
+  const bool use_graph = opt_ba_graph() != 0;
   if (!use_graph || !h->own_stream || max_it < 1 || h->collectives) return run_lm_eager(h, max_it);
   auto it = h->graphs.find(max_it);
   if (it == h->graphs.end()) {
@@ -3744,151 +2784,6 @@ int current_index(vo_ba *h, int *cur) {
 }  // namespace
 
 extern "C" {
-
-// The kernel is a chain of ~20 dependent LM iterations whose fixed part (6 x 6 solve, exp / log, reductions) every
-// wavefront of a workgroup repeats, and it needs all 256 registers (one wavefront per SIMD).  A single frame is
-// fastest with four wavefronts sharing its observations; a batch is fastest with ONE wavefront per frame, so that a
-// CU works on four frames at once instead of four times on one (1024 frames x 1000 observations: 1.45 -> see DESIGN).
-static inline int pose_block_width(int n_problems) {
-  const int forced = g_opt_pose_block.load(std::memory_order_relaxed);  // vo_set_option(VO_OPT_POSE_BLOCK, ...)
-  if (forced == 64 || forced == 128 || forced == 256) return forced;
-  return n_problems >= 512 ? 64 : 256;
-}
-
-int vo_pose_only_solve_dev(int n_problems, const int32_t *dev_offsets, int max_obs, const double *dev_points,
-                           const double *dev_obs, const double *dev_inv_sigma, const double *dev_cam5,
-                           double *dev_poses, uint8_t *dev_outlier, int32_t *dev_n_inliers,
-                           vo_lm_summary *dev_summaries, void *hip_stream) {
-  (void)max_obs;
-  if (n_problems < 0 || (n_problems > 0 && (!dev_offsets || !dev_poses || !dev_outlier || !dev_n_inliers || !dev_cam5)))
-    return VO_ERR_INVALID;
-  if (n_problems == 0) return VO_OK;
-  VO_CHECK(vo::ensure_device());
-  const int bw = pose_block_width(n_problems);
-  hipLaunchKernelGGL(bw == 64 ? k_pose_only<true> : k_pose_only<false>, dim3(n_problems), dim3(bw), 0, (hipStream_t)hip_stream,
-                     dev_offsets, dev_points, dev_obs, dev_inv_sigma, dev_cam5, dev_poses, dev_outlier, dev_n_inliers, dev_summaries, 0);
-  VO_HIP_CHECK(hipGetLastError());
-  return VO_OK;
-}
-
-int vo_pose_only_solve_ranges_dev(int n_problems, const int32_t *dev_ranges, const double *dev_points, const double *dev_obs,
-                                  const double *dev_inv_sigma, const double *dev_cam5, double *dev_poses,
-                                  uint8_t *dev_outlier, int32_t *dev_n_inliers, vo_lm_summary *dev_summaries,
-                                  void *hip_stream) {
-  if (n_problems < 0 || (n_problems > 0 && (!dev_ranges || !dev_poses || !dev_outlier || !dev_n_inliers || !dev_cam5)))
-    return VO_ERR_INVALID;
-  if (n_problems == 0) return VO_OK;
-  VO_CHECK(vo::ensure_device());
-  const int bw = pose_block_width(n_problems);
-  hipLaunchKernelGGL(bw == 64 ? k_pose_only<true> : k_pose_only<false>, dim3(n_problems), dim3(bw), 0, (hipStream_t)hip_stream,
-                     dev_ranges, dev_points, dev_obs, dev_inv_sigma, dev_cam5, dev_poses, dev_outlier, dev_n_inliers, dev_summaries, 1);
-  VO_HIP_CHECK(hipGetLastError());
-  return VO_OK;
-}
-
-int vo_pose_only_solve(int n_problems, const int32_t *offsets, const double *points, const double *obs,
-                       const double *inv_sigma, const double cam[5], double *poses, uint8_t *outlier,
-                       int32_t *n_inliers, vo_lm_summary *summaries) {
-  if (n_problems < 0 || (n_problems > 0 && (!offsets || !poses || !n_inliers || !cam))) return VO_ERR_INVALID;
-  if (n_problems == 0) return VO_OK;
-  VO_CHECK(vo::ensure_device());
-  const int total = offsets[n_problems];
-  if (total > 0 && (!points || !obs || !inv_sigma || !outlier)) return VO_ERR_INVALID;
-  // One staging block each way (a tracking thread calls this once or twice per frame: eleven small
-  // copies cost more than the kernel's first LM iterations).  Per host thread, grow-only.
-  auto up8 = [](size_t v) { return (v + 7) & ~(size_t)7; };
-  const size_t o_pts = 0, o_obs = o_pts + (size_t)total * 24, o_is = o_obs + (size_t)total * 24,
-               o_cam = o_is + (size_t)total * 8, o_pose = o_cam + 40, o_off = o_pose + (size_t)n_problems * 48,
-               in_bytes = up8(o_off + (size_t)(n_problems + 1) * 4);
-  const size_t r_pose = 0, r_sum = r_pose + (size_t)n_problems * 48,
-               r_inl = r_sum + (size_t)n_problems * 2 * sizeof(vo_lm_summary), r_out = up8(r_inl + (size_t)n_problems * 4),
-               out_bytes = up8(r_out + (size_t)std::max(total, 1));
-  hipStream_t st = vo::thread_stream();  // the calling thread's own stream: never queues behind another thread's solve
-  thread_local vo::PinnedBuf pinned;
-  thread_local vo::ScratchBuf d_in, d_out;
-  VO_CHECK(pinned.reserve(std::max(in_bytes, out_bytes)));
-  uint8_t *stage = pinned.data();
-  if (total > 0) {
-    memcpy(&stage[o_pts], points, (size_t)total * 24);
-    memcpy(&stage[o_obs], obs, (size_t)total * 24);
-    memcpy(&stage[o_is], inv_sigma, (size_t)total * 8);
-  }
-  memcpy(&stage[o_cam], cam, 40);
-  memcpy(&stage[o_pose], poses, (size_t)n_problems * 48);
-  memcpy(&stage[o_off], offsets, (size_t)(n_problems + 1) * 4);
-  VO_CHECK(d_in.reserve(in_bytes));
-  VO_CHECK(d_out.reserve(out_bytes));
-  VO_HIP_CHECK(hipMemcpyAsync(d_in.p, stage, in_bytes, hipMemcpyHostToDevice, st));
-  uint8_t *di = d_in.as<uint8_t>(), *dout = d_out.as<uint8_t>();
-  // the kernel updates poses in place: give it the output block's copy
-  VO_HIP_CHECK(hipMemcpyAsync(dout + r_pose, di + o_pose, (size_t)n_problems * 48, hipMemcpyDeviceToDevice, st));
-  VO_HIP_CHECK(hipMemsetAsync(dout + r_sum, 0, (size_t)n_problems * 2 * sizeof(vo_lm_summary), st));
-  VO_CHECK(vo_pose_only_solve_dev(n_problems, reinterpret_cast<const int32_t *>(di + o_off), 0,
-                                  reinterpret_cast<const double *>(di + o_pts), reinterpret_cast<const double *>(di + o_obs),
-                                  reinterpret_cast<const double *>(di + o_is), reinterpret_cast<const double *>(di + o_cam),
-                                  reinterpret_cast<double *>(dout + r_pose), dout + r_out,
-                                  reinterpret_cast<int32_t *>(dout + r_inl),
-                                  reinterpret_cast<vo_lm_summary *>(dout + r_sum), st));
-  // the inputs have left the staging block once the kernel has run: it takes the results back
-  if (hipMemcpyAsync(stage, dout, out_bytes, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    vo::set_error("pose-only kernel failed: %s", hipGetErrorString(hipGetLastError()));
-    return VO_ERR_HIP;
-  }
-  memcpy(poses, &stage[r_pose], (size_t)n_problems * 48);
-  if (total > 0) memcpy(outlier, &stage[r_out], total);
-  memcpy(n_inliers, &stage[r_inl], (size_t)n_problems * 4);
-  if (summaries) memcpy(summaries, &stage[r_sum], (size_t)n_problems * 2 * sizeof(vo_lm_summary));
-  return VO_OK;
-}
-
-int vo_sim3_solve(int n_problems, const int32_t *offsets, const double *cam_match, const double *pix_curr,
-                  const double *inv_sigma_curr, const double *cam_curr, const double *pix_match,
-                  const double *inv_sigma_match, const double camera[4], int fix_scale, double *poses, double *scales,
-                  uint8_t *outlier, int32_t *n_inliers, vo_lm_summary *summaries) {
-  if (n_problems < 0 || (n_problems > 0 && (!offsets || !poses || !scales || !n_inliers || !camera))) return VO_ERR_INVALID;
-  if (n_problems == 0) return VO_OK;
-  VO_CHECK(vo::ensure_device());
-  const int total = offsets[n_problems];
-  if (total > 0 && (!cam_match || !pix_curr || !inv_sigma_curr || !cam_curr || !pix_match || !inv_sigma_match || !outlier))
-    return VO_ERR_INVALID;
-  thread_local vo::ScratchBuf d_off, d_pm, d_pc, d_isc, d_Pc, d_pxm, d_ism, d_cam, d_pose, d_sc, d_out, d_inl, d_sum;
-  int rc = VO_OK;
-  auto fail = [&](int r) { return r; };
-  hipStream_t st = vo::thread_stream();
-  auto upload = [&](vo::DevBuf &b, const void *src, size_t bytes) { return vo::upload(b, src, bytes, st, "vo_sim3_solve"); };
-  if ((rc = upload(d_off, offsets, (size_t)(n_problems + 1) * 4)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_pm, cam_match, (size_t)total * 24)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_pc, pix_curr, (size_t)total * 16)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_isc, inv_sigma_curr, (size_t)total * 8)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_Pc, cam_curr, (size_t)total * 24)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_pxm, pix_match, (size_t)total * 16)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_ism, inv_sigma_match, (size_t)total * 8)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_cam, camera, 32)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_pose, poses, (size_t)n_problems * 48)) != VO_OK) return fail(rc);
-  if ((rc = upload(d_sc, scales, (size_t)n_problems * 8)) != VO_OK) return fail(rc);
-  if ((rc = d_out.reserve(std::max(64, total))) != VO_OK) return fail(rc);
-  if ((rc = d_inl.reserve((size_t)n_problems * 4)) != VO_OK) return fail(rc);
-  if ((rc = d_sum.reserve((size_t)n_problems * 2 * sizeof(vo_lm_summary))) != VO_OK) return fail(rc);
-  if (fix_scale)
-    hipLaunchKernelGGL(k_sim3<6>, dim3(n_problems), dim3(256), 0, st, d_off.as<int>(), d_pm.as<double>(),
-                       d_pc.as<double>(), d_isc.as<double>(), d_Pc.as<double>(), d_pxm.as<double>(), d_ism.as<double>(),
-                       d_cam.as<double>(), d_pose.as<double>(), d_sc.as<double>(), d_out.as<uint8_t>(), d_inl.as<int>(),
-                       d_sum.as<vo_lm_summary>());
-  else
-    hipLaunchKernelGGL(k_sim3<7>, dim3(n_problems), dim3(256), 0, st, d_off.as<int>(), d_pm.as<double>(),
-                       d_pc.as<double>(), d_isc.as<double>(), d_Pc.as<double>(), d_pxm.as<double>(), d_ism.as<double>(),
-                       d_cam.as<double>(), d_pose.as<double>(), d_sc.as<double>(), d_out.as<uint8_t>(), d_inl.as<int>(),
-                       d_sum.as<vo_lm_summary>());
-  VO_HIP_CHECK(hipGetLastError());
-  VO_CHECK(vo::copy_d2h(poses, d_pose.p, (size_t)n_problems * 48, st, "vo_sim3_solve"));
-  VO_CHECK(vo::copy_d2h(scales, d_sc.p, (size_t)n_problems * 8, st, "vo_sim3_solve"));
-  if (total > 0) VO_CHECK(vo::copy_d2h(outlier, d_out.p, total, st, "vo_sim3_solve"));
-  VO_CHECK(vo::copy_d2h(n_inliers, d_inl.p, (size_t)n_problems * 4, st, "vo_sim3_solve"));
-  if (summaries)
-    VO_CHECK(vo::copy_d2h(summaries, d_sum.p, (size_t)n_problems * 2 * sizeof(vo_lm_summary), st, "vo_sim3_solve"));
-  return vo::stream_sync(st, "vo_sim3_solve");
-}
 
 // the host part of a problem: validation, stable grouping of the edges by point (the order Ceres' Schur eliminator walks its
 // chunks) by a counting sort, free-camera slots
@@ -4088,34 +2983,6 @@ int vo_ba_set_option(vo_ba *h, int option, int value) {
     case VO_BA_OPT_COLLECTIVES_AT_ONE_RANK: h->opt_collectives_1 = value != 0; return VO_OK;
     case VO_BA_OPT_ORDER_PARTS: h->opt_order_parts = value; return VO_OK;
     default: vo::set_error("vo_ba_set_option: unknown option %d", option); return VO_ERR_INVALID;
-  }
-}
-
-int vo_set_option(int option, int value) {
-  switch (option) {
-    case VO_OPT_BA_GRAPH: g_opt_ba_graph.store(value != 0); return VO_OK;
-    case VO_OPT_POSE_BLOCK:
-      if (value != 0 && value != 64 && value != 128 && value != 256) {
-        vo::set_error("vo_set_option(VO_OPT_POSE_BLOCK): 0 (automatic), 64, 128 or 256");
-        return VO_ERR_INVALID;
-      }
-      g_opt_pose_block.store(value);
-      return VO_OK;
-    case VO_OPT_BA_PAIRS_KERNEL:
-      if (value != 0 && value != 1) {
-        vo::set_error("vo_set_option(VO_OPT_BA_PAIRS_KERNEL): 0 (blocks staged through LDS) or 1 (lane = couple, register loads)");
-        return VO_ERR_INVALID;
-      }
-      g_opt_pairs_kernel.store(value);
-      return VO_OK;
-    case VO_OPT_HAMMING_KERNEL:
-      if (value != 0 && value != 1) {
-        vo::set_error("vo_set_option(VO_OPT_HAMMING_KERNEL): 0 (matrix cores) or 1 (VALU)");
-        return VO_ERR_INVALID;
-      }
-      vo::set_hamming_kernel(value);
-      return VO_OK;
-    default: vo::set_error("vo_set_option: unknown option %d", option); return VO_ERR_INVALID;
   }
 }
 
@@ -4427,51 +3294,6 @@ int vo_ba_debug_schur(vo_ba *h, double hm, double hs, double point_damping, cons
     b[r] = HP[(r / 6) * 27 + 21 + r % 6] - pay[(size_t)r * M + n];
   }
   *cost = pay[(size_t)M * M + (size_t)h->nf * 27];
-  return VO_OK;
-}
-
-int vo_se3_exp(const double xi[6], double R[9], double t[3]) {
-  if (!xi || !R || !t) return VO_ERR_INVALID;
-  const Se3 T = se3_exp(xi);
-  const double *q = T.q;
-  const double tx = 2 * q[1], ty = 2 * q[2], tz = 2 * q[3];
-  const double twx = tx * q[0], twy = ty * q[0], twz = tz * q[0];
-  const double txx = tx * q[1], txy = ty * q[1], txz = tz * q[1];
-  const double tyy = ty * q[2], tyz = tz * q[2], tzz = tz * q[3];
-  R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-  R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-  R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-  t[0] = T.t[0], t[1] = T.t[1], t[2] = T.t[2];
-  return VO_OK;
-}
-
-int vo_se3_log(const double R[9], const double t[3], double xi[6]) {
-  if (!xi || !R || !t) return VO_ERR_INVALID;
-  // rotation matrix -> unit quaternion (Eigen's Quaternion(Matrix3) branch structure)
-  Se3 T;
-  const double tr = R[0] + R[4] + R[8];
-  if (tr > 0) {
-    double s = sqrt(tr + 1.0);
-    T.q[0] = 0.5 * s;
-    s = 0.5 / s;
-    T.q[1] = (R[7] - R[5]) * s, T.q[2] = (R[2] - R[6]) * s, T.q[3] = (R[3] - R[1]) * s;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[i * 4]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    double s = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-    double q[4];
-    q[1 + i] = 0.5 * s;
-    s = 0.5 / s;
-    q[0] = (R[k * 3 + j] - R[j * 3 + k]) * s;
-    q[1 + j] = (R[j * 3 + i] + R[i * 3 + j]) * s;
-    q[1 + k] = (R[k * 3 + i] + R[i * 3 + k]) * s;
-    for (int a = 0; a < 4; a++) T.q[a] = q[a];
-  }
-  quat_normalize(T.q);
-  T.t[0] = t[0], T.t[1] = t[1], T.t[2] = t[2];
-  se3_log(T, xi);
   return VO_OK;
 }
 

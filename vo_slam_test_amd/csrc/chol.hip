@@ -38,6 +38,7 @@
 // poll the flag with agent-scope loads.  Every poll loop is bounded: on expiry the kernel raises `fail` and all
 // workgroups leave (a hang would cost the GPU box).
 #include "vo_common.h"
+#include "wave_ops.h"
 
 #include <algorithm>
 #include <mutex>
@@ -57,14 +58,6 @@ constexpr int kNewton = 3;  // v_rsq_f64 is good to ~2^-26: 1, 2 = Newton steps 
 constexpr int LP = NB + 1;          // LDS pitch of a staged tile (conflict-free column and row walks)
 typedef double double4_t __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void st_sc1(double *p, double v) {
-  __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __double_as_longlong(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ double ld_sc1(const double *p) {
-  return __longlong_as_double(__hip_atomic_load(reinterpret_cast<const unsigned long long *>(p), __ATOMIC_RELAXED,
-                                                __HIP_MEMORY_SCOPE_AGENT));
-}
 __device__ __forceinline__ int ld_flag(const int *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void st_flag(int *p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 

@@ -6,7 +6,6 @@
 #include "vo_common.h"
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <vector>
 
@@ -300,13 +299,10 @@ __global__ __launch_bounds__(256, 2) void k_hamming_mfma(const uint32_t *__restr
 }
 
 
-// vo_set_option(VO_OPT_HAMMING_KERNEL): 0 = the matrix-core form (default), 1 = the VALU form
-std::atomic<int> g_hamming_kernel{0};
-
 int launch_hamming(const uint8_t *a, int na, size_t as, const uint8_t *b, int nb, size_t bs, uint16_t *d,
                    size_t ds, int n_pairs, hipStream_t st) {
   if (na <= 0 || nb <= 0 || n_pairs <= 0) return VO_OK;
-  if (g_hamming_kernel.load(std::memory_order_relaxed) == 0) {
+  if (vo::opt_hamming_kernel() == 0) {  // vo_set_option(VO_OPT_HAMMING_KERNEL): 0 = the matrix-core form (default), 1 = the VALU form
     // 16-byte stores: D, the pair stride and every row start 16-byte aligned
     const bool al16 = (reinterpret_cast<uintptr_t>(d) & 15) == 0 && (ds & 7) == 0 && (nb & 7) == 0;
     dim3 grid((na + kHmRows - 1) / kHmRows, 1, n_pairs);
@@ -705,10 +701,6 @@ int node_search_batch(int mode, int n_pairs, const NodePair *pairs, bool a_flag_
 }
 
 }  // namespace
-
-namespace vo {
-void set_hamming_kernel(int v) { g_hamming_kernel.store(v, std::memory_order_relaxed); }
-}  // namespace vo
 
 extern "C" {
 

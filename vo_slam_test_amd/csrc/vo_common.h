@@ -162,8 +162,12 @@ struct FrameStoreView {
 };
 FrameStoreView frame_store_view(const vo_frames *h);
 
-// vo_set_option(VO_OPT_HAMMING_KERNEL) (match.hip): 0 = matrix-core form, 1 = VALU form
-void set_hamming_kernel(int v);
+// vo_set_option's process-wide values as last set, 0 before (vo_common.hip): VO_OPT_BA_GRAPH (ba.hip), VO_OPT_POSE_BLOCK
+// (pose_only.hip), VO_OPT_BA_PAIRS_KERNEL (ba.hip), VO_OPT_HAMMING_KERNEL (match.hip: 0 = matrix-core form, 1 = VALU form)
+int opt_ba_graph();
+int opt_pose_block();
+int opt_pairs_kernel();
+int opt_hamming_kernel();
 
 // Device addresses of the handles' sticky error flags (NULL before the first use): vo_tracker copies them into its
 // result block so that one download answers "pose + counts + did anything overflow" (orb.hip, guided.hip).

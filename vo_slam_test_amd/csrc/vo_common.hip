@@ -1,9 +1,15 @@
-// vo_common.hip -- error reporting and device bring-up shared by every C-ABI entry point.
+// vo_common.hip -- error reporting, device bring-up and the process-wide options shared by every C-ABI entry point;
+// the SE3 exp / log entry points.
+#include "ba_math.h"
 #include "vo_common.h"
 
+#include <atomic>
 #include <vector>
 
 #include <mutex>
+
+// process-wide developer knobs (vo_set_option)
+static std::atomic<int> g_opt_ba_graph{0}, g_opt_pose_block{0}, g_opt_pairs_kernel{0}, g_opt_hamming_kernel{0};
 
 namespace vo {
 
@@ -91,7 +97,14 @@ int upload(DevBuf &b, const void *src, size_t bytes, hipStream_t st, const char 
   return copy_h2d(b.p, src, bytes, st, what);
 }
 
+int opt_ba_graph() { return g_opt_ba_graph.load(std::memory_order_relaxed); }
+int opt_pose_block() { return g_opt_pose_block.load(std::memory_order_relaxed); }
+int opt_pairs_kernel() { return g_opt_pairs_kernel.load(std::memory_order_relaxed); }
+int opt_hamming_kernel() { return g_opt_hamming_kernel.load(std::memory_order_relaxed); }
+
 }  // namespace vo
+
+using namespace vo::ba;  // vo_se3_exp / vo_se3_log
 
 extern "C" {
 const char *vo_last_error(void) { return vo::g_err; }
@@ -102,4 +115,78 @@ int vo_device_count(void) {
 }
 const char *vo_version(void) { return "vo_slam_test_amd 0.1 (gfx950)"; }
 size_t vo_release_thread_scratch(void) { return vo::release_thread_scratch(); }
+
+int vo_set_option(int option, int value) {
+  switch (option) {
+    case VO_OPT_BA_GRAPH: g_opt_ba_graph.store(value != 0); return VO_OK;
+    case VO_OPT_POSE_BLOCK:
+      if (value != 0 && value != 64 && value != 128 && value != 256) {
+        vo::set_error("vo_set_option(VO_OPT_POSE_BLOCK): 0 (automatic), 64, 128 or 256");
+        return VO_ERR_INVALID;
+      }
+      g_opt_pose_block.store(value);
+      return VO_OK;
+    case VO_OPT_BA_PAIRS_KERNEL:
+      if (value != 0 && value != 1) {
+        vo::set_error("vo_set_option(VO_OPT_BA_PAIRS_KERNEL): 0 (blocks staged through LDS) or 1 (lane = couple, register loads)");
+        return VO_ERR_INVALID;
+      }
+      g_opt_pairs_kernel.store(value);
+      return VO_OK;
+    case VO_OPT_HAMMING_KERNEL:
+      if (value != 0 && value != 1) {
+        vo::set_error("vo_set_option(VO_OPT_HAMMING_KERNEL): 0 (matrix cores) or 1 (VALU)");
+        return VO_ERR_INVALID;
+      }
+      g_opt_hamming_kernel.store(value);
+      return VO_OK;
+    default: vo::set_error("vo_set_option: unknown option %d", option); return VO_ERR_INVALID;
+  }
 }
+
+int vo_se3_exp(const double xi[6], double R[9], double t[3]) {
+  if (!xi || !R || !t) return VO_ERR_INVALID;
+  const Se3 T = se3_exp(xi);
+  const double *q = T.q;
+  const double tx = 2 * q[1], ty = 2 * q[2], tz = 2 * q[3];
+  const double twx = tx * q[0], twy = ty * q[0], twz = tz * q[0];
+  const double txx = tx * q[1], txy = ty * q[1], txz = tz * q[1];
+  const double tyy = ty * q[2], tyz = tz * q[2], tzz = tz * q[3];
+  R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
+  R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
+  R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
+  t[0] = T.t[0], t[1] = T.t[1], t[2] = T.t[2];
+  return VO_OK;
+}
+
+int vo_se3_log(const double R[9], const double t[3], double xi[6]) {
+  if (!xi || !R || !t) return VO_ERR_INVALID;
+  // rotation matrix -> unit quaternion (Eigen's Quaternion(Matrix3) branch structure)
+  Se3 T;
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0) {
+    double s = sqrt(tr + 1.0);
+    T.q[0] = 0.5 * s;
+    s = 0.5 / s;
+    T.q[1] = (R[7] - R[5]) * s, T.q[2] = (R[2] - R[6]) * s, T.q[3] = (R[3] - R[1]) * s;
+  } else {
+    int i = 0;
+    if (R[4] > R[0]) i = 1;
+    if (R[8] > R[i * 4]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double s = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
+    double q[4];
+    q[1 + i] = 0.5 * s;
+    s = 0.5 / s;
+    q[0] = (R[k * 3 + j] - R[j * 3 + k]) * s;
+    q[1 + j] = (R[j * 3 + i] + R[i * 3 + j]) * s;
+    q[1 + k] = (R[k * 3 + i] + R[i * 3 + k]) * s;
+    for (int a = 0; a < 4; a++) T.q[a] = q[a];
+  }
+  quat_normalize(T.q);
+  T.t[0] = t[0], T.t[1] = t[1], T.t[2] = t[2];
+  se3_log(T, xi);
+  return VO_OK;
+}
+
+}  // extern "C"
