@@ -114,8 +114,19 @@ void add_normal(MapPoint &m, const double c[3]) {
 }  // namespace
 
 int main(int argc, char **argv) {
+  // --vocabulary-out PATH (anywhere on the line): train a vocabulary on the run's descriptors at the end and save it,
+  // Map::createVocabulary as vo_run.cpp:234 calls it; the other arguments are positional as before
+  const char *vocabulary_out = nullptr;
+  for (int a = 1; a + 1 < argc; a++)
+    if (strcmp(argv[a], "--vocabulary-out") == 0) {
+      vocabulary_out = argv[a + 1];
+      for (int b = a; b + 2 < argc; b++) argv[b] = argv[b + 2];
+      argc -= 2;
+      break;
+    }
   if (argc < 3) {
-    fprintf(stderr, "usage: %s <sequence_dir/> <camera_trajectory.txt> [max_frames] [fx fy cx cy bf depth_scale] [pose_dump.txt]\n", argv[0]);
+    fprintf(stderr, "usage: %s <sequence_dir/> <camera_trajectory.txt> [max_frames] [fx fy cx cy bf depth_scale] [pose_dump.txt] "
+                    "[--vocabulary-out vocabulary.dbow3]\n", argv[0]);
     return 2;
   }
   const std::string dir = argv[1], out_path = argv[2];
@@ -398,6 +409,21 @@ int main(int argc, char **argv) {
       fprintf(fp, "\n");
     }
     fclose(fp);
+  }
+  if (vocabulary_out) {  // map.cpp:60-99: the descriptors of every frame of the run, one document per frame, k = 10, L = 5
+    std::vector<uint8_t> all;
+    std::vector<int32_t> offsets(1, 0);
+    for (const FrameRec &F : frames) {
+      all.insert(all.end(), F.desc.begin(), F.desc.begin() + (size_t)F.n * 32);
+      offsets.push_back((int32_t)(all.size() / 32));
+    }
+    vo_vocab *voc = nullptr;
+    vo_vocab_train_info vi;
+    VO_TRY(vo_vocab_train((int)(all.size() / 32), all.data(), (int)frames.size(), offsets.data(), 10, 5, 0, &voc, &vi));
+    VO_TRY(vo_vocab_save(voc, 10, vocabulary_out));
+    vo_vocab_destroy(voc);
+    printf("vocabulary info: k = 10, L = 5, %d nodes, %d words from %zu descriptors of %zu frames; saved to %s\n", vi.n_nodes,
+           vi.n_words, all.size() / 32, frames.size(), vocabulary_out);
   }
   vo_tracker_destroy(trk);
   vo_dataset_close(ds);

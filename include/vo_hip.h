@@ -384,6 +384,35 @@ int vo_bow_transform(const vo_vocab *v, int n, const uint8_t *desc, int levelsup
  * a stream that does not follow the format is refused), its cv::FileStorage form (.yml / .yml.gz: Vocabulary::save(cv::FileStorage&),
  * what DBoW3::Vocabulary(path) falls back to) or the ORB-SLAM2 text format; builds the device tree. */
 int vo_vocab_load(const char *path, vo_vocab **out, int *n_nodes, int *n_words, int *branching_k, int *depth_L);
+/* Map::createVocabulary (map.cpp:60-99): DBoW3::Vocabulary::create(descriptors) with k children per node and L levels,
+ * TF-IDF weights -- the k-majority tree (k-means++ seeding, Lloyd with per-bit majority centres, idf of the training
+ * set's own transform), trained on the device.  DBoW3 is unpinned and seeds itself from the clock: the contract (integer
+ * draw keyed by (seed, the node's path), breadth-first node ids, every deviation) is DESIGN.md section 4d; a tree is a
+ * function of (descriptors in order, image_offsets, k, L, seed) alone.  desc: n_desc x 32 bytes in the order
+ * createVocabulary concatenates them; image_offsets[n_images + 1]: CSR of the images (key-frames / lost frames) over the
+ * descriptors, starting at 0, ascending, ending at n_desc.  k < 2, L < 1, n_desc < 0 or bad offsets: VO_ERR_INVALID;
+ * k > VO_VOCAB_MAX_K, L > VO_VOCAB_MAX_L or n_desc > VO_VOCAB_MAX_DESC: VO_ERR_CAPACITY; *out is written on success
+ * only.  n_desc == 0 gives a root-only tree.  A clustering that still moves after VO_VOCAB_MAX_LLOYD assignments keeps its
+ * last one and is counted in info->n_capped.  The _dev form takes device arrays (descriptors 4-byte aligned) and works on
+ * hip_stream (NULL: the legacy stream); both forms synchronise (one word per Lloyd iteration, the tree's bookkeeping once
+ * per level) and allocate their own buffers: a one-off at the end of a run, like the reference's. */
+#define VO_VOCAB_MAX_K 32
+#define VO_VOCAB_MAX_L 16
+#define VO_VOCAB_MAX_DESC (1 << 23)
+#define VO_VOCAB_MAX_LLOYD 2048
+typedef struct { int32_t n_nodes, n_words, n_levels, lloyd_iterations_max, n_capped; } vo_vocab_train_info;
+int vo_vocab_train(int n_desc, const uint8_t *desc, int n_images, const int32_t *image_offsets, int k, int L, uint64_t seed,
+                   vo_vocab **out, vo_vocab_train_info *info);
+int vo_vocab_train_dev(int n_desc, const uint8_t *dev_desc, int n_images, const int32_t *dev_image_offsets, int k, int L,
+                       uint64_t seed, void *hip_stream, vo_vocab **out, vo_vocab_train_info *info);
+/* The tree of a handle back on the host, in vo_vocab_create's layout (what map.cpp:60-99 goes on to save).  Any array may
+ * be NULL (sizes only); children needs child_start[n_nodes] entries, which is n_nodes - 1 for a tree. */
+int vo_vocab_tree(const vo_vocab *v, int *n_nodes, int *depth_L, int32_t *child_start, int32_t *children, uint8_t *node_desc,
+                  double *node_weight, int32_t *word_id);
+/* vocab.save(path) of map.cpp:60-99: DBoW3's Vocabulary::toStream, uncompressed (the plain binary stream vo_vocab_load
+ * reads; DBoW3 reads it too, its QuickLZ form is not written).  k is recorded in the file's header (2 .. 64). */
+int vo_vocab_save(const vo_vocab *v, int k, const char *path);
+
 /* Map::score (map.cpp:335-376): L1 similarity of the query BoW vector (ascending word ids) with every
  * candidate's (CSR: candidate c owns cand_words / cand_values [cand_start[c], cand_start[c+1])); one
  * launch for all candidates of detectLoopCandidates / detectRelocalizationCandidates (:210-333). */

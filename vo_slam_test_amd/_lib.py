@@ -55,6 +55,7 @@ SYMBOLS = [
     "vo_match_frame_projection", "vo_match_local_map", "vo_match_frame_keyframe", "vo_match_bow",
     "vo_match_triangulation", "vo_match_bow_batch", "vo_match_triangulation_batch", "vo_match_fuse", "vo_match_area_best", "vo_match_sim3_projection",
     "vo_match_sim3_mutual", "vo_vocab_create", "vo_vocab_destroy", "vo_bow_transform",
+    "vo_vocab_train", "vo_vocab_train_dev", "vo_vocab_tree", "vo_vocab_save",
     "vo_pose_only_solve", "vo_sim3_solve", "vo_pose_graph_solve", "vo_sim3_reanchor_points", "vo_chol_solve", "vo_chol_solve_split", "vo_pose_only_solve_dev",
     "vo_ba_create", "vo_ba_reset", "vo_ba_destroy", "vo_ba_set_stream", "vo_ba_set_shard", "vo_ba_set_option", "vo_set_option", "vo_ba_set_allreduce", "vo_ba_set_state",
     "vo_ba_get_state", "vo_ba_n_free_cams", "vo_ba_local_ba", "vo_ba_local_ba_enqueue",
@@ -677,6 +678,44 @@ class Vocabulary:
         word, weight, node = np.zeros(n, np.int32), np.zeros(n, np.float64), np.zeros(n, np.int32)
         check(lib().vo_bow_transform(self._h, n, _p(desc), int(levelsup), _p(word), _p(weight), _p(node)), "vo_bow_transform")
         return word, weight, node
+
+    def tree(self):
+        """the tree back on the host (vo_vocab_tree): dict in vo_vocab_create's layout"""
+        nn, L = C.c_int(), C.c_int()
+        check(lib().vo_vocab_tree(self._h, C.byref(nn), C.byref(L), None, None, None, None, None), "vo_vocab_tree")
+        n = nn.value
+        cs = np.zeros(n + 1, np.int32)
+        check(lib().vo_vocab_tree(self._h, None, None, _p(cs), None, None, None, None), "vo_vocab_tree")
+        ch, nd = np.zeros(max(int(cs[n]), 1), np.int32), np.zeros((n, 32), np.uint8)
+        nw, wi = np.zeros(n, np.float64), np.zeros(n, np.int32)
+        check(lib().vo_vocab_tree(self._h, None, None, None, _p(ch), _p(nd), _p(nw), _p(wi)), "vo_vocab_tree")
+        return dict(L=L.value, child_start=cs, children=ch[:int(cs[n])], node_desc=nd, node_weight=nw, word_id=wi)
+
+    def save(self, path, k=10):
+        """DBoW3::Vocabulary::save(path, false): the plain binary stream load_vocabulary reads"""
+        check(lib().vo_vocab_save(self._h, int(k), str(path).encode()), "vo_vocab_save")
+
+
+class VocabTrainInfo(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("n_nodes", "n_words", "n_levels", "lloyd_iterations_max", "n_capped")]
+
+
+def train_vocabulary(desc, image_offsets, k=10, L=5, seed=0, stream=None):
+    """Map::createVocabulary's DBoW3::Vocabulary::create on the device -> (Vocabulary, info dict).  desc [n, 32] uint8 and
+    image_offsets [n_images + 1] int32: numpy arrays (vo_vocab_train) or torch device tensors (vo_vocab_train_dev, `stream`)."""
+    h, info = C.c_void_p(), VocabTrainInfo()
+    if isinstance(desc, np.ndarray) or not hasattr(desc, "data_ptr"):
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        off = np.ascontiguousarray(image_offsets, np.int32)
+        check(lib().vo_vocab_train(len(d), _p(d), len(off) - 1, _p(off), int(k), int(L), C.c_uint64(int(seed)), C.byref(h),
+                                   C.byref(info)), "vo_vocab_train")
+    else:
+        assert desc.is_contiguous() and image_offsets.is_contiguous()
+        check(lib().vo_vocab_train_dev(int(desc.numel() // 32), _p(desc), int(image_offsets.numel()) - 1, _p(image_offsets), int(k),
+                                       int(L), C.c_uint64(int(seed)), _p(stream), C.byref(h), C.byref(info)), "vo_vocab_train_dev")
+    v = Vocabulary.__new__(Vocabulary)
+    v._h = h
+    return v, {n: int(getattr(info, n)) for n, _ in VocabTrainInfo._fields_}
 
 
 class Matcher:

@@ -708,4 +708,60 @@ int vo_vocab_load(const char *path, vo_vocab **out, int *n_nodes, int *n_words, 
   return vocab_to_handle(nodes, L, out, n_nodes, n_words);
 }
 
+// vocab.save(vocabulary_out) (reference map.cpp:94) in the uncompressed form of Vocabulary::toStream, the layout the loader
+// above restates: records in node-id order (a parent precedes its children; a parent's children in child-list order).
+int vo_vocab_save(const vo_vocab *v, int k, const char *path) {
+  if (!v || !path || k < 2 || k > 64) return VO_ERR_INVALID;
+  int N = 0, L = 0, rc = VO_OK;
+  if ((rc = vo_vocab_tree(v, &N, &L, nullptr, nullptr, nullptr, nullptr, nullptr)) != VO_OK) return rc;
+  if (L < 1 || L > 16) {
+    vo::set_error("vo_vocab_save: depth %d cannot be written (the format's readers take 1 .. 16)", L);
+    return VO_ERR_INVALID;
+  }
+  std::vector<int32_t> cs((size_t)N + 1), wid(N);
+  std::vector<uint8_t> desc((size_t)N * 32);
+  std::vector<double> wt(N);
+  if ((rc = vo_vocab_tree(v, nullptr, nullptr, cs.data(), nullptr, nullptr, nullptr, nullptr)) != VO_OK) return rc;
+  std::vector<int32_t> ch((size_t)std::max(cs[N], 1));
+  if ((rc = vo_vocab_tree(v, nullptr, nullptr, nullptr, ch.data(), desc.data(), wt.data(), wid.data())) != VO_OK) return rc;
+  std::vector<uint32_t> parent(N, 0);
+  for (int i = 0; i < N; i++)
+    for (int c = cs[i]; c < cs[i + 1]; c++) parent[ch[c]] = (uint32_t)i;
+  std::string s;
+  auto put = [&s](const void *p, size_t n) { s.append(reinterpret_cast<const char *>(p), n); };
+  const uint64_t sig = 88877711233ULL;
+  const char compressed = 0;
+  const uint32_t nn = (uint32_t)N;
+  const int32_t hdr[4] = {k, L, 0 /* L1_NORM */, 0 /* TF_IDF */}, mat[3] = {32, 1, 0 /* CV_8UC1 */};
+  put(&sig, 8), put(&compressed, 1), put(&nn, 4), put(hdr, 16);
+  // breadth-first over the child lists, so that a loader which attaches children in file order rebuilds every list in order
+  std::vector<uint32_t> order(1, 0);
+  for (size_t q = 0; q < order.size(); q++)
+    for (int c = cs[order[q]]; c < cs[order[q] + 1]; c++) order.push_back((uint32_t)ch[c]);
+  if ((int)order.size() != N) {
+    vo::set_error("vo_vocab_save: %d of %d nodes are reachable from the root", (int)order.size(), N);
+    return VO_ERR_INVALID;
+  }
+  uint32_t nw = 0;
+  for (size_t q = 1; q < order.size(); q++) {
+    const uint32_t id = order[q];
+    put(&id, 4), put(&parent[id], 4), put(&wt[id], 8), put(mat, 12), put(&desc[(size_t)id * 32], 32);
+    nw += wid[id] >= 0;
+  }
+  put(&nw, 4);
+  for (int i = 0; i < N; i++)
+    if (wid[i] >= 0) {
+      const uint32_t id = (uint32_t)i, w = (uint32_t)wid[i];
+      put(&id, 4), put(&w, 4);
+    }
+  std::ofstream f(path, std::ios::binary);
+  f.write(s.data(), (std::streamsize)s.size());
+  f.close();
+  if (!f) {
+    vo::set_error("vo_vocab_save: cannot write %s", path);
+    return VO_ERR_INVALID;
+  }
+  return VO_OK;
+}
+
 }  // extern "C"

@@ -857,6 +857,7 @@ __global__ __launch_bounds__(256) void k_bow_transform(VocabDev V, int n, const 
 
 struct vo_vocab {
   VocabDev V{};
+  int n_children = 0;
   vo::DevBuf b_cs, b_ch, b_wid, b_desc, b_w;
 };
 
@@ -889,7 +890,7 @@ int vo_vocab_create(vo_vocab **out, int n_nodes, int depth_L, const int32_t *chi
     delete v;
     return rc;
   }
-  v->V.n_nodes = n_nodes, v->V.depth = depth_L;
+  v->V.n_nodes = n_nodes, v->V.depth = depth_L, v->n_children = n_children;
   v->V.child_start = v->b_cs.as<int>(), v->V.children = v->b_ch.as<int>(), v->V.word_id = v->b_wid.as<int>();
   v->V.desc = v->b_desc.as<uint32_t>(), v->V.weight = v->b_w.as<double>();
   *out = v;
@@ -922,7 +923,38 @@ int vo_bow_transform(const vo_vocab *v, int n, const uint8_t *desc, int levelsup
   return vo::stream_sync(st, "vo_bow_transform");
 }
 
+int vo_vocab_tree(const vo_vocab *v, int *n_nodes, int *depth_L, int32_t *child_start, int32_t *children, uint8_t *node_desc,
+                  double *node_weight, int32_t *word_id) {
+  if (!v) return VO_ERR_INVALID;
+  if (n_nodes) *n_nodes = v->V.n_nodes;
+  if (depth_L) *depth_L = v->V.depth;
+  const size_t N = (size_t)v->V.n_nodes;
+  auto down = [](void *dst, const vo::DevBuf &b, size_t bytes) -> int {
+    if (dst && bytes) VO_HIP_CHECK(hipMemcpy(dst, b.p, bytes, hipMemcpyDeviceToHost));
+    return VO_OK;
+  };
+  VO_CHECK(down(child_start, v->b_cs, (N + 1) * 4));
+  VO_CHECK(down(children, v->b_ch, (size_t)v->n_children * 4));
+  VO_CHECK(down(node_desc, v->b_desc, N * 32));
+  VO_CHECK(down(node_weight, v->b_w, N * 8));
+  return down(word_id, v->b_wid, N * 4);
+}
+
 }  // extern "C"
+
+// ---- the trainer's use of a tree it has just built (vocab_train.hip): the descent of resident descriptors, the idf weights
+int vo::vocab_transform_resident(const vo_vocab *v, int n, const uint32_t *dev_desc, int levelsup, int *dev_word, double *dev_weight,
+                                 int *dev_node, hipStream_t st) {
+  if (n <= 0) return VO_OK;
+  hipLaunchKernelGGL(k_bow_transform, dim3((n + 255) / 256), dim3(256), 0, st, v->V, n, dev_desc, levelsup, dev_word, dev_weight, dev_node);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int vo::vocab_set_weights(vo_vocab *v, const double *node_weight, hipStream_t st) {
+  VO_CHECK(vo::copy_h2d(v->b_w.p, node_weight, (size_t)v->V.n_nodes * 8, st, "vo_vocab_train"));
+  return vo::stream_sync(st, "vo_vocab_train");
+}
 
 // ---- trackRefKeyFrame's search with the current frames resident in a frame store (vo_common.h) --------------------
 int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int B, const vo::RefKeyFrame *kfs, float ratio,

@@ -153,6 +153,11 @@ struct RefKeyFrame {
 };
 int bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int B, const RefKeyFrame *kfs, float ratio, int check_rot,
                         int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st);
+// vo_vocab_train's use of the tree it has built (match.hip): k_bow_transform over resident descriptors (4-byte aligned) into
+// resident outputs, enqueued on st; the node weights replaced (synchronises st)
+int vocab_transform_resident(const vo_vocab *v, int n, const uint32_t *dev_desc, int levelsup, int *dev_word, double *dev_weight,
+                             int *dev_node, hipStream_t st);
+int vocab_set_weights(vo_vocab *v, const double *node_weight, hipStream_t st);
 // device views of a frame store's per-slot arrays (guided.hip)
 struct FrameStoreView {
   int cap;
