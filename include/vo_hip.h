@@ -631,9 +631,10 @@ int vo_track_scatter_gather_dev(vo_frames *h, int slot0, int n_frames, const int
  * device for the frames that need it (a per-frame flag, a second candidate / replay pass over the flagged frames only).
  * Status bits VO_TRACK_FEW_MATCHES / VO_TRACK_FEW_INLIERS tell the caller that the reference would have left
  * trackWithMotion (:247, :253); the route it takes then is vo_tracker_track_ref_keyframe below (trackRefKeyFrame,
- * :256-277).  Relocalisation (:307-402) has its PnP RANSAC in vo_pnp_ransac / _dev; its control plane (candidates,
- * gates, guided re-searches) stays caller code around vo_match_bow / vo_pnp_ransac / vo_match_frame_keyframe /
- * vo_pose_only_solve.  Not covered either: the map-side steps between the two stages:
+ * :256-277).  Relocalisation (:313-395), the route of a LOST stream, is vo_tracker_relocalize below: the ordered walk
+ * over the caller's candidate key-frames (searchByBoW, EPnP RANSAC, solvePoseOnlySE3, the two guided top-ups, the five
+ * gates) runs on the device for the whole batch; Map::detectRelocalizationCandidates and the hand-over to trackLocalMap
+ * after a success stay caller code.  Not covered: the map-side steps between the two stages:
  * trackLocalMap derives localKeyframes_ / localMappoints_ from frame_curr_->mappoints_ AFTER the first stage's culling
  * (updateLocalKeyFrames / updateLocalMapPoints, :286-291), whereas this call takes the local map BEFORE it starts.  A
  * caller that needs the reference's order runs the two stages as two calls: vo_tracker_track with an empty local map
@@ -652,6 +653,9 @@ typedef struct {
   int32_t max_features;                                 /* feature slots per frame; 0: the extractor's bound */
   int32_t single_stream;
   void *stream, *extract_stream;                        /* hipStream_t or NULL */
+  /* relocalisation route (vo_tracker_relocalize): candidate key-frames per frame and features per candidate the tracker
+   * can hold; 0 = route unavailable (the config of a caller that does not know these fields) */
+  int32_t max_reloc_candidates, max_reloc_features;
 } vo_tracker_config;
 typedef struct {
   float radius;     /* searchByProjection(frame, last frame): 15 */
@@ -662,7 +666,7 @@ typedef struct {
   int32_t no_retry;  /* 0: a frame with < 20 matches is cleared and searched again at 2 x radius (:241-245), on the
                         device, before the solve; 1: no second search (the status bit still reports < 20) */
 } vo_tracker_params;
-enum { VO_TRACK_FEW_MATCHES = 1, VO_TRACK_FEW_INLIERS = 2 };
+enum { VO_TRACK_FEW_MATCHES = 1, VO_TRACK_FEW_INLIERS = 2, VO_TRACK_RELOC_FAILED = 4 };
 int vo_tracker_create(vo_tracker **out, const vo_tracker_config *cfg);
 void vo_tracker_destroy(vo_tracker *t);
 int vo_tracker_info(const vo_tracker *t, int *batch, int *max_features, int *max_keypoints, int *n_levels);
@@ -725,6 +729,45 @@ int vo_tracker_track_ref_keyframe(vo_tracker *t, const uint8_t *images, const vo
 int vo_tracker_track_ref_keyframe_dev(vo_tracker *t, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
                                       const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
                                       const vo_tracker_params *params, int first_stage_only);
+/* VisualOdometry::relocalization() (visualOdometry.cpp:313-395) for every frame of the batch, from Frame construction
+ * to the pose.  Per frame and candidate key-frame IN THE CALLER'S ORDER, candidates flagged bad skipped:
+ *   Matcher(0.75).searchByBoW(kf, frame); < 15 matches: next.  poseEstimateByPnP (:776-826) = vo_pnp_ransac_dev(100, 8.0,
+ *   0.99) on the matches in feature order; its inliers' map points and its pose are written into the frame BEFORE the
+ *   `< 10` gate (:336), so a rejected candidate with 1..9 inliers leaves both behind for the next one.
+ *   solvePoseOnlySE3 over ALL non-null slots; < 10: next (pose and outliers_ kept, nothing culled).  Outliers culled;
+ *   < 50: searchByProjection(frame, kf, 10, 100, found = this candidate's PnP inliers); sum >= 50: solve (NOT culled);
+ *   in (30, 50): found = every point in the frame, searchByProjection(frame, kf, 3, 60, found); sum >= 50: solve, cull.
+ *   inliers_num_ >= 50: success, the walk stops.
+ * MapPoint identity (found.count, the leaked slots) is an int32 id per key-frame feature: the same map point carries
+ * the same id in every candidate of a frame; ids lie in [0, max_reloc_candidates x max_reloc_features).
+ * vo_tracker_set_reloc_candidates: cands [batch][max_cand] (n_cand[f] <= max_cand of them used per frame), every array
+ * copied before the call returns; more candidates or features than configured: VO_ERR_CAPACITY, nothing is truncated.
+ * The BoW searches and the PnP of all batch x max_cand pairs run in one pass (they do not depend on the walk); then
+ * max_cand rounds of the dependent tail are enqueued unconditionally, round r serving candidate r of every frame still
+ * walking.  The common-node walk of searchByBoW is host work: the call synchronises ONCE, after computeBow, and is
+ * asynchronous from there.  vo_tracker_results: pose, n_tracked = n_inliers = inliers_num_, status VO_TRACK_RELOC_FAILED
+ * when no candidate (or none at all) reached 50; VO_TRACKER_FEATURE_HAS_POINT / _POINTS / _OUTLIER and the
+ * VO_TRACKER_RELOC_* selectors describe the frame at the end.  Deviation: the P3P path of solvePnPRansac at exactly 4
+ * correspondences (vo_pnp_ransac) cannot occur here (>= 15 matches). */
+typedef struct {
+  int32_t n;                 /* features of the key-frame */
+  int32_t bad;               /* KeyFrame::isBad() */
+  const float *angle;        /* [n] unKeypoints_[i].angle */
+  const uint8_t *desc;       /* [n][32] descriptors_ */
+  const vo_bow_view *nodes;  /* featVec_ (levelsup 3) */
+  const uint8_t *flags;      /* [n] bit 0: the feature's map point exists and is not bad */
+  const double *points;      /* [n][3] MapPoint::getPose() */
+  const int32_t *ids;        /* [n] map point id */
+  const uint8_t *point_desc; /* [n][32] MapPoint::getDescriptor() */
+  const float *min_distance, *max_distance; /* [n] minDistance_, maxDistance_ */
+} vo_reloc_candidate;
+int vo_tracker_set_reloc_candidates(vo_tracker *t, const vo_vocab *vocab, int max_cand, const int32_t *n_cand,
+                                    const vo_reloc_candidate *cands);
+int vo_tracker_relocalize(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind,
+                          const vo_tracker_params *params);
+int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
+                              const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
+                              const vo_tracker_params *params);
 /* Waits for the batch and copies out (any pointer may be NULL): poses as se3 [batch][6] and as Tcw
  * [batch][12]; n_tracked = inliers of the second solve whose map point has observations (inliers_num_,
  * :289-300); n_inliers = the second solve's return value; the two searches' match counts; status bits.
@@ -743,7 +786,16 @@ enum {
   VO_TRACKER_LOCAL_FLAGS = 7, VO_TRACKER_LOCAL_U = 8, VO_TRACKER_LOCAL_V = 9, VO_TRACKER_LOCAL_UR = 10,
   VO_TRACKER_LOCAL_LEVEL = 11, VO_TRACKER_LOCAL_VIEWCOS = 12, /* Frame::isInFrame's outputs per local point */
   VO_TRACKER_KEYPOINT_COUNTS = 13,   /* int32 [batch] */
-  VO_TRACKER_FEATURE_OUTLIER = 14    /* uint8: frame->outliers_[i] after the second solve (valid after the local-map stage) */
+  VO_TRACKER_FEATURE_OUTLIER = 14,   /* uint8: frame->outliers_[i] after the second solve (valid after the local-map stage) */
+  /* after vo_tracker_relocalize ([batch][max_reloc_candidates] = the configured capacity as the row length) */
+  VO_TRACKER_RELOC_WINNER = 15,      /* int32 [batch]: index of the candidate that relocalised the frame, -1 on failure */
+  VO_TRACKER_RELOC_POINT_IDS = 16,   /* int32 [batch][max_features]: id of frame->mappoints_[i] at the end, -1 = null */
+  VO_TRACKER_RELOC_BOW_MATCHES = 17, /* int32 [batch][max_reloc_candidates]: searchByBoW's return value (0: bad / absent) */
+  VO_TRACKER_RELOC_PNP_INLIERS = 18, /* int32 [..][..]: poseEstimateByPnP's return value (0: not run) */
+  VO_TRACKER_RELOC_OUTCOME = 19,     /* int32 [..][..]: 0 bad, 1 < 15 BoW matches, 2 < 10 PnP inliers, 3 < 10 solve inliers,
+                                        4 below 50 at the end, 5 success, 6 not reached */
+  VO_TRACKER_RELOC_PNP_MASK = 20     /* uint8 [batch][max_reloc_candidates][max_features] (debug): per frame feature 0 = no
+                                        PnP correspondence, 1 = correspondence, RANSAC outlier, 2 = RANSAC inlier */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 int vo_tracker_sync(vo_tracker *t);

@@ -1,9 +1,12 @@
 #!/usr/bin/env python3
 """PnP RANSAC throughput (vo_pnp_ransac_dev): 1024 problems x {50, 150, 400} correspondences with 30 %
 outliers, 100 hypotheses each, against the numpy restatement (tests/pnp_ref.py) on one thread.  Prints one JSON line.
-(The relocalisation route around it -- BoW candidates, PnP, pose-only solve, guided re-searches -- is caller code, not
-a library entry point, so there is no relocalised-frames figure here.)
-usage: tools/reloc_bench.py [--problems 1024] [--reps 20] [--ref-problems 8]"""
+--route: relocalised frames per second of the tracker route (vo_tracker_relocalize_dev) at batch 1024 with up
+to 3 candidates per frame on the geometry of tests/reloc_inputs.py (its six frames tiled), next to the HOST-COMPOSED route
+the library offered before, timed in the same run: per candidate round vo_match_bow_batch -> vo_pnp_ransac ->
+vo_pose_only_solve -> vo_match_frame_keyframe ... with the decisions in this script.  The composed figure leaves Frame
+construction out (it starts from features already on the host); the device figure includes it.
+usage: tools/reloc_bench.py [--problems 1024] [--reps 20] [--ref-problems 8] | --route [--batch 1024] [--reps 5] [--out FILE]"""
 import argparse
 import json
 import os
@@ -21,12 +24,178 @@ sys.path.insert(0, str(ROOT / "tests"))
 import numpy as np  # noqa: E402
 
 
+def _project(pose6, kf, found_mask, cam5, sf1, vo):
+    """prologue of searchByProjection(Frame*, KeyFrame*) (matcher.cpp:165-203), vectorised on the host"""
+    R, t = vo.se3_exp(pose6)
+    P = kf["points"]
+    pc = P @ R.T + t
+    ow = -R.T @ t
+    z = pc[:, 2].astype(np.float32)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = (np.float64(cam5[0]) * pc[:, 0] / pc[:, 2] + np.float64(cam5[2])).astype(np.float32)
+        v = (np.float64(cam5[1]) * pc[:, 1] / pc[:, 2] + np.float64(cam5[3])).astype(np.float32)
+        dist = np.linalg.norm(P - ow, axis=1).astype(np.float32)
+        lv = np.ceil(np.log((kf["max_dist"] / dist).astype(np.float64)).astype(np.float32) / np.float32(np.log(np.float64(sf1))))
+    ok = ((kf["flags"] & 1) == 1) & ~found_mask & (z > 0) & (u >= 0) & (u <= 640) & (v >= 0) & (v <= 480)
+    ok &= ~((dist < np.float32(0.8) * kf["min_dist"]) | (dist > np.float32(1.2) * kf["max_dist"]))
+    lv = np.clip(np.nan_to_num(lv), 0, 7).astype(np.int32)
+    return dict(flags=ok.astype(np.uint8), u=np.where(ok, u, 0).astype(np.float32), v=np.where(ok, v, 0).astype(np.float32),
+                level=np.where(ok, lv, 0).astype(np.int32), angle=kf["angle"], desc=kf["point_desc"])
+
+
+def composed_route(vo, frames, fa, fbow, cands, cbow, ca, cam5, sf, max_cand):
+    """the route with the library's host entry points, one batched call per step and round, decisions here -> winners"""
+    B = len(frames)
+    mt = vo.Matcher(0.75)
+    cam_d = np.asarray(cam5, np.float64)
+    ids = [np.full(len(fr[0]), -1, np.int64) for fr in frames]
+    fpt = [np.zeros((len(fr[0]), 3)) for fr in frames]
+    outl = [np.zeros(len(fr[0]), np.uint8) for fr in frames]
+    pose, inl, winner = np.zeros((B, 6)), np.zeros(B, np.int32), np.full(B, -1)
+
+    def solve(fs):
+        if not fs:
+            return
+        prs, idxs = [], []
+        for f in fs:
+            k, _, ux, uy, ur, _ = frames[f]
+            idx = np.nonzero(ids[f] >= 0)[0]
+            idxs.append(idx)
+            prs.append(dict(pts=fpt[f][idx], obs=np.stack([ux[idx], uy[idx], ur[idx]], 1).astype(np.float64),
+                            inv_sigma=1.0 / sf[k["octave"][idx]].astype(np.float64), cam=cam_d, pose0=pose[f]))
+        ps, masks, ninl = vo.Optimizer.solvePoseOnlySE3(prs)
+        for j, f in enumerate(fs):
+            pose[f], inl[f] = ps[j], ninl[j]
+            outl[f][idxs[j]] = masks[j]
+
+    def cull(f):
+        ids[f][(outl[f] != 0) & (ids[f] >= 0)] = -1
+
+    def top_up(f, kf, radius, th, found_mask):
+        q = _project(pose[f], kf, found_mask, cam5, sf[1], vo)
+        n, a = mt.searchByProjection_keyframe(fa[f], q, radius, th, True, sf, (ids[f] >= 0).astype(np.uint8))
+        new = a >= 0
+        ids[f][new], fpt[f][new] = kf["ids"][a[new]], kf["points"][a[new]]
+        return n
+
+    for r in range(max_cand):
+        act = [f for f in range(B) if winner[f] < 0 and r < len(cands[f]) and not cands[f][r].get("bad", False)]
+        if not act:
+            continue
+        pairs = [(ca[f][r], cands[f][r]["flags"] & 1, cbow[f][r], fa[f], np.ones(fa[f].view.n, np.uint8), fbow[f]) for f in act]
+        counts, matches = mt.searchByBoW_batch(pairs, False)
+        act2 = [(f, m) for f, c, m in zip(act, counts, matches) if c >= 15]
+        if not act2:
+            continue
+        probs, srcs = [], []
+        for f, m in act2:
+            src = np.nonzero(m >= 0)[0]
+            srcs.append(src)
+            probs.append((cands[f][r]["points"][m[src]].astype(np.float32), np.stack([frames[f][2][src], frames[f][3][src]], 1)))
+        res = vo.pnp_ransac(probs, cam5[:4])
+        s1, found = [], {}
+        for j, (f, m) in enumerate(act2):
+            if res["status"][j] != 1:
+                continue
+            hit = srcs[j][res["inliers"][j]]
+            if len(hit) == 0:
+                continue
+            kf = cands[f][r]
+            ids[f][hit], fpt[f][hit], pose[f] = kf["ids"][m[hit]], kf["points"][m[hit]], res["pose6"][j]
+            if len(hit) >= 10:
+                s1.append(f)
+                found[f] = np.isin(kf["ids"], kf["ids"][m[hit]])
+        solve(s1)
+        t1 = []
+        for f in s1:
+            if inl[f] < 10:
+                continue
+            cull(f)
+            if inl[f] >= 50:
+                winner[f] = r
+            else:
+                t1.append(f)
+        s2 = [f for f in t1 if inl[f] + top_up(f, cands[f][r], 10.0, 100.0, found[f]) >= 50]
+        solve(s2)
+        s3 = []
+        for f in s2:
+            if 30 < inl[f] < 50:
+                kf = cands[f][r]
+                if inl[f] + top_up(f, kf, 3.0, 60.0, np.isin(kf["ids"], ids[f][ids[f] >= 0])) >= 50:
+                    s3.append(f)
+            elif inl[f] >= 50:
+                winner[f] = r
+        solve(s3)
+        for f in s3:
+            cull(f)
+            if inl[f] >= 50:
+                winner[f] = r
+    return winner
+
+
+def route(a):
+    import torch
+    import oracle_lib as orc
+    import reloc_inputs
+    from vo_slam_test_amd import _lib as vo
+    fx = reloc_inputs.build(orc)
+    nfx, B = len(fx["frames"]), a.batch
+    pick = [i % nfx for i in range(B)]
+    vd = fx["vocab"]
+    voc = vo.Vocabulary(vd["L"], vd["child_start"], vd["children"], vd["node_desc"], vd["node_weight"], vd["word_id"])
+    trk = vo.Tracker(B, fx["cam5"], None, reloc_inputs.W, reloc_inputs.H, max_last=8, max_local=8, inv_depth_scale=float(fx["inv"]),
+                     max_reloc_candidates=reloc_inputs.MAX_CAND, max_reloc_features=fx["nk"])
+    trk.set_reloc_candidates(voc, [fx["candidates"][i] for i in pick])
+    imgs = torch.from_numpy(np.ascontiguousarray(fx["imgs"][pick])).cuda()
+    raw = torch.from_numpy(np.ascontiguousarray(fx["raw"][pick]).view(np.int16)).cuda()
+    times = []
+    for rep in range(a.reps + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        trk.relocalize_dev(imgs, raw)
+        trk.sync()
+        times.append(time.perf_counter() - t0)
+    dev_s = float(np.median(times[1:]))
+    win = trk.get(trk.RELOC_WINNER)
+    trk.close()
+    # host-composed route: everything it needs on the host already, views and FeatureVectors prepared outside the clock
+    frames = [fx["frames"][i] for i in pick]
+    fa1 = [vo.FrameArrays(fr[2], fr[3], fr[0]["octave"], fr[0]["angle"], fr[4], fr[1]) for fr in fx["frames"]]
+    fb1 = [vo.BowNodes(n) for n in fx["fnodes"]]
+    ca1 = [[vo.FrameArrays(np.zeros(len(k["flags"]), np.float32), np.zeros(len(k["flags"]), np.float32), np.zeros(len(k["flags"]), np.int32),
+                           k["angle"], np.full(len(k["flags"]), -1, np.float32), k["desc"]) for k in cl] for cl in fx["candidates"]]
+    cb1 = [[vo.BowNodes(k["nodes"]) for k in cl] for cl in fx["candidates"]]
+    tile = lambda xs: [xs[i] for i in pick]
+    ctimes = []
+    for rep in range(max(1, a.reps // 3) + 1):
+        t0 = time.perf_counter()
+        cw = composed_route(vo, frames, tile(fa1), tile(fb1), tile(fx["candidates"]), tile(cb1), tile(ca1), fx["cam5"], fx["sf"],
+                            reloc_inputs.MAX_CAND)
+        ctimes.append(time.perf_counter() - t0)
+    comp_s = float(np.median(ctimes[1:]))
+    out = {"metric": "relocalised_frames_per_s", "batch": B, "max_candidates": reloc_inputs.MAX_CAND,
+           "device_route": {"s_per_batch": round(dev_s, 5), "frames_per_s": round(B / dev_s, 1), "includes_frame_construction": True,
+                            "relocalised": int((win >= 0).sum())},
+           "host_composed_route": {"s_per_batch": round(comp_s, 5), "frames_per_s": round(B / comp_s, 1),
+                                   "includes_frame_construction": False, "relocalised": int((cw >= 0).sum())},
+           "device_over_composed": round(comp_s / dev_s, 2), "winners_equal": bool(np.array_equal(win, cw))}
+    print(json.dumps(out))
+    if a.out:
+        pathlib.Path(a.out).write_text(json.dumps(out, indent=1) + "\n")
+    voc.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--route", action="store_true")
+    ap.add_argument("--batch", type=int, default=1024)
+    ap.add_argument("--out", default="")
     ap.add_argument("--problems", type=int, default=1024)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--ref-problems", type=int, default=8)
     a = ap.parse_args()
+    if a.route:
+        return route(a)
     import torch
     from vo_slam_test_amd import _lib as vo
     import pnp_ref as pr

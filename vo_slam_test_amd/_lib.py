@@ -49,6 +49,7 @@ SYMBOLS = [
     "vo_track_project_dev", "vo_track_scatter_dev", "vo_track_gather_dev", "vo_track_scatter_gather_dev", "vo_pose_only_solve_ranges_dev",
     "vo_tracker_track_first", "vo_tracker_track_first_dev", "vo_tracker_track_local_map", "vo_tracker_set_ref_keyframe",
     "vo_tracker_track_ref_keyframe", "vo_tracker_track_ref_keyframe_dev",
+    "vo_tracker_set_reloc_candidates", "vo_tracker_relocalize", "vo_tracker_relocalize_dev",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -428,7 +429,13 @@ class TrackerConfig(C.Structure):
                 ("intrinsics", C.c_float * 5), ("dist_coef", C.c_float * 5), ("has_distortion", C.c_int32),
                 ("inv_depth_scale", C.c_float), ("max_last", C.c_int32), ("max_local", C.c_int32),
                 ("max_features", C.c_int32), ("single_stream", C.c_int32), ("stream", C.c_void_p),
-                ("extract_stream", C.c_void_p)]
+                ("extract_stream", C.c_void_p), ("max_reloc_candidates", C.c_int32), ("max_reloc_features", C.c_int32)]
+
+
+class RelocCandidate(C.Structure):
+    _fields_ = [("n", C.c_int32), ("bad", C.c_int32), ("angle", C.c_void_p), ("desc", C.c_void_p), ("nodes", C.c_void_p),
+                ("flags", C.c_void_p), ("points", C.c_void_p), ("ids", C.c_void_p), ("point_desc", C.c_void_p),
+                ("min_distance", C.c_void_p), ("max_distance", C.c_void_p)]
 
 
 class TrackerParams(C.Structure):
@@ -441,14 +448,17 @@ class Tracker:
     batch (include/vo_hip.h).  This class only marshals arrays; torch appears where the caller hands over device
     tensors (images, depth) or streams."""
     (ASSIGNED_LAST, ASSIGNED_LOCAL, POSE_FIRST, INLIERS_FIRST, OBSERVED_INLIERS_FIRST, FEATURE_HAS_POINT, FEATURE_POINTS,
-     LOCAL_FLAGS, LOCAL_U, LOCAL_V, LOCAL_UR, LOCAL_LEVEL, LOCAL_VIEWCOS, KEYPOINT_COUNTS, FEATURE_OUTLIER) = range(15)
+     LOCAL_FLAGS, LOCAL_U, LOCAL_V, LOCAL_UR, LOCAL_LEVEL, LOCAL_VIEWCOS, KEYPOINT_COUNTS, FEATURE_OUTLIER,
+     RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK) = range(21)
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
-    FEW_MATCHES, FEW_INLIERS = 1, 2
+    FEW_MATCHES, FEW_INLIERS, RELOC_FAILED = 1, 2, 4
 
     def __init__(self, batch, intrinsics5, dist_coef=None, width=640, height=480, max_last=1024, max_local=2048,
                  inv_depth_scale=1.0, nfeatures=1000, scale_factor=1.2, nlevels=8, ini_th=20, min_th=7, max_features=0,
-                 stream=None, extract_stream=None, single_stream=False):
+                 stream=None, extract_stream=None, single_stream=False, max_reloc_candidates=0, max_reloc_features=0):
         cfg = TrackerConfig()
+        cfg.max_reloc_candidates, cfg.max_reloc_features = int(max_reloc_candidates), int(max_reloc_features)
+        self.max_reloc_candidates = int(max_reloc_candidates)
         cfg.batch, cfg.width, cfg.height = int(batch), int(width), int(height)
         cfg.nfeatures, cfg.nlevels, cfg.ini_th_fast, cfg.min_th_fast = int(nfeatures), int(nlevels), int(ini_th), int(min_th)
         cfg.scale_factor = float(scale_factor)
@@ -572,6 +582,49 @@ class Tracker:
         check(lib().vo_tracker_track_ref_keyframe(self._h, _p(img), _p(dp), kind, C.byref(pr), int(bool(first_stage_only))),
               "vo_tracker_track_ref_keyframe")
 
+    def set_reloc_candidates(self, vocab, candidates):
+        """candidates[f] = the frame's candidate key-frames in the order VisualOdometry::relocalization walks them, each a
+        dict(angle, desc, nodes (per-feature node ids), flags, points, ids, point_desc, min_dist, max_dist, bad=False)"""
+        assert len(candidates) == self.B
+        mc = max([len(c) for c in candidates] + [0])
+        n_cand = np.array([len(c) for c in candidates], np.int32)
+        arr = (RelocCandidate * max(self.B * mc, 1))()
+        keep = []
+        for f, cl in enumerate(candidates):
+            for c, k in enumerate(cl):
+                a = dict(angle=np.ascontiguousarray(k["angle"], np.float32), desc=np.ascontiguousarray(k["desc"], np.uint8),
+                         flags=np.ascontiguousarray(k["flags"], np.uint8), points=np.ascontiguousarray(k["points"], np.float64),
+                         ids=np.ascontiguousarray(k["ids"], np.int32), point_desc=np.ascontiguousarray(k["point_desc"], np.uint8),
+                         min_distance=np.ascontiguousarray(k["min_dist"], np.float32),
+                         max_distance=np.ascontiguousarray(k["max_dist"], np.float32))
+                nodes = BowNodes(np.asarray(k["nodes"]))
+                keep.append((a, nodes))
+                rc = arr[f * mc + c]
+                rc.n, rc.bad = len(a["flags"]), int(bool(k.get("bad", False)))
+                for key, v in a.items():
+                    setattr(rc, key, v.ctypes.data)
+                rc.nodes = C.addressof(nodes.view)
+        check(lib().vo_tracker_set_reloc_candidates(self._h, vocab._h, int(mc), _p(n_cand), arr), "vo_tracker_set_reloc_candidates")
+        self._reloc_vocab = vocab  # the C side keeps the pointer
+
+    def relocalize(self, images, depth=None):
+        """VisualOdometry::relocalization() from host arrays (Frame construction to pose); results() / get(RELOC_*) after"""
+        img = np.ascontiguousarray(images, np.uint8)
+        kind, dp = 0, None
+        if depth is not None:
+            dp = np.ascontiguousarray(depth)
+            kind = 1 if dp.dtype == np.float32 else 2
+        check(lib().vo_tracker_relocalize(self._h, _p(img), _p(dp), kind, None), "vo_tracker_relocalize")
+
+    def relocalize_dev(self, images, depth=None):
+        """the same from device tensors (uint8 [B,H,W]; depth float32 / (u)int16 [B,H,W] or None)"""
+        kind, fs, pitch = 0, 0, 0
+        if depth is not None:
+            kind = 1 if depth.element_size() == 4 else 2
+            fs, pitch = depth.stride(0) * depth.element_size(), depth.stride(1) * depth.element_size()
+        check(lib().vo_tracker_relocalize_dev(self._h, _p(images), int(images.stride(1)), C.c_size_t(images.stride(0)), _p(depth),
+                                              kind, C.c_size_t(fs), int(pitch), None), "vo_tracker_relocalize_dev")
+
     def results(self):
         B = self.B
         out = dict(pose=np.zeros((B, 6)), Tcw=np.zeros((B, 12)), n_tracked=np.zeros(B, np.int32), n_inliers=np.zeros(B, np.int32),
@@ -582,7 +635,7 @@ class Tracker:
         return out
 
     def get(self, what):
-        B, cap, nl = self.B, self.cap, self.max_local
+        B, cap, nl, mrc = self.B, self.cap, self.max_local, max(self.max_reloc_candidates, 1)
         shape, dt = {
             self.ASSIGNED_LAST: ((B, cap), np.int32), self.ASSIGNED_LOCAL: ((B, cap), np.int32),
             self.POSE_FIRST: ((B, 6), np.float64), self.INLIERS_FIRST: ((B,), np.int32),
@@ -591,7 +644,10 @@ class Tracker:
             self.LOCAL_U: ((B, max(nl, 1)), np.float32), self.LOCAL_V: ((B, max(nl, 1)), np.float32),
             self.LOCAL_UR: ((B, max(nl, 1)), np.float32), self.LOCAL_LEVEL: ((B, max(nl, 1)), np.int32),
             self.LOCAL_VIEWCOS: ((B, max(nl, 1)), np.float32), self.KEYPOINT_COUNTS: ((B,), np.int32),
-            self.FEATURE_OUTLIER: ((B, cap), np.uint8)}[what]
+            self.FEATURE_OUTLIER: ((B, cap), np.uint8), self.RELOC_WINNER: ((B,), np.int32),
+            self.RELOC_POINT_IDS: ((B, cap), np.int32), self.RELOC_BOW_MATCHES: ((B, mrc), np.int32),
+            self.RELOC_PNP_INLIERS: ((B, mrc), np.int32), self.RELOC_OUTCOME: ((B, mrc), np.int32),
+            self.RELOC_PNP_MASK: ((B, mrc, cap), np.uint8)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out

@@ -25,6 +25,7 @@ SOURCES = [
     ("guided.hip", ["-ffp-contract=off"]),
     ("track.hip", ["-ffp-contract=off"]),
     ("tracker.hip", ["-ffp-contract=off"]),
+    ("reloc.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-ffp-contract=fast"]),
     ("pose_only.hip", ["-ffp-contract=fast"]),
     ("sim3.hip", ["-ffp-contract=fast"]),

@@ -147,6 +147,35 @@ VO_HD void se3_log(const Se3 &T, double xi[6]) {
   xi[3] = wx, xi[4] = wy, xi[5] = wz;
 }
 
+// log of a pose given as rotation matrix (row-major) + translation: the matrix -> unit quaternion step has the branch
+// structure of Eigen's Quaternion(Matrix3), then Sophus SE3::log (vo_se3_log; the relocalisation route's PnP pose)
+VO_HD void se3_log_from_R(const double R[9], const double t[3], double xi[6]) {
+  Se3 T;
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0) {
+    double s = sqrt(tr + 1.0);
+    T.q[0] = 0.5 * s;
+    s = 0.5 / s;
+    T.q[1] = (R[7] - R[5]) * s, T.q[2] = (R[2] - R[6]) * s, T.q[3] = (R[3] - R[1]) * s;
+  } else {
+    int i = 0;
+    if (R[4] > R[0]) i = 1;
+    if (R[8] > R[i * 4]) i = 2;
+    const int j = (i + 1) % 3, k = (j + 1) % 3;
+    double s = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
+    double q[4];
+    q[1 + i] = 0.5 * s;
+    s = 0.5 / s;
+    q[0] = (R[k * 3 + j] - R[j * 3 + k]) * s;
+    q[1 + j] = (R[j * 3 + i] + R[i * 3 + j]) * s;
+    q[1 + k] = (R[k * 3 + i] + R[i * 3 + k]) * s;
+    for (int a = 0; a < 4; a++) T.q[a] = q[a];
+  }
+  quat_normalize(T.q);
+  T.t[0] = t[0], T.t[1] = t[1], T.t[2] = t[2];
+  se3_log(T, xi);
+}
+
 // The same with the Newton-refined reciprocals of the FAST forms (pose-only LM: one log per iteration, in a dependent
 // chain that nothing overlaps): 1 / n is the rsqrt that forms n, theta w / (2 n) = f w / 2.  The degenerate inputs
 // (rotation below 1e-10, w = 0) take the plain function.

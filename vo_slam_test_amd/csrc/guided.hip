@@ -1493,7 +1493,7 @@ int vo_match_sim3_mutual(const vo_frame_view *kf1, const vo_frame_view *kf2, con
 }  // extern "C"
 
 vo::FrameStoreView vo::frame_store_view(const vo_frames *h) {
-  return vo::FrameStoreView{h->cap, h->D.desc, h->D.angle, h->D.n};
+  return vo::FrameStoreView{h->cap, h->D.desc, h->D.angle, h->D.n, h->D.x, h->D.y, h->D.uright, h->D.octave};
 }
 
 const int *vo::guided_error_flag(const vo_frames *h) { return h ? h->b_err.as<int>() : nullptr; }

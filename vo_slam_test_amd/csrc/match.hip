@@ -958,8 +958,9 @@ int vo::vocab_set_weights(vo_vocab *v, const double *node_weight, hipStream_t st
 
 // ---- trackRefKeyFrame's search with the current frames resident in a frame store (vo_common.h) --------------------
 int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int B, const vo::RefKeyFrame *kfs, float ratio,
-                            int check_rot, int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st) {
-  if (!v || !frames || B < 1 || !kfs || !dev_assigned || !dev_n_matches) return VO_ERR_INVALID;
+                            int check_rot, int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st,
+                            int per, vo::BowResidentBufs *own) {
+  if (!v || !frames || B < 1 || per < 1 || !kfs || !dev_assigned || !dev_n_matches) return VO_ERR_INVALID;
   const vo::FrameStoreView fs = vo::frame_store_view(frames);
   if (fs.cap != cap || cap > kNodeMaxB) {
     vo::set_error("BoW search on resident frames: %d feature slots per frame (the store has %d, the kernel handles %d)", cap, fs.cap, kNodeMaxB);
@@ -967,9 +968,12 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
   }
   const char *what = "trackRefKeyFrame search";
   // Frame::computeBow (frame.cpp:248-253): the node of every feature at level L - levelsup, straight from the store's slots
-  thread_local vo::ScratchBuf d_w, d_wt, d_node, d_img;
-  thread_local vo::PinnedBuf stage;
+  thread_local vo::ScratchBuf t_w, t_wt, t_node, t_img;
+  thread_local vo::PinnedBuf t_stage, t_up;
+  vo::DevBuf &d_w = own ? own->w : t_w, &d_wt = own ? own->wt : t_wt, &d_node = own ? own->node : t_node, &d_img = own ? own->img : t_img;
+  vo::PinnedBuf &stage = own ? own->stage : t_stage, &up = own ? own->up : t_up;
   const size_t N = (size_t)B * cap;
+  const int NP = B * per;  // pairs: pair p searches frame p / per
   VO_CHECK(d_w.reserve(N * 4));
   VO_CHECK(d_wt.reserve(N * 8));
   VO_CHECK(d_node.reserve(N * 4));
@@ -991,27 +995,32 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
     if (bytes && src) memcpy(img.data() + off, src, bytes);
     return off;
   };
-  const size_t args_off = put(nullptr, (size_t)B * sizeof(NodeArgs));
+  const size_t args_off = put(nullptr, (size_t)NP * sizeof(NodeArgs));
   struct Off { size_t q, bf, ok, adesc, aang, claims; int nq, nB; };
-  std::vector<Off> off((size_t)B);
+  std::vector<Off> off((size_t)NP);
   size_t claims_bytes = 0;
   int max_b = 1;
   std::vector<int> order, queries;
   std::vector<uint32_t> bfeat;
   std::vector<int32_t> bnode, bstart;
-  for (int f = 0; f < B; f++) {
-    const vo::RefKeyFrame &K = kfs[f];
+  std::vector<uint32_t> bnode_u;
+  size_t bf_off = 0, ok_off = 0;
+  for (int pr = 0; pr < NP; pr++) {
+    const int f = pr / per;
+    const vo::RefKeyFrame &K = kfs[pr];
     const int nB = std::min(std::max(h_n[f], 0), cap);
-    const int *node = h_node + (size_t)f * cap;
-    order.resize((size_t)nB);
-    for (int i = 0; i < nB; i++) order[i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return node[a] < node[b]; });
-    bfeat.assign(order.begin(), order.end());
-    bnode.clear(), bstart.clear();
-    for (int i = 0; i < nB; i++)
-      if (i == 0 || node[order[i]] != node[order[i - 1]]) bnode.push_back(node[order[i]]), bstart.push_back(i);
-    bstart.push_back(nB);
-    std::vector<uint32_t> bnode_u(bnode.begin(), bnode.end());
+    if (pr % per == 0) {  // the frame's FeatureVector, once for its pairs
+      const int *node = h_node + (size_t)f * cap;
+      order.resize((size_t)nB);
+      for (int i = 0; i < nB; i++) order[i] = i;
+      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return node[a] < node[b]; });
+      bfeat.assign(order.begin(), order.end());
+      bnode.clear(), bstart.clear();
+      for (int i = 0; i < nB; i++)
+        if (i == 0 || node[order[i]] != node[order[i - 1]]) bnode.push_back(node[order[i]]), bstart.push_back(i);
+      bstart.push_back(nB);
+      bnode_u.assign(bnode.begin(), bnode.end());
+    }
     const vo_bow_view bv{(int32_t)bnode.size(), bnode_u.data(), bstart.data(), bfeat.data()};
     queries.clear();
     if (K.n > 0 && nB > 0 && K.nodes)
@@ -1022,12 +1031,15 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
           queries.push_back(i1), queries.push_back(bstart[ib]), queries.push_back(bstart[ib + 1]), queries.push_back(0);
         }
       });
-    Off &o = off[f];
+    Off &o = off[pr];
     o.nq = (int)queries.size() / 4, o.nB = nB;
     o.q = put(queries.data(), queries.size() * 4);
-    o.bf = put(bfeat.data(), (size_t)nB * 4);
-    std::vector<uint8_t> ok((size_t)std::max(nB, 1), 1);
-    o.ok = put(ok.data(), ok.size());
+    if (pr % per == 0) {
+      bf_off = put(bfeat.data(), (size_t)nB * 4);
+      std::vector<uint8_t> ok((size_t)std::max(nB, 1), 1);
+      ok_off = put(ok.data(), ok.size());
+    }
+    o.bf = bf_off, o.ok = ok_off;
     o.adesc = put(K.desc, (size_t)K.n * 32);
     o.aang = put(K.angle, (size_t)K.n * 4);
     o.claims = claims_bytes;
@@ -1038,10 +1050,11 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
   VO_CHECK(d_img.reserve(img_bytes + claims_bytes + 256));
   uint8_t *d = d_img.as<uint8_t>();
   NodeArgs *hargs = reinterpret_cast<NodeArgs *>(img.data() + args_off);
-  for (int f = 0; f < B; f++) {
-    const Off &o = off[f];
+  for (int pr = 0; pr < NP; pr++) {
+    const int f = pr / per;
+    const Off &o = off[pr];
     NodeArgs P{};
-    P.mode = kNodeBow0, P.nq = o.nq, P.nA = kfs[f].n, P.nB = o.nB, P.check_rot = check_rot, P.ratio = ratio;
+    P.mode = kNodeBow0, P.nq = o.nq, P.nA = kfs[pr].n, P.nB = o.nB, P.check_rot = check_rot, P.ratio = ratio;
     for (int i = 0; i < 16; i++) P.sf[i] = 1.f;
     P.queries = reinterpret_cast<const int4 *>(d + o.q), P.bfeat = reinterpret_cast<const uint32_t *>(d + o.bf);
     P.descA = reinterpret_cast<const uint4 *>(d + o.adesc);
@@ -1049,19 +1062,20 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
     P.angA = reinterpret_cast<const float *>(d + o.aang), P.angB = fs.angle + (size_t)(slot0 + f) * cap;
     P.b_ok = d + o.ok;
     P.claims = reinterpret_cast<int4 *>(d + img_bytes + o.claims);
-    P.match = dev_assigned + (size_t)f * cap;
-    P.n_matches = dev_n_matches + f;
-    hargs[f] = P;
+    P.match = dev_assigned + (size_t)pr * cap;
+    P.n_matches = dev_n_matches + pr;
+    hargs[pr] = P;
   }
-  thread_local vo::PinnedBuf up;
   VO_CHECK(up.reserve(img.size()));
   memcpy(up.data(), img.data(), img.size());
   VO_CHECK(vo::copy_h2d(d, up.data(), img.size(), st, what));
   const size_t lds = (((size_t)max_b + 15) & ~(size_t)15) * 5;
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
-  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)B), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(d + args_off));
+  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)NP), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(d + args_off));
   VO_HIP_CHECK(hipGetLastError());
-  VO_CHECK(vo::stream_sync(st, what));  // `up` is reused by the calling thread's next call
+  // `up` is reused by the calling thread's next call; a caller that owns the buffers synchronises before it comes back
+  // here (the one synchronisation up front), so its call stays asynchronous from this point on
+  if (!own) VO_CHECK(vo::stream_sync(st, what));
   return VO_OK;
 }
 

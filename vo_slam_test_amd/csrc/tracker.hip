@@ -328,6 +328,8 @@ struct vo_tracker {
   // trackRefKeyFrame's reference key-frame per frame of the batch (host copies: the common-node walk is host work)
   const vo_vocab *ref_vocab = nullptr;
   std::vector<RefKfHost> ref_kf;
+  // the relocalisation route (reloc.hip); NULL: not configured (vo_tracker_config.max_reloc_candidates == 0)
+  vo::Reloc *reloc = nullptr;
   // timing
   bool timing = false;
   // 2 events per stage and timed call, in a list that grows with the calls; they are read (after one synchronisation) only
@@ -468,7 +470,7 @@ int solve_pose(vo_tracker *t) {
 
 // What a call runs: the front (extraction + Frame::Frame), one of the two first stages -- trackWithMotion's projection
 // search (with its 2 x radius retry) or trackRefKeyFrame's vocabulary-node search --, and the local-map stage.
-enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u };
+enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u, kRunReloc = 16u };
 
 int stage_front(vo_tracker *t, const uint8_t *dev_images, int img_pitch, size_t img_frame_stride, const void *dev_depth,
                 int depth_kind, size_t depth_frame_stride, int depth_pitch, const void *host_depth) {
@@ -654,6 +656,24 @@ int stage_local(vo_tracker *t, const vo_tracker_params &P) {
   return VO_OK;
 }
 
+// VisualOdometry::relocalization() (:313-395) on the frames the front has built: reloc.hip works on the tracker's
+// per-feature frame state and pose-solver buffers
+int stage_reloc(vo_tracker *t) {
+  const vo_tracker_config &c = t->cfg;
+  vo::RelocShared S{};
+  S.frames = t->frames, S.B = t->B, S.cap = t->cap, S.n_levels = t->n_levels, S.width = c.width, S.height = c.height, S.sf = t->sf;
+  for (int i = 0; i < 5; i++) S.cam5[i] = c.intrinsics[i];
+  S.cam5d = t->Tcw.as<double>() + (size_t)t->B * 12;
+  S.pose = t->pose.as<double>(), S.fpoint = t->fpoint.as<double>(), S.fhas = t->fhas.as<uint8_t>(), S.foutl = t->foutl.as<uint8_t>();
+  S.pts = t->pts.as<double>(), S.obs = t->obs.as<double>(), S.isg = t->isg.as<double>(), S.ranges = t->ranges.as<int>();
+  S.index = t->index.as<int>(), S.outlier = t->outlier.as<uint8_t>(), S.ninl = t->ninl.as<int>(), S.assigned = t->assigned.as<int>();
+  S.nm = t->nm.as<int>();
+  VO_CHECK(t->resblk.reserve((size_t)t->B * 72 + 64));
+  S.resblk = t->resblk.as<uint8_t>(), S.orb_err = vo::orb_error_flag(t->orb), S.guided_err = vo::guided_error_flag(t->frames);
+  S.st = t->st;
+  return vo::reloc_run(t->reloc, S);
+}
+
 int run_pipeline(vo_tracker *t, const uint8_t *dev_images, int img_pitch, size_t img_frame_stride, const void *dev_depth,
                  int depth_kind, size_t depth_frame_stride, int depth_pitch, const vo_tracker_params *prm, unsigned run) {
   // (the host depth image of THIS call, if any: taken off the handle before anything can fail, so that a call that ends early never
@@ -673,6 +693,7 @@ int run_pipeline(vo_tracker *t, const uint8_t *dev_images, int img_pitch, size_t
   }
   if (run & kRunFront)
     VO_CHECK(stage_front(t, dev_images, img_pitch, img_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch, host_depth));
+  if (run & kRunReloc) return stage_reloc(t);
   const size_t capB = (size_t)B * t->cap;
   if ((run & kRunMotion) && t->nq_last == 0) {
     // no last frame (the first frame of a sequence, visualOdometry.cpp:170-214): Frame construction only; the pose is
@@ -770,6 +791,11 @@ int vo_tracker_create(vo_tracker **out, const vo_tracker_config *cfg) {
                                  (float)cfg->height)) != VO_OK)
     return fail(rc);
   if ((rc = alloc_all(t)) != VO_OK) return fail(rc);
+  if (cfg->max_reloc_candidates > 0 || cfg->max_reloc_features > 0) {
+    if (cfg->max_reloc_candidates < 1 || cfg->max_reloc_candidates > 256 || cfg->max_reloc_features < 1) return fail(VO_ERR_INVALID);
+    if ((rc = vo::reloc_create(&t->reloc, t->B, t->cap, cfg->max_reloc_candidates, cfg->max_reloc_features, t->sf, t->n_levels)) != VO_OK)
+      return fail(rc);
+  }
   // the intrinsics as doubles behind the Tcw block (the pose solver reads them from device memory)
   {
     double cam5d[5];
@@ -791,6 +817,7 @@ void vo_tracker_destroy(vo_tracker *t) {
   if (t->ev_extract) (void)hipEventDestroy(t->ev_extract);
   if (t->ev_build) (void)hipEventDestroy(t->ev_build);
   if (t->ev_depth) (void)hipEventDestroy(t->ev_depth);
+  if (t->reloc) vo::reloc_destroy(t->reloc);
   if (t->frames) vo_frames_destroy(t->frames);
   if (t->orb) vo_orb_destroy(t->orb);
   for (DevBuf *b : {&t->kps, &t->desc, &t->cnt, &t->images, &t->depth, &t->q0_flags, &t->q0_u, &t->q0_v, &t->q0_aux, &t->q0_level,
@@ -994,6 +1021,36 @@ int vo_tracker_set_ref_keyframe(vo_tracker *t, const vo_vocab *vocab, int n, con
   return VO_OK;
 }
 
+static int reloc_ready(vo_tracker *t) {
+  if (!t) return VO_ERR_INVALID;
+  if (!t->reloc) {
+    vo::set_error("vo_tracker: the relocalisation route is not configured (vo_tracker_config.max_reloc_candidates / _features)");
+    return VO_ERR_INVALID;
+  }
+  return VO_OK;
+}
+
+int vo_tracker_set_reloc_candidates(vo_tracker *t, const vo_vocab *vocab, int max_cand, const int32_t *n_cand,
+                                    const vo_reloc_candidate *cands) {
+  VO_CHECK(reloc_ready(t));
+  return vo::reloc_set_candidates(t->reloc, vocab, max_cand, n_cand, cands, t->st);
+}
+
+int vo_tracker_relocalize(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind, const vo_tracker_params *params) {
+  VO_CHECK(reloc_ready(t));
+  return track_host(t, images, depth, depth_kind, params, kRunFront | kRunReloc);
+}
+
+int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
+                              const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
+                              const vo_tracker_params *params) {
+  VO_CHECK(reloc_ready(t));
+  if (!dev_images || image_pitch < t->cfg.width || depth_kind < 0 || depth_kind > 2 || (depth_kind && !dev_depth))
+    return VO_ERR_INVALID;
+  return run_pipeline(t, dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch,
+                      params, kRunFront | kRunReloc);
+}
+
 int vo_tracker_track(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind, const vo_tracker_params *params) {
   return track_host(t, images, depth, depth_kind, params, kRunFront | kRunMotion | kRunLocal);
 }
@@ -1032,6 +1089,18 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
   const size_t B = t->B, cap = t->cap;
   const DevBuf *b = nullptr;
   size_t bytes = 0;
+  if (what >= VO_TRACKER_RELOC_WINNER && what <= VO_TRACKER_RELOC_PNP_MASK) {
+    VO_CHECK(reloc_ready(t));
+    const void *src = vo::reloc_selector(t->reloc, what, &bytes);
+    if (!src) return VO_ERR_INVALID;
+    if (dst_bytes < bytes) {
+      vo::set_error("vo_tracker_get(%d): destination holds %zu bytes, %zu needed", what, dst_bytes, bytes);
+      return VO_ERR_CAPACITY;
+    }
+    VO_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, t->st));
+    VO_HIP_CHECK(hipStreamSynchronize(t->st));
+    return VO_OK;
+  }
   switch (what) {
     case VO_TRACKER_ASSIGNED_LAST: b = &t->assigned_first, bytes = B * cap * 4; break;
     case VO_TRACKER_ASSIGNED_LOCAL: b = &t->assigned, bytes = B * cap * 4; break;

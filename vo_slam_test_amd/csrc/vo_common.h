@@ -151,8 +151,17 @@ struct RefKeyFrame {
   const float *angle;    // [n]
   const vo_bow_view *nodes;
 };
+// `per` key-frames per frame (relocalisation candidates): kfs [B * per], pair p = f * per + c searches slot slot0 + f and
+// owns dev_assigned [p][cap], dev_n_matches [p]; a pair with n == 0 matches nothing.  With `own` the call works in the
+// caller's buffers instead of the calling thread's and does NOT synchronise at its end: the caller must not call again
+// before the stream has drained (the synchronisation up front does that for calls on the same stream).
+struct BowResidentBufs {
+  DevBuf w, wt, node, img;
+  PinnedBuf stage, up;
+};
 int bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int B, const RefKeyFrame *kfs, float ratio, int check_rot,
-                        int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st);
+                        int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st, int per = 1,
+                        BowResidentBufs *own = nullptr);
 // vo_vocab_train's use of the tree it has built (match.hip): k_bow_transform over resident descriptors (4-byte aligned) into
 // resident outputs, enqueued on st; the node weights replaced (synchronises st)
 int vocab_transform_resident(const vo_vocab *v, int n, const uint32_t *dev_desc, int levelsup, int *dev_word, double *dev_weight,
@@ -164,8 +173,40 @@ struct FrameStoreView {
   const uint8_t *desc;  // [slots][cap][32]
   const float *angle;   // [slots][cap]
   const int *n;         // [slots]
+  const float *x = nullptr, *y = nullptr, *uright = nullptr;  // [slots][cap]
+  const int *octave = nullptr;
 };
 FrameStoreView frame_store_view(const vo_frames *h);
+
+// The relocalisation route of the tracker (reloc.hip): VisualOdometry::relocalization() (visualOdometry.cpp:313-395) for
+// the frames resident in the tracker's frame store.  The tracker owns the per-feature frame state and the pose solver's
+// buffers (RelocShared); the candidates, the PnP problems and the per-frame walk state live in the Reloc object.
+struct Reloc;
+struct RelocShared {
+  vo_frames *frames;
+  const vo_vocab *vocab;
+  int B, cap, n_levels, width, height;
+  const float *sf;      // host, n_levels
+  float cam5[5];
+  const double *cam5d;  // device
+  double *pose;         // [B][6]
+  double *fpoint;       // [B][cap][3]
+  uint8_t *fhas, *foutl;
+  double *pts, *obs, *isg;
+  int *ranges, *index;
+  uint8_t *outlier;
+  int *ninl, *assigned, *nm;
+  uint8_t *resblk;
+  const int *orb_err, *guided_err;
+  hipStream_t st;
+};
+int reloc_create(Reloc **out, int B, int cap, int max_cand, int max_feat, const float *sf, int n_levels);
+void reloc_destroy(Reloc *r);
+int reloc_set_candidates(Reloc *r, const vo_vocab *vocab, int max_cand, const int32_t *n_cand, const vo_reloc_candidate *cands,
+                         hipStream_t st);
+int reloc_run(Reloc *r, const RelocShared &S);
+// device array behind a VO_TRACKER_RELOC_* selector (nullptr: not one of them)
+const void *reloc_selector(const Reloc *r, int what, size_t *bytes);
 
 // vo_set_option's process-wide values as last set, 0 before (vo_common.hip): VO_OPT_BA_GRAPH (ba.hip), VO_OPT_POSE_BLOCK
 // (pose_only.hip), VO_OPT_BA_PAIRS_KERNEL (ba.hip), VO_OPT_HAMMING_KERNEL (match.hip: 0 = matrix-core form, 1 = VALU form)

@@ -161,31 +161,7 @@ int vo_se3_exp(const double xi[6], double R[9], double t[3]) {
 
 int vo_se3_log(const double R[9], const double t[3], double xi[6]) {
   if (!xi || !R || !t) return VO_ERR_INVALID;
-  // rotation matrix -> unit quaternion (Eigen's Quaternion(Matrix3) branch structure)
-  Se3 T;
-  const double tr = R[0] + R[4] + R[8];
-  if (tr > 0) {
-    double s = sqrt(tr + 1.0);
-    T.q[0] = 0.5 * s;
-    s = 0.5 / s;
-    T.q[1] = (R[7] - R[5]) * s, T.q[2] = (R[2] - R[6]) * s, T.q[3] = (R[3] - R[1]) * s;
-  } else {
-    int i = 0;
-    if (R[4] > R[0]) i = 1;
-    if (R[8] > R[i * 4]) i = 2;
-    const int j = (i + 1) % 3, k = (j + 1) % 3;
-    double s = sqrt(R[i * 4] - R[j * 4] - R[k * 4] + 1.0);
-    double q[4];
-    q[1 + i] = 0.5 * s;
-    s = 0.5 / s;
-    q[0] = (R[k * 3 + j] - R[j * 3 + k]) * s;
-    q[1 + j] = (R[j * 3 + i] + R[i * 3 + j]) * s;
-    q[1 + k] = (R[k * 3 + i] + R[i * 3 + k]) * s;
-    for (int a = 0; a < 4; a++) T.q[a] = q[a];
-  }
-  quat_normalize(T.q);
-  T.t[0] = t[0], T.t[1] = t[1], T.t[2] = t[2];
-  se3_log(T, xi);
+  se3_log_from_R(R, t, xi);  // (ba_math.h: shared with the device)
   return VO_OK;
 }
 
