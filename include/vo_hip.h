@@ -369,8 +369,8 @@ int vo_match_fuse(const vo_frame_view *kf, int nq, const uint8_t *q_flags, const
  * word_id[i] >= 0 marks a leaf (a word) with weight node_weight[i], node_desc holds one 32-byte ORB
  * descriptor per node.  Per feature: the word, its weight, and the node reached at level
  * depth_L - levelsup (the key of the FeatureVector that searchByBoW / searchForTriangulation walk).
- * The (word -> summed weight) map, its L1 normalisation and the (node -> feature list) map stay in
- * the shim: they are std::map insertions. */
+ * The (word -> summed weight) map and its L1 normalisation are vo_bow_vector below (or std::map insertions
+ * in the shim); the (node -> feature list) map stays in the shim. */
 typedef struct vo_vocab vo_vocab;
 int vo_vocab_create(vo_vocab **out, int n_nodes, int depth_L, const int32_t *child_start, const int32_t *children,
                     const uint8_t *node_desc, const double *node_weight, const int32_t *word_id);
@@ -418,6 +418,76 @@ int vo_vocab_save(const vo_vocab *v, int k, const char *path);
  * launch for all candidates of detectLoopCandidates / detectRelocalizationCandidates (:210-333). */
 int vo_bow_score(int n_query, const int32_t *query_words, const double *query_values, int n_candidates,
                  const int32_t *cand_start, const int32_t *cand_words, const double *cand_values, double *scores);
+
+/* The BoW vector of DBoW3::Vocabulary::transform for a ragged batch of frames: frame f owns the per-feature (word, weight)
+ * pairs feat_start[f] .. feat_start[f+1] as vo_bow_transform writes them.  Features with weight <= 0 are skipped, the
+ * weights of one word are added in FP64 in feature order, the L1 norm is the FP64 sum of fabs(value) in ascending word
+ * order and every value is divided by it when it is > 0: bitwise what BowVector::addWeight / normalize(L1) give.  Output
+ * as CSR: out_start[n_frames + 1], ascending distinct words and their values (room for as many entries as features).
+ * The _dev form takes device arrays and enqueues three launches on hip_stream.  Its intermediate result lives in scratch of
+ * the calling host thread that only grows: a call that needs more than any earlier call of the thread reallocates it
+ * (hipFree: a device synchronisation, once per size), every other call synchronises nothing.  Because the scratch is per
+ * thread and not per stream, one host thread must keep its calls on ONE stream (or drain the previous stream first): a second
+ * call on another stream would overwrite what the first call's kernels still read. */
+int vo_bow_vector(int n_frames, const int32_t *feat_start, const int32_t *word, const double *weight, int32_t *out_start,
+                  int32_t *out_words, double *out_values);
+int vo_bow_vector_dev(int n_frames, int n_features, const int32_t *dev_feat_start, const int32_t *dev_word, const double *dev_weight,
+                      int32_t *dev_out_start, int32_t *dev_out_words, double *dev_out_values, void *hip_stream);
+
+/* The key-frame database: Map::insertKeyFrame's inverted index (map.cpp:9-22),
+ * Map::detectRelocalizationCandidates (:101-208) and Map::detectLoopCandidates (:210-333) with the minScore loop of
+ * LoopClosing::detectLoop (loopClosing.cpp:71-83), resident on the device and answered for a batch of queries at once.
+ * A key-frame is known by its insertion number 0, 1, 2 ...; there is no erase (Map::eraseKeyFrame edits a copy of the
+ * posting list and removes nothing) and isBad() is never consulted.  The handle owns every device buffer: all of them are
+ * sized at creation from (n_words, max_keyframes, max_words_per_keyframe, max_batch), only the staging of the host forms
+ * grows with their arguments.  Exceeding max_keyframes, max_words_per_keyframe, max_batch or max_out is VO_ERR_CAPACITY.
+ * Calls on one handle are serialised by the caller (the reference holds mutexMap_); different handles are independent.
+ * Work is enqueued on the handle's stream (NULL, the legacy stream, until vo_kfdb_set_stream).
+ *
+ * insert: the key-frame's BoW vector (vo_bow_vector's output: word ids strictly ascending, checked by the host form).
+ * set_neighbors: KeyFrame::getBestCovisibleKFs(10) of an inserted key-frame, in its order (n <= 10, ids already inserted).
+ *
+ * Queries: query i owns q_words / q_values [q_start[i], q_start[i+1]) (a BoW vector).  n_cand[i] is the true number of
+ * candidates, cand [n_queries][max_out] holds the first min(n_cand[i], max_out) of them in the reference's order; the host
+ * forms return VO_ERR_CAPACITY when a query has more than max_out (n_cand is still written), the _dev forms leave that
+ * comparison to the caller.  score_out [n_queries][size] (or NULL): relocalisation -- the value relocateScore_ holds after
+ * query i alone: its Map::score as float where the key-frame was scored, stale_score (NULL = 0.0f) elsewhere; loop -- the
+ * loopScore_ written by query i, -1.0f where the key-frame was not scored.  stale_score [size]: relocateScore_ as earlier
+ * queries left it, which the reference adds for a neighbour that shares a word but was not scored; results are a pure
+ * function of (database, query, stale_score) and do not depend on the batch.
+ * Loop query: excl = getConnectKFs() and the key-frame itself (CSR over queries); min_score [n_queries], or NULL: computed
+ * as detectLoop does, the float minimum (from 1.0f) of Map::score against conn = the non-bad orderedConnectKFs_ (CSR).
+ * The _dev forms take device arrays, allocate nothing and do not synchronise: one launch, preceded by the four launches
+ * that rebuild the index when key-frames were inserted since the previous query.  They cannot validate what they do not
+ * read: the caller guarantees word ids within [0, n_words), excl / conn ids within [0, size) and at most max_keyframes conn
+ * entries per query (the kernels skip anything else, so memory stays safe, but the skip is not reported), and
+ * vo_kfdb_insert_dev trusts its words to ascend strictly within [0, n_words) (scores of a key-frame that breaks this are
+ * undefined).  The host forms check all of it and return VO_ERR_INVALID. */
+typedef struct vo_kfdb vo_kfdb;
+int vo_kfdb_create(vo_kfdb **out, int n_words, int max_keyframes, int max_words_per_keyframe, int max_batch);
+void vo_kfdb_destroy(vo_kfdb *db);
+int vo_kfdb_set_stream(vo_kfdb *db, void *hip_stream);
+int vo_kfdb_size(const vo_kfdb *db);
+/* VO_KFDB_OPT_LDS_KEYFRAMES: the largest database whose per-query counters are kept in LDS (default and maximum 16384);
+ * larger ones use a slab in device memory, with the same results. */
+#define VO_KFDB_OPT_LDS_KEYFRAMES 1
+int vo_kfdb_set_option(vo_kfdb *db, int option, int value);
+int vo_kfdb_insert(vo_kfdb *db, int n, const int32_t *words, const double *values, int32_t *index);
+int vo_kfdb_insert_dev(vo_kfdb *db, int n, const int32_t *dev_words, const double *dev_values, int32_t *index);
+int vo_kfdb_set_neighbors(vo_kfdb *db, int keyframe, int n, const int32_t *ids);
+/* set_neighbors for the key-frames first .. first + count - 1 in one call (two copies, no launch per key-frame):
+ * n[count] list lengths (<= 10), ids [count][10] (entries beyond n[k] are ignored). */
+int vo_kfdb_set_neighbors_batch(vo_kfdb *db, int first, int count, const int32_t *n, const int32_t *ids);
+int vo_kfdb_query_reloc(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
+                        const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand, float *score_out);
+int vo_kfdb_query_reloc_dev(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
+                            const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand, float *score_out);
+int vo_kfdb_query_loop(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
+                       const int32_t *excl_start, const int32_t *excl, const float *min_score, const int32_t *conn_start,
+                       const int32_t *conn, int max_out, int32_t *n_cand, int32_t *cand, float *score_out);
+int vo_kfdb_query_loop_dev(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
+                           const int32_t *excl_start, const int32_t *excl, const float *min_score, const int32_t *conn_start,
+                           const int32_t *conn, int max_out, int32_t *n_cand, int32_t *cand, float *score_out);
 
 /* cv::solvePnPRansac(pts3d, pts2d, K, noArray(), rvec, tvec, false, iterations, reproj_error, confidence, inliers,
  * SOLVEPNP_EPNP) as VisualOdometry::poseEstimateByPnP calls it (visualOdometry.cpp:778-830: 100, 8.0, 0.99), for a ragged

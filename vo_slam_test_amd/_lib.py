@@ -57,6 +57,9 @@ SYMBOLS = [
     "vo_match_triangulation", "vo_match_bow_batch", "vo_match_triangulation_batch", "vo_match_fuse", "vo_match_area_best", "vo_match_sim3_projection",
     "vo_match_sim3_mutual", "vo_vocab_create", "vo_vocab_destroy", "vo_bow_transform",
     "vo_vocab_train", "vo_vocab_train_dev", "vo_vocab_tree", "vo_vocab_save",
+    "vo_bow_vector", "vo_bow_vector_dev", "vo_kfdb_create", "vo_kfdb_destroy", "vo_kfdb_set_stream", "vo_kfdb_size", "vo_kfdb_set_option",
+    "vo_kfdb_insert", "vo_kfdb_insert_dev", "vo_kfdb_set_neighbors", "vo_kfdb_set_neighbors_batch", "vo_kfdb_query_reloc", "vo_kfdb_query_reloc_dev",
+    "vo_kfdb_query_loop", "vo_kfdb_query_loop_dev",
     "vo_pose_only_solve", "vo_sim3_solve", "vo_pose_graph_solve", "vo_sim3_reanchor_points", "vo_chol_solve", "vo_chol_solve_split", "vo_pose_only_solve_dev",
     "vo_ba_create", "vo_ba_reset", "vo_ba_destroy", "vo_ba_set_stream", "vo_ba_set_shard", "vo_ba_set_option", "vo_set_option", "vo_ba_set_allreduce", "vo_ba_set_state",
     "vo_ba_get_state", "vo_ba_n_free_cams", "vo_ba_local_ba", "vo_ba_local_ba_enqueue",
@@ -102,6 +105,8 @@ def lib():
         L.vo_ba_destroy.restype = None
     if hasattr(L, "vo_vocab_destroy"):
         L.vo_vocab_destroy.restype = None
+    if hasattr(L, "vo_kfdb_destroy"):
+        L.vo_kfdb_destroy.restype = None
     if hasattr(L, "vo_tracker_destroy"):
         L.vo_tracker_destroy.restype = None
         L.vo_tracker_extractor.restype = C.c_void_p
@@ -1298,6 +1303,127 @@ def bow_score(query_words, query_values, cand_words_list, cand_values_list):
     out = np.zeros(max(len(cand_words_list), 1))
     check(lib().vo_bow_score(len(qw), _p(qw), _p(qv), len(cand_words_list), _p(start), _p(cw), _p(cv), _p(out)), "vo_bow_score")
     return out[:len(cand_words_list)]
+
+
+def _csr(lists, dtype):
+    start = np.zeros(len(lists) + 1, np.int32)
+    for i, w in enumerate(lists):
+        start[i + 1] = start[i] + len(w)
+    flat = np.ascontiguousarray(np.concatenate([np.asarray(w, dtype) for w in lists]) if start[-1] else np.zeros(0, dtype), dtype)
+    return start, flat
+
+
+def bow_vector(words_list, weights_list):
+    """vo_bow_vector: per-feature (word, weight) of each frame (vo_bow_transform's output) -> list of (words, values), the
+    L1-normalised DBoW3::BowVector of every frame (ascending distinct words)."""
+    start, w = _csr(words_list, np.int32)
+    _, wt = _csr(weights_list, np.float64)
+    nf, n = len(words_list), int(start[-1])
+    os_, ow, ov = np.zeros(nf + 1, np.int32), np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.float64)
+    check(lib().vo_bow_vector(nf, _p(start), _p(w), _p(wt), _p(os_), _p(ow), _p(ov)), "vo_bow_vector")
+    return [(ow[os_[f]:os_[f + 1]].copy(), ov[os_[f]:os_[f + 1]].copy()) for f in range(nf)]
+
+
+def bow_vector_dev(n_frames, n_features, feat_start, word, weight, out_start, out_words, out_values, stream=0):
+    """vo_bow_vector_dev on device tensors (int32 / float64; outputs sized n_frames + 1 and n_features)"""
+    check(lib().vo_bow_vector_dev(int(n_frames), int(n_features), _p(feat_start), _p(word), _p(weight), _p(out_start), _p(out_words),
+                                  _p(out_values), _p(stream)), "vo_bow_vector_dev")
+
+
+class KeyFrameDatabase:
+    """vo_kfdb: the inverted index of Map::insertKeyFrame with Map::detectRelocalizationCandidates / detectLoopCandidates
+    for a batch of queries.  Key-frames are known by their insertion number."""
+
+    OPT_LDS_KEYFRAMES = 1
+
+    def __init__(self, n_words, max_keyframes, max_words_per_keyframe, max_batch, stream=None):
+        self._h = C.c_void_p()
+        check(lib().vo_kfdb_create(C.byref(self._h), int(n_words), int(max_keyframes), int(max_words_per_keyframe), int(max_batch)),
+              "vo_kfdb_create")
+        if stream is not None:
+            check(lib().vo_kfdb_set_stream(self._h, _p(stream)), "vo_kfdb_set_stream")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            _lib.vo_kfdb_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __len__(self):
+        return int(lib().vo_kfdb_size(self._h))
+
+    def set_option(self, option, value):
+        check(lib().vo_kfdb_set_option(self._h, int(option), int(value)), "vo_kfdb_set_option")
+
+    def insert(self, words, values):
+        """numpy arrays (vo_kfdb_insert) or device tensors (vo_kfdb_insert_dev) -> insertion number"""
+        idx = C.c_int32(-1)
+        if hasattr(words, "data_ptr"):
+            check(lib().vo_kfdb_insert_dev(self._h, int(words.numel()), _p(words), _p(values), C.byref(idx)), "vo_kfdb_insert_dev")
+        else:
+            w, v = np.ascontiguousarray(words, np.int32), np.ascontiguousarray(values, np.float64)
+            check(lib().vo_kfdb_insert(self._h, len(w), _p(w), _p(v), C.byref(idx)), "vo_kfdb_insert")
+        return int(idx.value)
+
+    def set_neighbors(self, keyframe, ids):
+        ids = np.ascontiguousarray(ids, np.int32)
+        check(lib().vo_kfdb_set_neighbors(self._h, int(keyframe), len(ids), _p(ids)), "vo_kfdb_set_neighbors")
+
+    def set_neighbors_batch(self, first, lists):
+        """set_neighbors for the key-frames first, first + 1, ... in one call"""
+        n = np.array([len(x) for x in lists], np.int32)
+        ids = np.full((len(lists), 10), -1, np.int32)
+        for k, x in enumerate(lists):
+            if len(x) > 10:
+                raise VoError("at most 10 neighbours per key-frame")
+            ids[k, :len(x)] = x
+        check(lib().vo_kfdb_set_neighbors_batch(self._h, int(first), len(lists), _p(n), _p(ids)), "vo_kfdb_set_neighbors_batch")
+
+    def _unpack(self, rc, what, n_cand, cand, score, want_scores, max_out):
+        if rc == -4 and max_out >= 0:  # VO_ERR_CAPACITY: n_cand still holds the true counts
+            raise VoError(f"{what} failed with status {rc}: {lib().vo_last_error().decode()}", n_cand)
+        check(rc, what)
+        out = [cand[i, :n_cand[i]].copy() for i in range(len(n_cand))]
+        return (out, score) if want_scores else out
+
+    def query_reloc(self, queries, stale_score=None, max_out=64, scores=False):
+        """queries: list of (words, values) BoW vectors -> list of candidate arrays (insertion numbers, reference order)
+        [, score_out [nq, size] float32]"""
+        qs, qw = _csr([q[0] for q in queries], np.int32)
+        _, qv = _csr([q[1] for q in queries], np.float64)
+        nq, size = len(queries), len(self)
+        st = None if stale_score is None else np.ascontiguousarray(stale_score, np.float32)
+        assert st is None or len(st) == size
+        n_cand, cand = np.zeros(max(nq, 1), np.int32), np.zeros((max(nq, 1), max(max_out, 1)), np.int32)
+        so = np.zeros((nq, size), np.float32) if scores else None
+        rc = lib().vo_kfdb_query_reloc(self._h, nq, _p(qs), _p(qw), _p(qv), _p(st), int(max_out), _p(n_cand), _p(cand), _p(so))
+        return self._unpack(rc, "vo_kfdb_query_reloc", n_cand[:nq], cand, so, scores, max_out)
+
+    def query_loop(self, queries, excluded, min_score=None, connected=None, max_out=64, scores=False):
+        """excluded: per query, getConnectKFs() and the key-frame itself; min_score: per-query floats, or None with
+        connected = per query the non-bad orderedConnectKFs_ (the minimum is then computed as detectLoop does)"""
+        qs, qw = _csr([q[0] for q in queries], np.int32)
+        _, qv = _csr([q[1] for q in queries], np.float64)
+        nq, size = len(queries), len(self)
+        es, ex = _csr(excluded, np.int32)
+        ms = None if min_score is None else np.ascontiguousarray(min_score, np.float32)
+        cs, cn = (None, None) if connected is None else _csr(connected, np.int32)
+        n_cand, cand = np.zeros(max(nq, 1), np.int32), np.zeros((max(nq, 1), max(max_out, 1)), np.int32)
+        so = np.zeros((nq, size), np.float32) if scores else None
+        rc = lib().vo_kfdb_query_loop(self._h, nq, _p(qs), _p(qw), _p(qv), _p(es), _p(ex), _p(ms), _p(cs), _p(cn), int(max_out),
+                                      _p(n_cand), _p(cand), _p(so))
+        return self._unpack(rc, "vo_kfdb_query_loop", n_cand[:nq], cand, so, scores, max_out)
+
+    def query_reloc_dev(self, nq, q_start, q_words, q_values, stale_score, max_out, n_cand, cand, score_out=None):
+        check(lib().vo_kfdb_query_reloc_dev(self._h, int(nq), _p(q_start), _p(q_words), _p(q_values), _p(stale_score), int(max_out),
+                                            _p(n_cand), _p(cand), _p(score_out)), "vo_kfdb_query_reloc_dev")
+
+    def query_loop_dev(self, nq, q_start, q_words, q_values, excl_start, excl, min_score, conn_start, conn, max_out, n_cand, cand,
+                       score_out=None):
+        check(lib().vo_kfdb_query_loop_dev(self._h, int(nq), _p(q_start), _p(q_words), _p(q_values), _p(excl_start), _p(excl),
+                                           _p(min_score), _p(conn_start), _p(conn), int(max_out), _p(n_cand), _p(cand), _p(score_out)),
+              "vo_kfdb_query_loop_dev")
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -34,6 +34,7 @@ SOURCES = [
     ("loop.hip", ["-ffp-contract=off"]),
     ("pnp.hip", ["-ffp-contract=off"]),
     ("vocab_train.hip", ["-ffp-contract=off"]),
+    ("kfdb.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]
