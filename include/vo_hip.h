@@ -704,7 +704,9 @@ int vo_track_scatter_gather_dev(vo_frames *h, int slot0, int n_frames, const int
  * :256-277).  Relocalisation (:313-395), the route of a LOST stream, is vo_tracker_relocalize below: the ordered walk
  * over the caller's candidate key-frames (searchByBoW, EPnP RANSAC, solvePoseOnlySE3, the two guided top-ups, the five
  * gates) runs on the device for the whole batch; Map::detectRelocalizationCandidates and the hand-over to trackLocalMap
- * after a success stay caller code.  Not covered: the map-side steps between the two stages:
+ * after a success stay caller code on that call.  vo_tracker_relocalize_db / vo_tracker_relocalize_store further below
+ * take the candidates from the device key-frame database (vo_kfdb) and read their features from a device store
+ * (vo_kfstore): detectRelocalizationCandidates and the walk in one asynchronous call.  Not covered: the map-side steps between the two stages:
  * trackLocalMap derives localKeyframes_ / localMappoints_ from frame_curr_->mappoints_ AFTER the first stage's culling
  * (updateLocalKeyFrames / updateLocalMapPoints, :286-291), whereas this call takes the local map BEFORE it starts.  A
  * caller that needs the reference's order runs the two stages as two calls: vo_tracker_track with an empty local map
@@ -818,7 +820,8 @@ int vo_tracker_track_ref_keyframe_dev(vo_tracker *t, const uint8_t *dev_images, 
  * asynchronous from there.  vo_tracker_results: pose, n_tracked = n_inliers = inliers_num_, status VO_TRACK_RELOC_FAILED
  * when no candidate (or none at all) reached 50; VO_TRACKER_FEATURE_HAS_POINT / _POINTS / _OUTLIER and the
  * VO_TRACKER_RELOC_* selectors describe the frame at the end.  Deviation: the P3P path of solvePnPRansac at exactly 4
- * correspondences (vo_pnp_ransac) cannot occur here (>= 15 matches). */
+ * correspondences (vo_pnp_ransac) cannot occur here (>= 15 matches).
+ * On vo_tracker_relocalize_store / vo_tracker_relocalize_db (below) the candidates come from a device store. */
 typedef struct {
   int32_t n;                 /* features of the key-frame */
   int32_t bad;               /* KeyFrame::isBad() */
@@ -838,10 +841,78 @@ int vo_tracker_relocalize(vo_tracker *t, const uint8_t *images, const void *dept
 int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
                               const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
                               const vo_tracker_params *params);
+
+/* The key-frame feature store: everything the relocalisation route reads of a key-frame, resident
+ * on the device, so that the route takes its candidates as key-frame numbers.  A key-frame is known by its insertion
+ * number 0, 1, 2 ... -- the numbering of vo_kfdb -- and is never erased.  Every device buffer is sized at creation from
+ * (max_keyframes, max_features); one more key-frame, or a key-frame with more features (or more FeatureVector entries)
+ * than that, is VO_ERR_CAPACITY and nothing is truncated.  Per key-frame: n, bad; per feature: angle, desc, flags (bit 0:
+ * the map point exists and is not bad), points, ids, point_desc, min / max distance; the FeatureVector (levelsup 3) as a
+ * CSR: node ids ascending, start, feat.  ids are global map-point ids: any non-negative int32 (the route maps them to
+ * dense ids per frame itself).  Calls on one handle are serialised by the caller; work is enqueued on the handle's stream
+ * (NULL, the legacy stream, until vo_kfstore_set_stream).  A tracker call that reads the store orders itself behind
+ * that stream with an event, and the store's later work behind the tracker's.
+ * insert: vo_reloc_candidate with the validation of vo_tracker_set_reloc_candidates except the id range (ids of flagged
+ * features must be >= 0); one staging copy, synchronises the stream once (the caller's arrays are free on return).
+ * insert_dev: the arrays in device memory [n], the FeatureVector as the per-feature node id that vo_bow_transform writes:
+ * the CSR is built on the device (node ascending, the features of a node in index order: Frame::computeBow's); no host
+ * synchronisation, nothing is validated beyond n.  The arrays must stay untouched until the stream has passed the call.
+ * set_bad: KeyFrame::isBad() from now on.  update_points: the map side of key-frame `keyframe` replaced (host arrays [n],
+ * n as inserted) -- after BA or culling; descriptors, angles and the FeatureVector never change.  Synchronises once. */
+typedef struct vo_kfstore vo_kfstore;
+int vo_kfstore_create(vo_kfstore **out, int max_keyframes, int max_features);
+void vo_kfstore_destroy(vo_kfstore *s);
+int vo_kfstore_set_stream(vo_kfstore *s, void *hip_stream);
+int vo_kfstore_size(const vo_kfstore *s);
+int vo_kfstore_insert(vo_kfstore *s, const vo_reloc_candidate *kf, int32_t *index);
+int vo_kfstore_insert_dev(vo_kfstore *s, int n, int bad, const float *dev_angle, const uint8_t *dev_desc,
+                          const int32_t *dev_node_of_feature, const uint8_t *dev_flags, const double *dev_points,
+                          const int32_t *dev_ids, const uint8_t *dev_point_desc, const float *dev_min_distance,
+                          const float *dev_max_distance, int32_t *index);
+int vo_kfstore_set_bad(vo_kfstore *s, int keyframe, int bad);
+int vo_kfstore_update_points(vo_kfstore *s, int keyframe, const uint8_t *flags, const double *points, const int32_t *ids,
+                             const uint8_t *point_desc, const float *min_distance, const float *max_distance);
+/* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
+ * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
+ * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors
+ * (k_featvec), the candidates' records gathered from the store, their global ids mapped to dense ids per frame, the
+ * common-node walk (k_bow_walk), k_node_replay and the rest of the route as vo_tracker_relocalize has it: all enqueued, no
+ * host synchronisation, no device-to-host copy, and no allocation after the first call (which sizes the route's buffers
+ * from the tracker's capacities).  The store's max_features must not exceed max_reloc_features (VO_ERR_CAPACITY at the
+ * call).  Results are bit-identical to vo_tracker_set_reloc_candidates + vo_tracker_relocalize on the same key-frames;
+ * VO_TRACKER_RELOC_POINT_IDS reports the store's global ids.  Conditions only the device sees are sticky and reported by
+ * vo_tracker_results: a frame with more candidates than max_reloc_candidates -> VO_ERR_CAPACITY (its first
+ * max_reloc_candidates are walked and every output is valid); a candidate outside [0, store size) -> VO_ERR_INVALID (that
+ * candidate is walked as a bad key-frame, outcome 0; every other output is valid).  The candidates handed to
+ * vo_tracker_set_reloc_candidates are gone after these calls (set them again before vo_tracker_relocalize).
+ * vo_tracker_relocalize_db: the same with Map::detectRelocalizationCandidates in front -- vo_bow_vector_dev on the
+ * transform's words and weights, the database query with max_out = max_reloc_candidates, on the tracker's stream;
+ * dev_stale_score [size] or NULL as in vo_kfdb_query_reloc_dev.  db and store must hold the same number of key-frames
+ * (VO_ERR_INVALID) and the database's max_batch must cover the batch (VO_ERR_CAPACITY), checked before anything is enqueued. */
+int vo_tracker_relocalize_store(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_n_cand,
+                                const int32_t *dev_cand, int cand_stride, const uint8_t *images, const void *depth,
+                                int depth_kind, const vo_tracker_params *params);
+int vo_tracker_relocalize_store_dev(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_n_cand,
+                                    const int32_t *dev_cand, int cand_stride, const uint8_t *dev_images, int image_pitch,
+                                    size_t image_frame_stride, const void *dev_depth, int depth_kind,
+                                    size_t depth_frame_stride, int depth_pitch, const vo_tracker_params *params);
+int vo_tracker_relocalize_db(vo_tracker *t, vo_kfdb *db, const vo_kfstore *store, const vo_vocab *vocab,
+                             const float *dev_stale_score, const uint8_t *images, const void *depth, int depth_kind,
+                             const vo_tracker_params *params);
+int vo_tracker_relocalize_db_dev(vo_tracker *t, vo_kfdb *db, const vo_kfstore *store, const vo_vocab *vocab,
+                                 const float *dev_stale_score, const uint8_t *dev_images, int image_pitch,
+                                 size_t image_frame_stride, const void *dev_depth, int depth_kind, size_t depth_frame_stride,
+                                 int depth_pitch, const vo_tracker_params *params);
+/* With vo_tracker_set_timing on, a store route records HIP events around its four new stages: 0 k_featvec, 1 the gather
+ * from the store, 2 the id compaction, 3 k_bow_walk.  Synchronises and returns the milliseconds of the LAST such call
+ * (VO_ERR_INVALID when none has run with timing on).  tools/reloc_db_bench.py. */
+#define VO_TRACKER_RELOC_STAGES 4
+int vo_tracker_get_reloc_timing(vo_tracker *t, double *ms /*VO_TRACKER_RELOC_STAGES*/);
 /* Waits for the batch and copies out (any pointer may be NULL): poses as se3 [batch][6] and as Tcw
  * [batch][12]; n_tracked = inliers of the second solve whose map point has observations (inliers_num_,
  * :289-300); n_inliers = the second solve's return value; the two searches' match counts; status bits.
- * Reports sticky stage errors (dropped key-points, exhausted candidate pools) as VO_ERR_CAPACITY. */
+ * Reports sticky stage errors (dropped key-points, exhausted candidate pools) as VO_ERR_CAPACITY, and the two sticky
+ * conditions of vo_tracker_relocalize_store / _db (above); the outputs are copied out before it reports. */
 int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_tracked, int32_t *n_inliers,
                        int32_t *n_matches_last, int32_t *n_matches_local, int32_t *status);
 /* intermediate state of the last batch (tests, shims): [batch][max_features] / [batch][max_local] arrays */
@@ -864,8 +935,11 @@ enum {
   VO_TRACKER_RELOC_PNP_INLIERS = 18, /* int32 [..][..]: poseEstimateByPnP's return value (0: not run) */
   VO_TRACKER_RELOC_OUTCOME = 19,     /* int32 [..][..]: 0 bad, 1 < 15 BoW matches, 2 < 10 PnP inliers, 3 < 10 solve inliers,
                                         4 below 50 at the end, 5 success, 6 not reached */
-  VO_TRACKER_RELOC_PNP_MASK = 20     /* uint8 [batch][max_reloc_candidates][max_features] (debug): per frame feature 0 = no
+  VO_TRACKER_RELOC_PNP_MASK = 20,    /* uint8 [batch][max_reloc_candidates][max_features] (debug): per frame feature 0 = no
                                         PnP correspondence, 1 = correspondence, RANSAC outlier, 2 = RANSAC inlier */
+  /* after vo_tracker_relocalize_store / _db */
+  VO_TRACKER_RELOC_CANDIDATES = 21,  /* int32 [batch][max_reloc_candidates]: the key-frame numbers walked, -1 beyond them */
+  VO_TRACKER_RELOC_N_CANDIDATES = 22 /* int32 [batch]: the frame's true candidate count (may exceed max_reloc_candidates) */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 int vo_tracker_sync(vo_tracker *t);

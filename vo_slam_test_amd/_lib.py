@@ -50,6 +50,9 @@ SYMBOLS = [
     "vo_tracker_track_first", "vo_tracker_track_first_dev", "vo_tracker_track_local_map", "vo_tracker_set_ref_keyframe",
     "vo_tracker_track_ref_keyframe", "vo_tracker_track_ref_keyframe_dev",
     "vo_tracker_set_reloc_candidates", "vo_tracker_relocalize", "vo_tracker_relocalize_dev",
+    "vo_kfstore_create", "vo_kfstore_destroy", "vo_kfstore_set_stream", "vo_kfstore_size", "vo_kfstore_insert", "vo_kfstore_insert_dev",
+    "vo_kfstore_set_bad", "vo_kfstore_update_points", "vo_tracker_relocalize_store", "vo_tracker_relocalize_store_dev",
+    "vo_tracker_relocalize_db", "vo_tracker_relocalize_db_dev", "vo_tracker_get_reloc_timing",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -107,6 +110,8 @@ def lib():
         L.vo_vocab_destroy.restype = None
     if hasattr(L, "vo_kfdb_destroy"):
         L.vo_kfdb_destroy.restype = None
+    if hasattr(L, "vo_kfstore_destroy"):
+        L.vo_kfstore_destroy.restype = None
     if hasattr(L, "vo_tracker_destroy"):
         L.vo_tracker_destroy.restype = None
         L.vo_tracker_extractor.restype = C.c_void_p
@@ -454,7 +459,9 @@ class Tracker:
     tensors (images, depth) or streams."""
     (ASSIGNED_LAST, ASSIGNED_LOCAL, POSE_FIRST, INLIERS_FIRST, OBSERVED_INLIERS_FIRST, FEATURE_HAS_POINT, FEATURE_POINTS,
      LOCAL_FLAGS, LOCAL_U, LOCAL_V, LOCAL_UR, LOCAL_LEVEL, LOCAL_VIEWCOS, KEYPOINT_COUNTS, FEATURE_OUTLIER,
-     RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK) = range(21)
+     RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK,
+     RELOC_CANDIDATES, RELOC_N_CANDIDATES) = range(23)
+    RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
     FEW_MATCHES, FEW_INLIERS, RELOC_FAILED = 1, 2, 4
 
@@ -630,6 +637,53 @@ class Tracker:
         check(lib().vo_tracker_relocalize_dev(self._h, _p(images), int(images.stride(1)), C.c_size_t(images.stride(0)), _p(depth),
                                               kind, C.c_size_t(fs), int(pitch), None), "vo_tracker_relocalize_dev")
 
+    @staticmethod
+    def _host_frames(images, depth):
+        img = np.ascontiguousarray(images, np.uint8)
+        kind, dp = 0, None
+        if depth is not None:
+            dp = np.ascontiguousarray(depth)
+            kind = 1 if dp.dtype == np.float32 else 2
+        return img, dp, kind
+
+    @staticmethod
+    def _dev_frames(images, depth):
+        kind, fs, pitch = 0, 0, 0
+        if depth is not None:
+            kind = 1 if depth.element_size() == 4 else 2
+            fs, pitch = depth.stride(0) * depth.element_size(), depth.stride(1) * depth.element_size()
+        return (_p(images), int(images.stride(1)), C.c_size_t(images.stride(0)), _p(depth), kind, C.c_size_t(fs), int(pitch))
+
+    def relocalize_store(self, store, vocab, n_cand, cand, images, depth=None):
+        """vo_tracker_relocalize_store[_dev]: n_cand [B] and cand [B, stride] int32 DEVICE tensors of key-frame numbers of
+        `store` in walk order (the output layout of KeyFrameDatabase.query_reloc_dev); images / depth host arrays or device
+        tensors.  Asynchronous; results() / get(RELOC_*) after."""
+        stride = int(cand.stride(0)) if cand.dim() > 1 else int(cand.numel() // max(self.B, 1))
+        head = (self._h, store._h, vocab._h, _p(n_cand), _p(cand), stride)
+        if hasattr(images, "data_ptr"):
+            check(lib().vo_tracker_relocalize_store_dev(*head, *self._dev_frames(images, depth), None), "vo_tracker_relocalize_store_dev")
+        else:
+            img, dp, kind = self._host_frames(images, depth)
+            check(lib().vo_tracker_relocalize_store(*head, _p(img), _p(dp), kind, None), "vo_tracker_relocalize_store")
+        self._reloc_keep = (store, vocab, n_cand, cand)  # the enqueued kernels read them
+
+    def relocalize_db(self, db, store, vocab, images, depth=None, stale_score=None):
+        """vo_tracker_relocalize_db[_dev]: Map::detectRelocalizationCandidates on `db` (a KeyFrameDatabase over the same
+        key-frames as `store`), then the walk; stale_score: float32 [size] device tensor or None"""
+        head = (self._h, db._h, store._h, vocab._h, _p(stale_score))
+        if hasattr(images, "data_ptr"):
+            check(lib().vo_tracker_relocalize_db_dev(*head, *self._dev_frames(images, depth), None), "vo_tracker_relocalize_db_dev")
+        else:
+            img, dp, kind = self._host_frames(images, depth)
+            check(lib().vo_tracker_relocalize_db(*head, _p(img), _p(dp), kind, None), "vo_tracker_relocalize_db")
+        self._reloc_keep = (db, store, vocab, stale_score)
+
+    def get_reloc_timing(self):
+        """milliseconds of the four new stages of the last store route run with set_timing(True)"""
+        ms = (C.c_double * len(self.RELOC_STAGES))()
+        check(lib().vo_tracker_get_reloc_timing(self._h, ms), "vo_tracker_get_reloc_timing")
+        return {k: ms[i] for i, k in enumerate(self.RELOC_STAGES)}
+
     def results(self):
         B = self.B
         out = dict(pose=np.zeros((B, 6)), Tcw=np.zeros((B, 12)), n_tracked=np.zeros(B, np.int32), n_inliers=np.zeros(B, np.int32),
@@ -652,7 +706,8 @@ class Tracker:
             self.FEATURE_OUTLIER: ((B, cap), np.uint8), self.RELOC_WINNER: ((B,), np.int32),
             self.RELOC_POINT_IDS: ((B, cap), np.int32), self.RELOC_BOW_MATCHES: ((B, mrc), np.int32),
             self.RELOC_PNP_INLIERS: ((B, mrc), np.int32), self.RELOC_OUTCOME: ((B, mrc), np.int32),
-            self.RELOC_PNP_MASK: ((B, mrc, cap), np.uint8)}[what]
+            self.RELOC_PNP_MASK: ((B, mrc, cap), np.uint8), self.RELOC_CANDIDATES: ((B, mrc), np.int32),
+            self.RELOC_N_CANDIDATES: ((B,), np.int32)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out
@@ -1424,6 +1479,63 @@ class KeyFrameDatabase:
         check(lib().vo_kfdb_query_loop_dev(self._h, int(nq), _p(q_start), _p(q_words), _p(q_values), _p(excl_start), _p(excl),
                                            _p(min_score), _p(conn_start), _p(conn), int(max_out), _p(n_cand), _p(cand), _p(score_out)),
               "vo_kfdb_query_loop_dev")
+
+
+class KeyFrameStore:
+    """vo_kfstore: the features of the key-frames the relocalisation route reads, resident on the device (DESIGN.md
+    section 4f).  Key-frames are known by their insertion number, the numbering of KeyFrameDatabase."""
+
+    def __init__(self, max_keyframes, max_features, stream=None):
+        self._h = C.c_void_p()
+        check(lib().vo_kfstore_create(C.byref(self._h), int(max_keyframes), int(max_features)), "vo_kfstore_create")
+        self.max_features = int(max_features)
+        if stream is not None:
+            check(lib().vo_kfstore_set_stream(self._h, _p(stream)), "vo_kfstore_set_stream")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value and _lib is not None:
+            _lib.vo_kfstore_destroy(self._h)
+            self._h = C.c_void_p()
+
+    __del__ = close
+
+    def __len__(self):
+        return int(lib().vo_kfstore_size(self._h))
+
+    def insert(self, k):
+        """k: the dict Tracker.set_reloc_candidates takes per candidate (numpy arrays) -> insertion number"""
+        a = dict(angle=np.ascontiguousarray(k["angle"], np.float32), desc=np.ascontiguousarray(k["desc"], np.uint8),
+                 flags=np.ascontiguousarray(k["flags"], np.uint8), points=np.ascontiguousarray(k["points"], np.float64),
+                 ids=np.ascontiguousarray(k["ids"], np.int32), point_desc=np.ascontiguousarray(k["point_desc"], np.uint8),
+                 min_distance=np.ascontiguousarray(k["min_dist"], np.float32), max_distance=np.ascontiguousarray(k["max_dist"], np.float32))
+        nodes = BowNodes(np.asarray(k["nodes"]))
+        rc = RelocCandidate()
+        rc.n, rc.bad = len(a["flags"]), int(bool(k.get("bad", False)))
+        for key, v in a.items():
+            setattr(rc, key, v.ctypes.data)
+        rc.nodes = C.addressof(nodes.view)
+        idx = C.c_int32(-1)
+        check(lib().vo_kfstore_insert(self._h, C.byref(rc), C.byref(idx)), "vo_kfstore_insert")
+        return int(idx.value)
+
+    def insert_dev(self, k):
+        """the same from device tensors (angle f32 [n], desc u8 [n, 32], nodes i32 [n] per-feature node ids, flags u8 [n],
+        points f64 [n, 3], ids i32 [n], point_desc u8 [n, 32], min_dist / max_dist f32 [n]); no synchronisation"""
+        idx = C.c_int32(-1)
+        check(lib().vo_kfstore_insert_dev(self._h, int(k["flags"].numel()), int(bool(k.get("bad", False))), _p(k["angle"]), _p(k["desc"]),
+                                          _p(k["nodes"]), _p(k["flags"]), _p(k["points"]), _p(k["ids"]), _p(k["point_desc"]),
+                                          _p(k["min_dist"]), _p(k["max_dist"]), C.byref(idx)), "vo_kfstore_insert_dev")
+        return int(idx.value)
+
+    def set_bad(self, keyframe, bad=True):
+        check(lib().vo_kfstore_set_bad(self._h, int(keyframe), int(bool(bad))), "vo_kfstore_set_bad")
+
+    def update_points(self, keyframe, flags, points, ids, point_desc, min_dist, max_dist):
+        """the map side of a key-frame replaced (numpy arrays [n], n as inserted)"""
+        a = lambda x, dt: np.ascontiguousarray(x, dt)
+        check(lib().vo_kfstore_update_points(self._h, int(keyframe), _p(a(flags, np.uint8)), _p(a(points, np.float64)), _p(a(ids, np.int32)),
+                                             _p(a(point_desc, np.uint8)), _p(a(min_dist, np.float32)), _p(a(max_dist, np.float32))),
+              "vo_kfstore_update_points")
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -35,6 +35,7 @@ SOURCES = [
     ("pnp.hip", ["-ffp-contract=off"]),
     ("vocab_train.hip", ["-ffp-contract=off"]),
     ("kfdb.hip", ["-ffp-contract=off"]),
+    ("kfstore.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

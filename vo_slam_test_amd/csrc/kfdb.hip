@@ -393,6 +393,7 @@ struct vo_kfdb {
   int lds_kf = kLdsKeyframes;
   bool lds_attr = false;
   hipStream_t st = nullptr;
+  hipEvent_t ev_in = nullptr, ev_out = nullptr;  // a query on a caller's stream (kfdb_query_reloc_on), created on first use
   // the database
   vo::DevBuf kf_start, kf_words, kf_vals, nbr_n, nbr, post_cnt, post_start, post_tmp, post_kf;
   // per-query work slabs [max_batch][max_kf]
@@ -575,6 +576,34 @@ int kfdb_query_host(vo_kfdb *db, bool loop, int nq, const int32_t *q_start, cons
 
 }  // namespace
 
+// ---- the relocalisation query on a caller's stream (the tracker's: reloc.hip)
+void vo::kfdb_info(const vo_kfdb *db, int *size, int *max_batch) {
+  if (size) *size = db->size;
+  if (max_batch) *max_batch = db->max_batch;
+}
+
+int vo::kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const int32_t *q_start, const int32_t *q_words,
+                            const double *q_values, const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand) {
+  if (!db) return VO_ERR_INVALID;
+  hipStream_t own = db->st;
+  if (own != st) {  // insertions enqueued on the database's stream come first; its later work waits for the query
+    if (!db->ev_in) VO_HIP_CHECK(hipEventCreateWithFlags(&db->ev_in, hipEventDisableTiming));
+    if (!db->ev_out) VO_HIP_CHECK(hipEventCreateWithFlags(&db->ev_out, hipEventDisableTiming));
+    VO_HIP_CHECK(hipEventRecord(db->ev_in, own));
+    VO_HIP_CHECK(hipStreamWaitEvent(st, db->ev_in, 0));
+  }
+  db->st = st;  // (the rebuild and the query launch read the handle's stream)
+  const int rc = kfdb_query_dev(db, false, n_queries, q_start, q_words, q_values, stale_score, nullptr, nullptr, nullptr, nullptr,
+                                nullptr, max_out, n_cand, cand, nullptr, "vo_tracker_relocalize_db");
+  db->st = own;
+  VO_CHECK(rc);
+  if (own != st) {
+    VO_HIP_CHECK(hipEventRecord(db->ev_out, st));
+    VO_HIP_CHECK(hipStreamWaitEvent(own, db->ev_out, 0));
+  }
+  return VO_OK;
+}
+
 extern "C" {
 
 int vo_bow_vector_dev(int n_frames, int n_features, const int32_t *dev_feat_start, const int32_t *dev_word, const double *dev_weight,
@@ -671,6 +700,8 @@ int vo_kfdb_create(vo_kfdb **out, int n_words, int max_keyframes, int max_words_
 void vo_kfdb_destroy(vo_kfdb *db) {
   if (!db) return;
   (void)hipStreamSynchronize(db->st);
+  if (db->ev_in) (void)hipEventDestroy(db->ev_in);
+  if (db->ev_out) (void)hipEventDestroy(db->ev_out);
   db->release();
   delete db;
 }

@@ -4,6 +4,7 @@
 // searchByProjection (:18-148, :274-353) is replayed on the host over the device-computed matrix
 // so that match pairs stay identical to the reference's visiting order.
 #include "vo_common.h"
+#include "block_sort.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1079,3 +1080,241 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
   return VO_OK;
 }
 
+
+// ---- searchByBoW against the key-frames of a device store: the common-node walk on the device ----
+namespace {
+
+// The FeatureVector of a frame from the per-feature node ids k_bow_transform writes: the distinct nodes ascending, bstart,
+// and bfeat = the feature indices stably ordered by node -- std::stable_sort by node on the host (bow_search_resident).
+// One workgroup per frame.  The keys (node << 32 | index) are distinct, so their sorted order is unique and equals the
+// stable order by node: nothing depends on which thread runs when.  The node heads are compacted in order by ballot.
+// LDS: 8 bytes per slot of the power of two above the frame's feature count (128 KiB at kNodeMaxB = 16384 slots).
+struct FeatVecArgs {
+  const int *n_dev;  // [frames] feature counts, or NULL: n_fixed
+  int n_fixed, cap;
+  const int *node;   // [frames][cap]
+  int *nn;           // [frames * nn_stride] number of distinct nodes
+  int nn_stride;
+  int *onode, *ostart, *ofeat;  // [frames][cap], [frames][cap + 1], [frames][cap]
+};
+__global__ __launch_bounds__(256) void k_featvec(FeatVecArgs A) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long fv_keys[];
+  __shared__ int wsum[4];
+  __shared__ int s_base;
+  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int n = min(max(A.n_dev ? A.n_dev[f] : A.n_fixed, 0), A.cap);
+  const int *node = A.node + (size_t)f * A.cap;
+  int *onode = A.onode + (size_t)f * A.cap, *ostart = A.ostart + (size_t)f * (A.cap + 1), *ofeat = A.ofeat + (size_t)f * A.cap;
+  const int np2 = vo::pow2_ceil(n);
+  for (int i = tid; i < np2; i += 256) fv_keys[i] = i < n ? ((unsigned long long)(unsigned)node[i] << 32) | (unsigned)i : ~0ull;
+  vo::block_bitonic_sort(fv_keys, np2);
+  if (tid == 0) s_base = 0;
+  __syncthreads();
+  for (int b = 0; b < n; b += 256) {
+    const int i = b + tid;
+    const bool in = i < n;
+    const unsigned long long key = in ? fv_keys[i] : 0ull;
+    const int nd = (int)(key >> 32);
+    const bool head = in && (i == 0 || (int)(fv_keys[i - 1] >> 32) != nd);
+    if (in) ofeat[i] = (int)(key & 0xffffffffu);
+    const unsigned long long mk = __builtin_amdgcn_ballot_w64(head);
+    const int within = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+    if (lane == 0) wsum[wave] = __popcll(mk);
+    __syncthreads();
+    int pos = s_base + within;
+    for (int w = 0; w < wave; w++) pos += wsum[w];
+    if (head) onode[pos] = nd, ostart[pos] = i;
+    __syncthreads();
+    if (tid == 0) s_base += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    __syncthreads();
+  }
+  if (tid == 0) ostart[s_base] = n, A.nn[(size_t)f * A.nn_stride] = s_base;
+}
+
+int launch_featvec(const FeatVecArgs &A, int frames, hipStream_t st) {
+  const size_t lds = (size_t)vo::pow2_ceil(std::max(A.cap, 1)) * 8;
+  if (lds > 64 * 1024) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_featvec, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 8));
+      attr_set = true;
+    }
+  }
+  hipLaunchKernelGGL(k_featvec, dim3((unsigned)frames), dim3(256), lds, st, A);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+// The walk over the nodes a (key-frame, frame) pair shares (matcher.cpp:465-545; for_common_nodes + the query loop of
+// bow_search_resident), one wavefront per pair.  The reference visits the key-frame's nodes ascending and a node's
+// features in FeatureVector order: that is the order of the key-frame's CSR entries t = 0, 1, 2 ..., so the wave takes
+// 64 consecutive entries at a time; a lane finds its entry's node (the last start <= t), looks the node up in the frame's
+// ascending node list, and the entries that survive (`node shared` and flags & 1) are appended in lane order: ballot +
+// prefix count.  The output is the host walk's query list, entry for entry.  A pair has at most NK queries (one per CSR
+// entry), so query list and claim scratch are fixed [pairs][NK] regions.
+struct BowWalkArgs {
+  int per, cap, NK, check_rot;
+  float ratio;
+  vo::KfStoreView S;
+  const int *pair_kf;  // [pairs] key-frame of the store or -1
+  const int *fn;       // frame store
+  const uint8_t *fdesc;
+  const float *fangle;
+  const int *fv_nn, *fv_node, *fv_start;
+  const uint32_t *fv_feat;
+  int4 *queries, *claims;
+  NodeArgs *args;
+  const uint8_t *ones;
+  int *match, *n_matches;
+};
+__global__ __launch_bounds__(64) void k_bow_walk(BowWalkArgs A) {
+  const int p = blockIdx.x, f = p / A.per, lane = threadIdx.x;
+  const int nB = min(max(A.fn[f], 0), A.cap);
+  const int k = A.pair_kf[p];
+  int4 *Q = A.queries + (size_t)p * A.NK;
+  int nq = 0, nA = 0;
+  const bool have = k >= 0 && k < A.S.size;
+  if (have) {
+    const int *head = vo::kf_head(A.S, k);
+    const int n = min(max(head[0], 0), A.NK), bad = head[1], nnA = min(max(head[2], 0), A.NK);
+    nA = bad ? 0 : n;
+    if (!bad && n > 0 && nB > 0 && nnA > 0) {
+      const int *nodeA = vo::kf_sec<int>(A.S, k, A.S.o_node), *startA = vo::kf_sec<int>(A.S, k, A.S.o_start);
+      const int *featA = vo::kf_sec<int>(A.S, k, A.S.o_feat);
+      const uint8_t *flagsA = vo::kf_sec<uint8_t>(A.S, k, A.S.o_flags);
+      const int nnB = min(max(A.fv_nn[f], 0), A.cap);
+      const int *nodeB = A.fv_node + (size_t)f * A.cap, *startB = A.fv_start + (size_t)f * (A.cap + 1);
+      const int total = min(max(startA[nnA], 0), A.NK);
+      for (int b = 0; b < total; b += 64) {
+        const int t = b + lane;
+        bool emit = false;
+        int4 q = make_int4(0, 0, 0, 0);
+        if (t < total) {
+          int lo = 0, hi = nnA;  // first node whose start is beyond t; the entry belongs to the node before it
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (startA[mid] <= t) lo = mid + 1;
+            else hi = mid;
+          }
+          const int nd = nodeA[max(lo - 1, 0)];
+          int l2 = 0, h2 = nnB;  // first frame node >= nd
+          while (l2 < h2) {
+            const int mid = (l2 + h2) >> 1;
+            if (nodeB[mid] < nd) l2 = mid + 1;
+            else h2 = mid;
+          }
+          if (l2 < nnB && nodeB[l2] == nd) {
+            const int i1 = featA[t];
+            if (i1 >= 0 && i1 < n && (flagsA[i1] & 1)) {  // `if (!mpk || mpk->isBad()) continue;` :475-477
+              emit = true;
+              q = make_int4(i1, startB[l2], startB[l2 + 1], 0);
+            }
+          }
+        }
+        const unsigned long long mk = __builtin_amdgcn_ballot_w64(emit);
+        const int within = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+        if (emit) Q[nq + within] = q;
+        nq += (int)__popcll(mk);
+      }
+    }
+  }
+  if (lane == 0) {
+    NodeArgs &P = A.args[p];
+    P.mode = kNodeBow0, P.nq = nq, P.nA = nA, P.nB = nB, P.check_rot = A.check_rot;
+    P.ratio = A.ratio, P.ex = 0.f, P.ey = 0.f;
+    for (int i = 0; i < 9; i++) P.F[i] = 0.0;
+    for (int i = 0; i < 16; i++) P.sf[i] = 1.f;
+    P.queries = Q, P.bfeat = A.fv_feat + (size_t)f * A.cap;
+    P.descA = have ? vo::kf_sec<uint4>(A.S, k, A.S.o_desc) : nullptr;
+    P.descB = reinterpret_cast<const uint4 *>(A.fdesc + (size_t)f * A.cap * 32);
+    P.angA = have ? vo::kf_sec<float>(A.S, k, A.S.o_angle) : nullptr, P.angB = A.fangle + (size_t)f * A.cap;
+    P.xA = P.yA = P.urA = P.xB = P.yB = P.urB = nullptr, P.octB = nullptr;
+    P.b_ok = A.ones;
+    P.claims = A.claims + (size_t)p * A.NK;
+    P.match = A.match + (size_t)p * A.cap, P.n_matches = A.n_matches + p;
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fill_u8(uint8_t *p, int n, uint8_t v) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) p[i] = v;
+}
+
+}  // namespace
+
+int vo::bow_walk_reserve(vo::BowWalkBufs &b, int B, int cap, int per, int NK, hipStream_t st) {
+  if (b.B == B && b.cap == cap && b.per == per && b.NK == NK) return VO_OK;
+  if (cap > kNodeMaxB) {
+    vo::set_error("BoW search on resident frames: %d feature slots per frame (the kernels handle %d)", cap, kNodeMaxB);
+    return VO_ERR_CAPACITY;
+  }
+  const size_t N = (size_t)B * cap, P = (size_t)B * per;
+  VO_CHECK(b.w.reserve(N * 4));
+  VO_CHECK(b.wt.reserve(N * 8));
+  VO_CHECK(b.node.reserve(N * 4));
+  VO_CHECK(b.fv_nn.reserve((size_t)B * 4 + 64));
+  VO_CHECK(b.fv_node.reserve(N * 4));
+  VO_CHECK(b.fv_start.reserve((size_t)B * (cap + 1) * 4));
+  VO_CHECK(b.fv_feat.reserve(N * 4));
+  VO_CHECK(b.queries.reserve(P * NK * 16));
+  VO_CHECK(b.claims.reserve(P * NK * 16));
+  VO_CHECK(b.args.reserve(P * sizeof(NodeArgs)));
+  VO_CHECK(b.ones.reserve((size_t)cap + 64));
+  hipLaunchKernelGGL(k_fill_u8, dim3((cap + 255) / 256), dim3(256), 0, st, b.ones.as<uint8_t>(), cap, (uint8_t)1);
+  VO_HIP_CHECK(hipGetLastError());
+  b.B = B, b.cap = cap, b.per = per, b.NK = NK;
+  return VO_OK;
+}
+
+int vo::bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int levelsup, vo::BowWalkBufs &b, hipStream_t st,
+                             hipEvent_t ev0, hipEvent_t ev1) {
+  if (!v || !frames || B < 1 || B != b.B) return VO_ERR_INVALID;
+  const vo::FrameStoreView fs = vo::frame_store_view(frames);
+  if (fs.cap != b.cap) {
+    vo::set_error("BoW search on resident frames: %d feature slots per frame, the store has %d", b.cap, fs.cap);
+    return VO_ERR_CAPACITY;
+  }
+  const size_t N = (size_t)B * b.cap;
+  // Frame::computeBow (frame.cpp:248-253), as bow_search_resident runs it
+  hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, v->V, (int)N,
+                     reinterpret_cast<const uint32_t *>(fs.desc), levelsup, b.w.as<int>(), b.wt.as<double>(), b.node.as<int>());
+  VO_HIP_CHECK(hipGetLastError());
+  if (ev0) VO_HIP_CHECK(hipEventRecord(ev0, st));
+  FeatVecArgs A{fs.n, 0, b.cap, b.node.as<int>(), b.fv_nn.as<int>(), 1, b.fv_node.as<int>(), b.fv_start.as<int>(), b.fv_feat.as<int>()};
+  VO_CHECK(launch_featvec(A, B, st));
+  if (ev1) VO_HIP_CHECK(hipEventRecord(ev1, st));
+  return VO_OK;
+}
+
+int vo::featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int *dev_node, int *dev_start, int *dev_feat,
+                    hipStream_t st) {
+  if (n < 0 || n > kNodeMaxB || !dev_n_nodes || !dev_start || (n > 0 && (!dev_node_of_feature || !dev_node || !dev_feat)))
+    return VO_ERR_INVALID;
+  FeatVecArgs A{nullptr, n, n, dev_node_of_feature, dev_n_nodes, 0, dev_node, dev_start, dev_feat};
+  return launch_featvec(A, 1, st);
+}
+
+int vo::bow_walk_replay(vo_frames *frames, int B, int per, const vo::KfStoreView &S, const int *dev_pair_kf, float ratio,
+                        int check_rot, vo::BowWalkBufs &b, int32_t *dev_assigned, int32_t *dev_n_matches, hipStream_t st,
+                        hipEvent_t ev0, hipEvent_t ev1) {
+  if (!frames || B != b.B || per != b.per || !dev_pair_kf || !dev_assigned || !dev_n_matches) return VO_ERR_INVALID;
+  if (S.NK > b.NK) return VO_ERR_CAPACITY;
+  const vo::FrameStoreView fs = vo::frame_store_view(frames);
+  const int NP = B * per;
+  BowWalkArgs A{};
+  A.per = per, A.cap = b.cap, A.NK = b.NK, A.check_rot = check_rot, A.ratio = ratio, A.S = S, A.pair_kf = dev_pair_kf;
+  A.fn = fs.n, A.fdesc = fs.desc, A.fangle = fs.angle;
+  A.fv_nn = b.fv_nn.as<int>(), A.fv_node = b.fv_node.as<int>(), A.fv_start = b.fv_start.as<int>(), A.fv_feat = b.fv_feat.as<uint32_t>();
+  A.queries = b.queries.as<int4>(), A.claims = b.claims.as<int4>(), A.args = b.args.as<NodeArgs>(), A.ones = b.ones.as<uint8_t>();
+  A.match = dev_assigned, A.n_matches = dev_n_matches;
+  if (ev0) VO_HIP_CHECK(hipEventRecord(ev0, st));
+  hipLaunchKernelGGL(k_bow_walk, dim3((unsigned)NP), dim3(64), 0, st, A);
+  VO_HIP_CHECK(hipGetLastError());
+  if (ev1) VO_HIP_CHECK(hipEventRecord(ev1, st));
+  // (the frames' feature counts stay on the device: the taken[] / tmpb[] arrays are sized for the store's capacity)
+  const size_t lds = (((size_t)b.cap + 15) & ~(size_t)15) * 5;
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
+  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)NP), dim3(64), lds, st, b.args.as<const NodeArgs>());
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "ba_math.h"
+#include "block_sort.h"
 
 namespace {
 
@@ -426,6 +427,137 @@ __global__ __launch_bounds__(256) void k_reloc_finish(RelocDev D, int *winner, u
   }
 }
 
+// ---- the store routes: the candidates are key-frame numbers in device memory ------------------
+enum { kErrTooMany = 1, kErrBadId = 2 };  // the sticky word of the store routes
+
+struct StoreDev {
+  vo::KfStoreView S;
+  const int *n_cand_in, *cand_in;  // the caller's (or the database's) lists: [B], [B][cand_stride]
+  int cand_stride;
+  int *nc, *nc_true, *walked, *pair_kf;  // [B] walked / true counts, [B * MC] ids as given (-1 beyond), validated (-1: none)
+  int *kf_n;                             // the Reloc arrays the dependent tail reads, written here
+  uint8_t *kf_bad, *kf_flags;
+  double *kf_point;
+  int *kf_id;
+  uint8_t *kf_pdesc;
+  float *kf_mind, *kf_maxd, *kf_angle;
+  int *l2g;    // [B][MC * NK] local id -> global id
+  int *fid_g;  // [B][cap] the frame's ids at the end, global
+  int *err;
+};
+
+// Candidate c of frame f: the chosen key-frame's record out of the store into the arrays of pair p = f * MC + c, in the
+// layout reloc_set_candidates uploads -- the dependent tail runs unchanged.  A number outside the store makes the pair a
+// bad key-frame without features and raises the sticky word; so does a frame with more candidates than MC (its first MC
+// are walked).  The word is only ever OR-ed: its value does not depend on the order of the workgroups.
+__global__ __launch_bounds__(256) void k_kfstore_gather(RelocDev D, StoreDev T) {
+  const int p = blockIdx.x, f = p / D.MC, c = p % D.MC, tid = threadIdx.x;
+  const int ntrue = T.n_cand_in[f], nc = min(max(ntrue, 0), min(D.MC, T.cand_stride));
+  if (c == 0 && tid == 0) {
+    T.nc[f] = nc, T.nc_true[f] = ntrue;
+    if (ntrue > D.MC) atomicOr(T.err, kErrTooMany);
+  }
+  int raw = -1, k = -1;
+  if (c < nc) {
+    raw = T.cand_in[(size_t)f * T.cand_stride + c];
+    if (raw >= 0 && raw < T.S.size) k = raw;
+    else if (tid == 0) atomicOr(T.err, kErrBadId);
+  }
+  if (tid == 0) T.walked[p] = raw, T.pair_kf[p] = k;
+  if (c >= nc) return;  // (the arrays of a pair beyond the frame's count are never read)
+  if (k < 0) {
+    if (tid == 0) T.kf_n[p] = 0, T.kf_bad[p] = 1;
+    return;
+  }
+  const int *head = vo::kf_head(T.S, k);
+  const int n = min(max(head[0], 0), D.NK);
+  if (tid == 0) T.kf_n[p] = n, T.kf_bad[p] = head[1] != 0;
+  const size_t ko = (size_t)p * D.NK;
+  const uint8_t *flags = vo::kf_sec<uint8_t>(T.S, k, T.S.o_flags);
+  const int *ids = vo::kf_sec<int>(T.S, k, T.S.o_ids);
+  const float *mind = vo::kf_sec<float>(T.S, k, T.S.o_mind), *maxd = vo::kf_sec<float>(T.S, k, T.S.o_maxd);
+  const float *angle = vo::kf_sec<float>(T.S, k, T.S.o_angle);
+  const double *pts = vo::kf_sec<double>(T.S, k, T.S.o_points);
+  const uint32_t *pd = vo::kf_sec<uint32_t>(T.S, k, T.S.o_pdesc);
+  for (int i = tid; i < n; i += 256) {
+    T.kf_flags[ko + i] = flags[i], T.kf_id[ko + i] = (flags[i] & 1) ? ids[i] : 0;  // (an unflagged feature's id is never read)
+    T.kf_mind[ko + i] = mind[i], T.kf_maxd[ko + i] = maxd[i], T.kf_angle[ko + i] = angle[i];
+  }
+  for (int i = tid; i < 3 * n; i += 256) T.kf_point[3 * ko + i] = pts[i];
+  uint32_t *opd = reinterpret_cast<uint32_t *>(T.kf_pdesc + ko * 32);
+  for (int i = tid; i < 8 * n; i += 256) opd[i] = pd[i];
+}
+
+// MapPoint identity for the walk: `found` and fid are indexed by an id in [0, MC * NK), the store's ids are any
+// non-negative int32.  One workgroup per frame: the flagged features of the frame's candidates as keys (global id << 32 |
+// slot), slot = c * NK + i; sorted (distinct keys: one possible order), every feature's local id is the SMALLEST slot that
+// carries its global id -- the head of its run, found by binary search.  Equal global ids get equal local ids, distinct
+// ones distinct slots, all below MC * NK, and nothing depends on timing.  l2g keeps the way back.  Keys in LDS when the
+// power of two above MC * NK fits (lds_slots), else in a slab of device memory owned by the frame.
+__global__ __launch_bounds__(256) void k_reloc_local_ids(int MC, int NK, const int *nc, const int *kf_n, const uint8_t *kf_flags,
+                                                         int *kf_id, int *l2g, unsigned long long *gkeys, int gstride, int lds_slots) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long li_keys[];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const int M = min(max(nc[f], 0), MC) * NK, np2 = vo::pow2_ceil(M);
+  if (M == 0) return;
+  unsigned long long *keys = np2 <= lds_slots ? li_keys : gkeys + (size_t)f * gstride;
+  const size_t fo = (size_t)f * MC * NK;
+  for (int s = tid; s < np2; s += 256) {
+    unsigned long long key = ~0ull;
+    if (s < M) {
+      const int c = s / NK, i = s - c * NK;
+      if (i < kf_n[f * MC + c] && (kf_flags[fo + s] & 1)) key = ((unsigned long long)(unsigned)kf_id[fo + s] << 32) | (unsigned)s;
+    }
+    keys[s] = key;
+  }
+  vo::block_bitonic_sort(keys, np2);
+  for (int j = tid; j < np2; j += 256) {
+    const unsigned long long key = keys[j];
+    if (key == ~0ull) continue;
+    const unsigned long long first = key & 0xffffffff00000000ull;
+    int lo = 0, hi = j;  // first position whose key is >= (id, slot 0): the head of the id's run
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (keys[mid] < first) lo = mid + 1;
+      else hi = mid;
+    }
+    const int local = (int)(keys[lo] & 0xffffffffu);
+    kf_id[fo + (key & 0xffffffffu)] = local;
+    if (lo == j) l2g[fo + local] = (int)(key >> 32);
+  }
+}
+
+// behind k_reloc_finish: the frame's ids back as the store's, the sticky word into the result block (third flag)
+__global__ __launch_bounds__(256) void k_reloc_store_finish(RelocDev D, StoreDev T, uint8_t *resblk) {
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const size_t o = (size_t)f * D.cap, fo = (size_t)f * D.MC * D.NK;
+  for (int i = tid; i < D.cap; i += 256) {
+    const int id = D.fid[o + i];
+    T.fid_g[o + i] = id >= 0 && id < D.MC * D.NK ? T.l2g[fo + id] : -1;
+  }
+  if (f == 0 && tid == 0) reinterpret_cast<int *>(resblk + (size_t)D.B * 72)[2] = *T.err;
+}
+
+// Map::detectRelocalizationCandidates' query vectors: the frames' (word, weight) pairs out of the [B][cap] slots into the
+// ragged layout vo_bow_vector_dev reads.  One workgroup scans the feature counts, one per frame copies.
+__global__ __launch_bounds__(256) void k_reloc_word_start(int B, int cap, const int *fn, int *start) {
+  __shared__ int s_sum[256];
+  const int tid = threadIdx.x, per = (B + 255) / 256, b = min(tid * per, B), e = min(b + per, B);
+  int s = 0;
+  for (int i = b; i < e; i++) s += min(max(fn[i], 0), cap);
+  s_sum[tid] = s;
+  __syncthreads();
+  int base = 0;
+  for (int t = 0; t < tid; t++) base += s_sum[t];
+  for (int i = b; i < e; i++) start[i] = base, base += min(max(fn[i], 0), cap);
+  if (tid == 255) start[B] = base;
+}
+__global__ __launch_bounds__(256) void k_reloc_word_pack(int cap, const int *fn, const int *start, const int *w, const double *wt,
+                                                         int *ow, double *owt) {
+  const int f = blockIdx.x, n = min(max(fn[f], 0), cap), o = start[f];
+  for (int i = threadIdx.x; i < n; i += 256) ow[o + i] = w[(size_t)f * cap + i], owt[o + i] = wt[(size_t)f * cap + i];
+}
+
 struct CandHost {
   int n = 0;
   std::vector<uint8_t> valid, desc;
@@ -448,13 +580,32 @@ struct vo::Reloc {
   DevBuf rec, fid, found, out_bow, out_pnp, out_code, nq, qflags, qu, qv, qlevel, ninl_solve, winner;
   BowResidentBufs bow;
   PinnedBuf stage;
+  // the store routes: sized by reloc_store_prepare on their first call
+  bool store_ready = false, store_db = false, last_store = false;
+  int ids_lds_slots = 0, ids_gstride = 0;
+  BowWalkBufs walk;
+  DevBuf s_nc, s_nc_true, s_walked, s_pair_kf, s_l2g, s_fid_g, s_err, s_keys;
+  DevBuf q_fstart, q_w, q_wt, q_bstart, q_bw, q_bv, q_nc, q_cand;  // the database query
   std::vector<DevBuf *> all() {
+    std::vector<DevBuf *> v = base();
+    for (DevBuf *b : walk.all()) v.push_back(b);
+    for (DevBuf *b : {&s_nc, &s_nc_true, &s_walked, &s_pair_kf, &s_l2g, &s_fid_g, &s_err, &s_keys, &q_fstart, &q_w, &q_wt, &q_bstart,
+                      &q_bw, &q_bv, &q_nc, &q_cand})
+      v.push_back(b);
+    return v;
+  }
+  std::vector<DevBuf *> base() {
     return {&sf, &n_cand, &kf_n, &kf_bad, &kf_flags, &kf_point, &kf_id, &kf_pdesc, &kf_mind, &kf_maxd, &kf_angle, &bow_assigned,
             &bow_n, &cnt, &off, &p3, &p2, &src, &pnp_T, &pnp_mask, &pnp_n, &pnp_status, &pnp_ws, &dbg_mask, &rec, &fid, &found,
             &out_bow, &out_pnp, &out_code, &nq, &qflags, &qu, &qv, &qlevel, &ninl_solve, &winner, &bow.w, &bow.wt, &bow.node,
             &bow.img};
   }
 };
+
+namespace {
+RelocDev reloc_dev(vo::Reloc *r, const vo::RelocShared &S, const int *n_cand);
+int reloc_tail(vo::Reloc *r, const vo::RelocShared &S, const RelocDev &D);
+}  // namespace
 
 namespace vo {
 
@@ -635,9 +786,8 @@ int reloc_run(Reloc *r, const RelocShared &S) {
     set_error("vo_tracker_relocalize: no candidates (vo_tracker_set_reloc_candidates)");
     return VO_ERR_INVALID;
   }
-  const int B = r->B, MC = r->MC, NK = r->NK, P = B * MC;
+  const int B = r->B, MC = r->MC, P = B * MC;
   hipStream_t st = S.st;
-  const FrameStoreView fs = frame_store_view(S.frames);
   // ---- independent front: searchByBoW of every pair (the call's one synchronisation is inside, after computeBow)
   std::vector<RefKeyFrame> kfs((size_t)P);
   for (int p = 0; p < P; p++) {
@@ -646,10 +796,23 @@ int reloc_run(Reloc *r, const RelocShared &S) {
   }
   VO_CHECK(bow_search_resident(r->vocab, S.frames, 0, B, kfs.data(), 0.75f, 1, 3, r->bow_assigned.as<int32_t>(), r->cap,
                                r->bow_n.as<int32_t>(), st, MC, &r->bow));
+  r->last_store = false;
+  const RelocDev D = reloc_dev(r, S, r->n_cand.as<int>());
+  return reloc_tail(r, S, D);
+}
+
+}  // namespace vo
+
+namespace {
+
+// the device view of a route: the Reloc object's arrays and the tracker's (n_cand: the per-frame counts the walk obeys)
+RelocDev reloc_dev(vo::Reloc *r, const vo::RelocShared &S, const int *n_cand) {
+  const vo::FrameStoreView fs = vo::frame_store_view(S.frames);
+  const int B = r->B, MC = r->MC, NK = r->NK;
   RelocDev D{};
   D.B = B, D.cap = r->cap, D.MC = MC, D.NK = NK;
   D.fn = fs.n, D.X = fs.x, D.Y = fs.y, D.UR = fs.uright, D.OCT = fs.octave, D.sf = r->sf.as<float>();
-  D.n_cand = r->n_cand.as<int>(), D.kf_n = r->kf_n.as<int>(), D.kf_bad = r->kf_bad.as<uint8_t>();
+  D.n_cand = n_cand, D.kf_n = r->kf_n.as<int>(), D.kf_bad = r->kf_bad.as<uint8_t>();
   D.kf_flags = r->kf_flags.as<uint8_t>(), D.kf_point = r->kf_point.as<double>(), D.kf_id = r->kf_id.as<int>();
   D.kf_mind = r->kf_mind.as<float>(), D.kf_maxd = r->kf_maxd.as<float>();
   D.bow_assigned = r->bow_assigned.as<int>(), D.bow_n = r->bow_n.as<int>(), D.cnt = r->cnt.as<int>(), D.off = r->off.as<int>();
@@ -662,6 +825,13 @@ int reloc_run(Reloc *r, const RelocShared &S) {
   D.qlevel = r->qlevel.as<int>(), D.ninl_solve = r->ninl_solve.as<int>();
   D.pose = S.pose, D.fpoint = S.fpoint, D.fhas = S.fhas, D.foutl = S.foutl, D.pts = S.pts, D.obs = S.obs, D.isg = S.isg;
   D.ranges = S.ranges, D.index = S.index, D.outlier = S.outlier, D.assigned = S.assigned, D.nm = S.nm;
+  return D;
+}
+
+// everything behind the BoW searches: the PnP of every pair, the dependent tail, the result block
+int reloc_tail(vo::Reloc *r, const vo::RelocShared &S, const RelocDev &D) {
+  const int B = r->B, MC = r->MC, NK = r->NK, P = B * MC;
+  hipStream_t st = S.st;
   // ---- poseEstimateByPnP of every pair: ragged correspondence lists with device offsets, then the RANSAC
   hipLaunchKernelGGL(k_reloc_count, dim3(P), dim3(256), 0, st, D);
   hipLaunchKernelGGL(k_reloc_scan, dim3(1), dim3(256), 0, st, P, (const int *)D.cnt, D.off);
@@ -711,18 +881,125 @@ int reloc_run(Reloc *r, const RelocShared &S) {
   return VO_OK;
 }
 
+}  // namespace
+
+namespace vo {
+
 const void *reloc_selector(const Reloc *r, int what, size_t *bytes) {
   if (!r) return nullptr;
   const size_t B = r->B, P = B * r->MC;
   switch (what) {
     case VO_TRACKER_RELOC_WINNER: *bytes = B * 4; return r->winner.p;
-    case VO_TRACKER_RELOC_POINT_IDS: *bytes = B * r->cap * 4; return r->fid.p;
+    case VO_TRACKER_RELOC_POINT_IDS: *bytes = B * r->cap * 4; return r->last_store ? r->s_fid_g.p : r->fid.p;
     case VO_TRACKER_RELOC_BOW_MATCHES: *bytes = P * 4; return r->out_bow.p;
     case VO_TRACKER_RELOC_PNP_INLIERS: *bytes = P * 4; return r->out_pnp.p;
     case VO_TRACKER_RELOC_OUTCOME: *bytes = P * 4; return r->out_code.p;
     case VO_TRACKER_RELOC_PNP_MASK: *bytes = P * r->cap; return r->dbg_mask.p;
+    case VO_TRACKER_RELOC_CANDIDATES: *bytes = P * 4; return r->last_store ? r->s_walked.p : nullptr;
+    case VO_TRACKER_RELOC_N_CANDIDATES: *bytes = B * 4; return r->last_store ? r->s_nc_true.p : nullptr;
     default: return nullptr;
   }
 }
+
+// ---- the store routes ------------------------------------------------------------------------------------------
+int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st) {
+  if (!r) return VO_ERR_INVALID;
+  const size_t B = r->B, P = B * r->MC, PK = P * r->NK, Bc = B * r->cap;
+  if (!r->store_ready) {
+    VO_CHECK(bow_walk_reserve(r->walk, r->B, r->cap, r->MC, r->NK, st));
+    VO_CHECK(r->s_nc.reserve(B * 4 + 64));
+    VO_CHECK(r->s_nc_true.reserve(B * 4 + 64));
+    VO_CHECK(r->s_walked.reserve(P * 4 + 64));
+    VO_CHECK(r->s_pair_kf.reserve(P * 4 + 64));
+    VO_CHECK(r->s_l2g.reserve(PK * 4));
+    VO_CHECK(r->s_fid_g.reserve(Bc * 4));
+    VO_CHECK(r->s_err.reserve(64));
+    VO_HIP_CHECK(hipMemsetAsync(r->s_err.p, 0, 64, st));
+    // the id compaction sorts the power of two above MC * NK keys per frame: in LDS up to 128 KiB, else in a slab
+    const int np2 = pow2_ceil(r->MC * r->NK);
+    if ((size_t)np2 * 8 <= 128 * 1024) {
+      r->ids_lds_slots = np2, r->ids_gstride = 0;
+      if ((size_t)np2 * 8 > 64 * 1024)
+        VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_reloc_local_ids, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    } else {
+      r->ids_lds_slots = 0, r->ids_gstride = np2;
+      VO_CHECK(r->s_keys.reserve(B * (size_t)np2 * 8));
+    }
+    r->store_ready = true;
+  }
+  if (with_db && !r->store_db) {
+    VO_CHECK(r->q_fstart.reserve(B * 4 + 64));
+    VO_CHECK(r->q_w.reserve(Bc * 4));
+    VO_CHECK(r->q_wt.reserve(Bc * 8));
+    VO_CHECK(r->q_bstart.reserve(B * 4 + 64));
+    VO_CHECK(r->q_bw.reserve(Bc * 4));
+    VO_CHECK(r->q_bv.reserve(Bc * 8));
+    VO_CHECK(r->q_nc.reserve(B * 4 + 64));
+    VO_CHECK(r->q_cand.reserve(P * 4 + 64));
+    r->store_db = true;
+  }
+  return VO_OK;
+}
+
+int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
+  if (!r || !r->store_ready || !A.store || !A.vocab || (A.db ? !r->store_db : (!A.dev_n_cand || !A.dev_cand || A.cand_stride < 0)))
+    return VO_ERR_INVALID;
+  const int B = r->B, MC = r->MC, NK = r->NK, P = B * MC;
+  hipStream_t st = S.st;
+  const FrameStoreView fs = frame_store_view(S.frames);
+  hipEvent_t *ev = A.tev;
+  auto mark = [&](int i) -> int {
+    if (ev) VO_HIP_CHECK(hipEventRecord(ev[i], st));
+    return VO_OK;
+  };
+  r->have = false;  // the candidate arrays are the store's from here: vo_tracker_relocalize needs its candidates set again
+  r->last_store = true;
+  // ---- Frame::computeBow and the frames' FeatureVectors
+  VO_CHECK(bow_featvec_resident(A.vocab, S.frames, B, 3, r->walk, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+  // ---- Map::detectRelocalizationCandidates: the frames' BoW vectors, the database query
+  const int *n_cand = A.dev_n_cand, *cand = A.dev_cand;
+  int stride = A.cand_stride;
+  if (A.db) {
+    hipLaunchKernelGGL(k_reloc_word_start, dim3(1), dim3(256), 0, st, B, r->cap, fs.n, r->q_fstart.as<int>());
+    hipLaunchKernelGGL(k_reloc_word_pack, dim3(B), dim3(256), 0, st, r->cap, fs.n, (const int *)r->q_fstart.as<int>(),
+                       (const int *)r->walk.w.as<int>(), (const double *)r->walk.wt.as<double>(), r->q_w.as<int>(), r->q_wt.as<double>());
+    VO_HIP_CHECK(hipGetLastError());
+    VO_CHECK(vo_bow_vector_dev(B, B * r->cap, r->q_fstart.as<int>(), r->q_w.as<int>(), r->q_wt.as<double>(), r->q_bstart.as<int>(),
+                               r->q_bw.as<int>(), r->q_bv.as<double>(), st));
+    VO_CHECK(kfdb_query_reloc_on(A.db, st, B, r->q_bstart.as<int>(), r->q_bw.as<int>(), r->q_bv.as<double>(), A.dev_stale, MC,
+                                 r->q_nc.as<int>(), r->q_cand.as<int>()));
+    n_cand = r->q_nc.as<int>(), cand = r->q_cand.as<int>(), stride = MC;
+  }
+  // ---- the candidates out of the store, their ids made dense
+  VO_CHECK(kfstore_order_before(A.store, st));
+  const RelocDev D = reloc_dev(r, S, r->s_nc.as<int>());
+  StoreDev T{};
+  T.S = kfstore_view(A.store), T.n_cand_in = n_cand, T.cand_in = cand, T.cand_stride = stride;
+  T.nc = r->s_nc.as<int>(), T.nc_true = r->s_nc_true.as<int>(), T.walked = r->s_walked.as<int>(), T.pair_kf = r->s_pair_kf.as<int>();
+  T.kf_n = r->kf_n.as<int>(), T.kf_bad = r->kf_bad.as<uint8_t>(), T.kf_flags = r->kf_flags.as<uint8_t>();
+  T.kf_point = r->kf_point.as<double>(), T.kf_id = r->kf_id.as<int>(), T.kf_pdesc = r->kf_pdesc.as<uint8_t>();
+  T.kf_mind = r->kf_mind.as<float>(), T.kf_maxd = r->kf_maxd.as<float>(), T.kf_angle = r->kf_angle.as<float>();
+  T.l2g = r->s_l2g.as<int>(), T.fid_g = r->s_fid_g.as<int>(), T.err = r->s_err.as<int>();
+  VO_CHECK(mark(2));
+  hipLaunchKernelGGL(k_kfstore_gather, dim3(P), dim3(256), 0, st, D, T);
+  VO_HIP_CHECK(hipGetLastError());
+  VO_CHECK(mark(3));
+  VO_CHECK(mark(4));
+  hipLaunchKernelGGL(k_reloc_local_ids, dim3(B), dim3(256), (size_t)r->ids_lds_slots * 8, st, MC, NK, (const int *)T.nc,
+                     (const int *)T.kf_n, (const uint8_t *)T.kf_flags, T.kf_id, T.l2g, r->s_keys.as<unsigned long long>(),
+                     r->ids_gstride, r->ids_lds_slots);
+  VO_HIP_CHECK(hipGetLastError());
+  VO_CHECK(mark(5));
+  // ---- searchByBoW of every pair: the common-node walk and the replay
+  VO_CHECK(bow_walk_replay(S.frames, B, MC, T.S, T.pair_kf, 0.75f, 1, r->walk, r->bow_assigned.as<int32_t>(), r->bow_n.as<int32_t>(), st,
+                           ev ? ev[6] : nullptr, ev ? ev[7] : nullptr));
+  VO_CHECK(reloc_tail(r, S, D));
+  hipLaunchKernelGGL(k_reloc_store_finish, dim3(B), dim3(256), 0, st, D, T, S.resblk);
+  VO_HIP_CHECK(hipGetLastError());
+  return kfstore_order_after(A.store, st);
+}
+
+const int *reloc_store_error_flag(const Reloc *r) { return r && r->store_ready ? r->s_err.as<int>() : nullptr; }
+bool reloc_last_was_store(const Reloc *r) { return r && r->last_store; }
 
 }  // namespace vo

@@ -330,6 +330,10 @@ struct vo_tracker {
   std::vector<RefKfHost> ref_kf;
   // the relocalisation route (reloc.hip); NULL: not configured (vo_tracker_config.max_reloc_candidates == 0)
   vo::Reloc *reloc = nullptr;
+  const vo::RelocStoreArgs *store_args = nullptr;  // set for the duration of a vo_tracker_relocalize_store / _db call
+  const char *store_call = "";                      // the entry point of the last store route (error texts)
+  hipEvent_t rtev[8] = {nullptr};                   // vo_tracker_get_reloc_timing: created by the first timed store route
+  bool rtimed = false;
   // timing
   bool timing = false;
   // 2 events per stage and timed call, in a list that grows with the calls; they are read (after one synchronisation) only
@@ -671,7 +675,17 @@ int stage_reloc(vo_tracker *t) {
   VO_CHECK(t->resblk.reserve((size_t)t->B * 72 + 64));
   S.resblk = t->resblk.as<uint8_t>(), S.orb_err = vo::orb_error_flag(t->orb), S.guided_err = vo::guided_error_flag(t->frames);
   S.st = t->st;
-  return vo::reloc_run(t->reloc, S);
+  if (!t->store_args) return vo::reloc_run(t->reloc, S);
+  vo::RelocStoreArgs A = *t->store_args;
+  t->rtimed = false;
+  if (t->timing) {  // events around the four new stages of the call (vo_tracker_get_reloc_timing)
+    for (hipEvent_t &e : t->rtev)
+      if (!e) VO_HIP_CHECK(hipEventCreate(&e));
+    A.tev = t->rtev;
+  }
+  VO_CHECK(vo::reloc_run_store(t->reloc, S, A));
+  t->rtimed = t->timing;
+  return VO_OK;
 }
 
 int run_pipeline(vo_tracker *t, const uint8_t *dev_images, int img_pitch, size_t img_frame_stride, const void *dev_depth,
@@ -818,6 +832,8 @@ void vo_tracker_destroy(vo_tracker *t) {
   if (t->ev_build) (void)hipEventDestroy(t->ev_build);
   if (t->ev_depth) (void)hipEventDestroy(t->ev_depth);
   if (t->reloc) vo::reloc_destroy(t->reloc);
+  for (hipEvent_t e : t->rtev)
+    if (e) (void)hipEventDestroy(e);
   if (t->frames) vo_frames_destroy(t->frames);
   if (t->orb) vo_orb_destroy(t->orb);
   for (DevBuf *b : {&t->kps, &t->desc, &t->cnt, &t->images, &t->depth, &t->q0_flags, &t->q0_u, &t->q0_v, &t->q0_aux, &t->q0_level,
@@ -1051,6 +1067,106 @@ int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int imag
                       params, kRunFront | kRunReloc);
 }
 
+// what both store routes check before anything is enqueued; sizes the route's buffers on the first call
+static int store_route_ready(vo_tracker *t, const char *call, vo_kfdb *db, const vo_kfstore *store, const vo_vocab *vocab) {
+  VO_CHECK(reloc_ready(t));
+  if (!store || !vocab) {
+    vo::set_error("%s: no store or no vocabulary", call);
+    return VO_ERR_INVALID;
+  }
+  const vo::KfStoreView V = vo::kfstore_view(store);
+  if (V.NK > t->cfg.max_reloc_features) {
+    vo::set_error("%s: the store holds %d features per key-frame, the tracker %d (max_reloc_features)", call, V.NK,
+                  t->cfg.max_reloc_features);
+    return VO_ERR_CAPACITY;
+  }
+  if (db) {
+    int size = 0, max_batch = 0;
+    vo::kfdb_info(db, &size, &max_batch);
+    if (size != V.size) {
+      vo::set_error("%s: the database holds %d key-frames, the store %d", call, size, V.size);
+      return VO_ERR_INVALID;
+    }
+    if (max_batch < t->B) {
+      vo::set_error("%s: a batch of %d frames, the database was created for batches of %d", call, t->B, max_batch);
+      return VO_ERR_CAPACITY;
+    }
+  }
+  t->store_call = call;
+  return vo::reloc_store_prepare(t->reloc, db != nullptr, t->st);
+}
+
+static int store_route_host(vo_tracker *t, const vo::RelocStoreArgs &A, const uint8_t *images, const void *depth, int depth_kind,
+                            const vo_tracker_params *params) {
+  t->store_args = &A;
+  const int rc = track_host(t, images, depth, depth_kind, params, kRunFront | kRunReloc);
+  t->store_args = nullptr;
+  return rc;
+}
+
+static int store_route_dev(vo_tracker *t, const vo::RelocStoreArgs &A, const uint8_t *dev_images, int image_pitch,
+                           size_t image_frame_stride, const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
+                           const vo_tracker_params *params) {
+  if (!dev_images || image_pitch < t->cfg.width || depth_kind < 0 || depth_kind > 2 || (depth_kind && !dev_depth)) return VO_ERR_INVALID;
+  t->store_args = &A;
+  const int rc = run_pipeline(t, dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch,
+                              params, kRunFront | kRunReloc);
+  t->store_args = nullptr;
+  return rc;
+}
+
+int vo_tracker_relocalize_store(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_n_cand,
+                                const int32_t *dev_cand, int cand_stride, const uint8_t *images, const void *depth, int depth_kind,
+                                const vo_tracker_params *params) {
+  VO_CHECK(store_route_ready(t, "vo_tracker_relocalize_store", nullptr, store, vocab));
+  if (!dev_n_cand || !dev_cand || cand_stride < 1) return VO_ERR_INVALID;
+  const vo::RelocStoreArgs A{store, vocab, dev_n_cand, dev_cand, cand_stride, nullptr, nullptr, nullptr};
+  return store_route_host(t, A, images, depth, depth_kind, params);
+}
+
+int vo_tracker_relocalize_store_dev(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_n_cand,
+                                    const int32_t *dev_cand, int cand_stride, const uint8_t *dev_images, int image_pitch,
+                                    size_t image_frame_stride, const void *dev_depth, int depth_kind, size_t depth_frame_stride,
+                                    int depth_pitch, const vo_tracker_params *params) {
+  VO_CHECK(store_route_ready(t, "vo_tracker_relocalize_store_dev", nullptr, store, vocab));
+  if (!dev_n_cand || !dev_cand || cand_stride < 1) return VO_ERR_INVALID;
+  const vo::RelocStoreArgs A{store, vocab, dev_n_cand, dev_cand, cand_stride, nullptr, nullptr, nullptr};
+  return store_route_dev(t, A, dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch, params);
+}
+
+int vo_tracker_relocalize_db(vo_tracker *t, vo_kfdb *db, const vo_kfstore *store, const vo_vocab *vocab, const float *dev_stale_score,
+                             const uint8_t *images, const void *depth, int depth_kind, const vo_tracker_params *params) {
+  if (!db) return VO_ERR_INVALID;
+  VO_CHECK(store_route_ready(t, "vo_tracker_relocalize_db", db, store, vocab));
+  const vo::RelocStoreArgs A{store, vocab, nullptr, nullptr, 0, db, dev_stale_score, nullptr};
+  return store_route_host(t, A, images, depth, depth_kind, params);
+}
+
+int vo_tracker_relocalize_db_dev(vo_tracker *t, vo_kfdb *db, const vo_kfstore *store, const vo_vocab *vocab,
+                                 const float *dev_stale_score, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
+                                 const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
+                                 const vo_tracker_params *params) {
+  if (!db) return VO_ERR_INVALID;
+  VO_CHECK(store_route_ready(t, "vo_tracker_relocalize_db_dev", db, store, vocab));
+  const vo::RelocStoreArgs A{store, vocab, nullptr, nullptr, 0, db, dev_stale_score, nullptr};
+  return store_route_dev(t, A, dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch, params);
+}
+
+int vo_tracker_get_reloc_timing(vo_tracker *t, double *ms) {
+  if (!t || !ms) return VO_ERR_INVALID;
+  if (!t->rtimed) {
+    vo::set_error("vo_tracker_get_reloc_timing: no store route has run with timing on (vo_tracker_set_timing)");
+    return VO_ERR_INVALID;
+  }
+  VO_HIP_CHECK(hipStreamSynchronize(t->st));
+  for (int s = 0; s < VO_TRACKER_RELOC_STAGES; s++) {
+    float v = 0.f;
+    VO_HIP_CHECK(hipEventElapsedTime(&v, t->rtev[2 * s], t->rtev[2 * s + 1]));
+    ms[s] = v;
+  }
+  return VO_OK;
+}
+
 int vo_tracker_track(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind, const vo_tracker_params *params) {
   return track_host(t, images, depth, depth_kind, params, kRunFront | kRunMotion | kRunLocal);
 }
@@ -1065,7 +1181,7 @@ int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_
   }
   VO_CHECK(t->stage.reserve(B * 72 + 64));
   uint8_t *h = t->stage.data();
-  VO_HIP_CHECK(hipMemcpyAsync(h, t->resblk.p, B * 72 + 8, hipMemcpyDeviceToHost, t->st));  // one download: k_track_pack's block
+  VO_HIP_CHECK(hipMemcpyAsync(h, t->resblk.p, B * 72 + 12, hipMemcpyDeviceToHost, t->st));  // one download: k_track_pack's block
   VO_HIP_CHECK(hipStreamSynchronize(t->st));
   int32_t *dst[5] = {n_tracked, n_inliers, n_matches_last, n_matches_local, status};
   for (size_t f = 0; f < B; f++) {
@@ -1077,10 +1193,23 @@ int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_
       if (dst[k]) dst[k][f] = pi[k];
   }
   const int32_t *flags = reinterpret_cast<const int32_t *>(h + B * 72);
-  if (flags[0] == 0 && flags[1] == 0) return VO_OK;
-  // a sticky error flag of a stage is up (dropped key-points, exhausted candidate pools): report and clear it
-  VO_CHECK(vo_orb_sync(t->orb));
-  VO_CHECK(vo_match_guided_status(t->frames, t->st));
+  const int32_t store_err = vo::reloc_last_was_store(t->reloc) ? flags[2] : 0;  // (the third word is the store routes' only)
+  if (flags[0] != 0 || flags[1] != 0) {
+    // a sticky error flag of a stage is up (dropped key-points, exhausted candidate pools): report and clear it
+    VO_CHECK(vo_orb_sync(t->orb));
+    VO_CHECK(vo_match_guided_status(t->frames, t->st));
+  }
+  if (store_err) {  // report and clear
+    VO_HIP_CHECK(hipMemsetAsync(const_cast<int *>(vo::reloc_store_error_flag(t->reloc)), 0, 4, t->st));
+    VO_HIP_CHECK(hipMemsetAsync(t->resblk.as<uint8_t>() + B * 72 + 8, 0, 4, t->st));
+    if (store_err & 2) {
+      vo::set_error("%s: a candidate key-frame number lies outside the store (walked as a bad key-frame)", t->store_call);
+      return VO_ERR_INVALID;
+    }
+    vo::set_error("%s: a frame has more candidates than the tracker walks (max_reloc_candidates = %d); the first %d were walked",
+                  t->store_call, t->cfg.max_reloc_candidates, t->cfg.max_reloc_candidates);
+    return VO_ERR_CAPACITY;
+  }
   return VO_OK;
 }
 
@@ -1089,10 +1218,14 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
   const size_t B = t->B, cap = t->cap;
   const DevBuf *b = nullptr;
   size_t bytes = 0;
-  if (what >= VO_TRACKER_RELOC_WINNER && what <= VO_TRACKER_RELOC_PNP_MASK) {
+  if (what >= VO_TRACKER_RELOC_WINNER && what <= VO_TRACKER_RELOC_N_CANDIDATES) {
     VO_CHECK(reloc_ready(t));
     const void *src = vo::reloc_selector(t->reloc, what, &bytes);
-    if (!src) return VO_ERR_INVALID;
+    if (!src) {
+      if (what >= VO_TRACKER_RELOC_CANDIDATES)
+        vo::set_error("vo_tracker_get(%d): the last route was not vo_tracker_relocalize_store / _db", what);
+      return VO_ERR_INVALID;
+    }
     if (dst_bytes < bytes) {
       vo::set_error("vo_tracker_get(%d): destination holds %zu bytes, %zu needed", what, dst_bytes, bytes);
       return VO_ERR_CAPACITY;

@@ -208,6 +208,73 @@ int reloc_run(Reloc *r, const RelocShared &S);
 // device array behind a VO_TRACKER_RELOC_* selector (nullptr: not one of them)
 const void *reloc_selector(const Reloc *r, int what, size_t *bytes);
 
+// ---- the key-frame feature store (kfstore.hip).  One fixed-size record per key-frame, every
+// section at a fixed byte offset: [n, bad, n_nodes, 0 | angle | min_distance | max_distance | ids | node | start | feat |
+// points | desc | point_desc | flags], NK entries per section (start: NK + 1).  A record is one contiguous copy for the
+// host insert; kernels address a section as base + k * rec + offset.
+struct KfStoreView {
+  int size, max_kf, NK;
+  size_t rec;
+  const uint8_t *base;
+  size_t o_angle, o_mind, o_maxd, o_ids, o_node, o_start, o_feat, o_points, o_desc, o_pdesc, o_flags;
+};
+__host__ __device__ __forceinline__ const int *kf_head(const KfStoreView &V, int k) {
+  return reinterpret_cast<const int *>(V.base + (size_t)k * V.rec);
+}
+template <class T>
+__host__ __device__ __forceinline__ const T *kf_sec(const KfStoreView &V, int k, size_t off) {
+  return reinterpret_cast<const T *>(V.base + (size_t)k * V.rec + off);
+}
+KfStoreView kfstore_view(const vo_kfstore *s);
+// `st` waits for what the store's stream holds now / the store's stream waits for what `st` holds now (events, no host wait)
+int kfstore_order_before(const vo_kfstore *s, hipStream_t st);
+int kfstore_order_after(const vo_kfstore *s, hipStream_t st);
+
+// vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
+// query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
+void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
+int kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const int32_t *q_start, const int32_t *q_words,
+                        const double *q_values, const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand);
+
+// ---- searchByBoW against key-frames of a store with the common-node walk on the device (match.hip): k_bow_transform and
+// k_featvec build every resident frame's FeatureVector; k_bow_walk writes every (frame, candidate) pair's query list and
+// argument block; k_node_replay runs as in bow_search_resident.  All buffers are sized once from (B, cap, per, NK).
+struct BowWalkBufs {
+  int B = 0, cap = 0, per = 0, NK = 0;
+  DevBuf w, wt, node;                          // [B][cap] word, weight, node of every feature slot
+  DevBuf fv_nn, fv_node, fv_start, fv_feat;    // the frames' FeatureVectors: [B], [B][cap], [B][cap + 1], [B][cap]
+  DevBuf queries, claims, args, ones;          // [B * per][NK] int4 x 2, [B * per] argument blocks, [cap] ones
+  std::vector<DevBuf *> all() { return {&w, &wt, &node, &fv_nn, &fv_node, &fv_start, &fv_feat, &queries, &claims, &args, &ones}; }
+};
+int bow_walk_reserve(BowWalkBufs &b, int B, int cap, int per, int NK, hipStream_t st);
+int bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int levelsup, BowWalkBufs &b, hipStream_t st,
+                         hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);  // (events around k_featvec)
+// pair p = f * per + c searches key-frame dev_pair_kf[p] of the store (-1: no key-frame, the pair matches nothing)
+int bow_walk_replay(vo_frames *frames, int B, int per, const KfStoreView &S, const int *dev_pair_kf, float ratio, int check_rot,
+                    BowWalkBufs &b, int32_t *dev_assigned, int32_t *dev_n_matches, hipStream_t st, hipEvent_t ev0 = nullptr,
+                    hipEvent_t ev1 = nullptr);  // (events around k_bow_walk)
+// the FeatureVector of n features from their node ids (device arrays): n_nodes into *dev_n_nodes, node [n] ascending,
+// start [n + 1], feat [n] (the features of a node in index order); n <= 16384
+int featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int *dev_node, int *dev_start, int *dev_feat,
+                hipStream_t st);
+
+// The store routes of the tracker (reloc.hip): reloc_run with the candidates read from a store, optionally chosen by
+// the database.  reloc_store_prepare sizes the route's own buffers (first call) before anything is enqueued.
+struct RelocStoreArgs {
+  const vo_kfstore *store;
+  const vo_vocab *vocab;
+  const int *dev_n_cand, *dev_cand;  // device [B], [B][cand_stride]; ignored with a database
+  int cand_stride;
+  vo_kfdb *db;                       // or NULL
+  const float *dev_stale;
+  hipEvent_t *tev;                   // 8 events (featvec, gather, local ids, walk: begin / end) or NULL
+};
+int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st);
+int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A);
+// the sticky word of the store routes (bit 0: more candidates than the route holds, bit 1: a candidate outside the store)
+const int *reloc_store_error_flag(const Reloc *r);
+bool reloc_last_was_store(const Reloc *r);
+
 // vo_set_option's process-wide values as last set, 0 before (vo_common.hip): VO_OPT_BA_GRAPH (ba.hip), VO_OPT_POSE_BLOCK
 // (pose_only.hip), VO_OPT_BA_PAIRS_KERNEL (ba.hip), VO_OPT_HAMMING_KERNEL (match.hip: 0 = matrix-core form, 1 = VALU form)
 int opt_ba_graph();
