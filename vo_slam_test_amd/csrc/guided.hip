@@ -897,9 +897,9 @@ struct vo_frames {
   FramesDev D{};
   CamDev cam{};
   float width = 640.f, height = 480.f;
-  vo::DevBuf b_x, b_y, b_angle, b_ur, b_depth, b_oct, b_desc, b_n, b_cs, b_ci, b_srec, b_sdesc;
+  vo::OwnedDevBuf b_x, b_y, b_angle, b_ur, b_depth, b_oct, b_desc, b_n, b_cs, b_ci, b_srec, b_sdesc;
   // matcher scratch (grow-only)
-  vo::DevBuf b_pool, b_rank, b_ovf, b_ovfr, b_qrec, b_used, b_best, b_asg, b_push, b_nm, b_err, b_sf;
+  vo::OwnedDevBuf b_pool, b_rank, b_ovf, b_ovfr, b_qrec, b_used, b_best, b_asg, b_push, b_nm, b_err, b_sf;
   size_t pool_stride = 0, replay_lds_attr = 0;
   float sf_host[16] = {0};  // scale factors last uploaded for vo_track_gather_dev
 };
@@ -927,6 +927,9 @@ int frames_alloc(vo_frames *h) {
   D.desc = h->b_desc.as<uint8_t>(), D.n = h->b_n.as<int>(), D.cell_start = h->b_cs.as<int>();
   D.cell_items = h->b_ci.as<unsigned short>();
   D.srec = h->b_srec.as<uint4>(), D.sdesc = h->b_sdesc.as<uint4>();
+  const size_t lds = (size_t)((h->cap + 15) & ~15) + (size_t)h->cap * 2;  // the replay kernel's, for a store this wide
+  if (lds > 48 * 1024)
+    VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_guided_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   return VO_OK;
 }
 
@@ -1033,21 +1036,11 @@ int vo_frames_create(vo_frames **out, int max_frames, int max_features) {
     return rc;
   }
   frames_set_bounds(h, 0.f, 0.f, 640.f, 480.f);
-  const size_t lds = (size_t)((h->cap + 15) & ~15) + (size_t)h->cap * 2;
-  if (lds > 48 * 1024)
-    VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_guided_replay, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   *out = h;
   return VO_OK;
 }
 
-void vo_frames_destroy(vo_frames *h) {
-  if (!h) return;
-  for (vo::DevBuf *b : {&h->b_x, &h->b_y, &h->b_angle, &h->b_ur, &h->b_depth, &h->b_oct, &h->b_desc, &h->b_n, &h->b_cs,
-                        &h->b_ci, &h->b_srec, &h->b_sdesc, &h->b_pool, &h->b_rank, &h->b_ovf, &h->b_ovfr, &h->b_qrec, &h->b_used, &h->b_best, &h->b_asg, &h->b_push,
-                        &h->b_nm, &h->b_err, &h->b_sf})
-    b->release();
-  delete h;
-}
+void vo_frames_destroy(vo_frames *h) { delete h; }
 
 int vo_frames_set_camera(vo_frames *h, const float intrinsics[5], const float dist_coef[5], float width, float height) {
   if (!h || !intrinsics || !(width > 0) || !(height > 0)) return VO_ERR_INVALID;

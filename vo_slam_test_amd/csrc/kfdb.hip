@@ -395,17 +395,11 @@ struct vo_kfdb {
   hipStream_t st = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // a query on a caller's stream (kfdb_query_reloc_on), created on first use
   // the database
-  vo::DevBuf kf_start, kf_words, kf_vals, nbr_n, nbr, post_cnt, post_start, post_tmp, post_kf;
+  vo::OwnedDevBuf kf_start, kf_words, kf_vals, nbr_n, nbr, post_cnt, post_start, post_tmp, post_kf;
   // per-query work slabs [max_batch][max_kf]
-  vo::DevBuf keys, order, grep, gsc, g_cnt, g_first, score, err;
+  vo::OwnedDevBuf keys, order, grep, gsc, g_cnt, g_first, score, err;
   // staging of the host forms (grow-only)
-  vo::DevBuf h_qs, h_qw, h_qv, h_stale, h_es, h_ex, h_ms, h_cs, h_cn, h_nc, h_cand;
-  void release() {
-    for (vo::DevBuf *b : {&kf_start, &kf_words, &kf_vals, &nbr_n, &nbr, &post_cnt, &post_start, &post_tmp, &post_kf, &keys, &order,
-                          &grep, &gsc, &g_cnt, &g_first, &score, &err, &h_qs, &h_qw, &h_qv, &h_stale, &h_es, &h_ex, &h_ms, &h_cs,
-                          &h_cn, &h_nc, &h_cand})
-      b->release();
-  }
+  vo::OwnedDevBuf h_qs, h_qw, h_qv, h_stale, h_es, h_ex, h_ms, h_cs, h_cn, h_nc, h_cand;
 };
 
 namespace {
@@ -689,7 +683,6 @@ int vo_kfdb_create(vo_kfdb **out, int n_words, int max_keyframes, int max_words_
     rc = VO_ERR_HIP;
   }
   if (rc != VO_OK) {
-    db->release();
     delete db;
     return rc;
   }
@@ -702,7 +695,6 @@ void vo_kfdb_destroy(vo_kfdb *db) {
   (void)hipStreamSynchronize(db->st);
   if (db->ev_in) (void)hipEventDestroy(db->ev_in);
   if (db->ev_out) (void)hipEventDestroy(db->ev_out);
-  db->release();
   delete db;
 }
 

@@ -25,8 +25,8 @@ struct vo_kfstore {
   hipStream_t st = nullptr;
   hipEvent_t ev_in = nullptr, ev_out = nullptr;
   vo::KfStoreView V{};
-  vo::DevBuf rec;
-  vo::PinnedBuf stage;
+  vo::OwnedDevBuf rec;
+  vo::OwnedPinnedBuf stage;
   std::vector<int> n;  // features per key-frame (host copy: update_points' lengths)
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
@@ -104,7 +104,6 @@ void vo_kfstore_destroy(vo_kfstore *s) {
   if (!s) return;
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
   if (s->ev_out) (void)hipEventDestroy(s->ev_out);
-  s->rec.release();
   delete s;
 }
 

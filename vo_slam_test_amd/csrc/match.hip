@@ -859,7 +859,7 @@ __global__ __launch_bounds__(256) void k_bow_transform(VocabDev V, int n, const 
 struct vo_vocab {
   VocabDev V{};
   int n_children = 0;
-  vo::DevBuf b_cs, b_ch, b_wid, b_desc, b_w;
+  vo::OwnedDevBuf b_cs, b_ch, b_wid, b_desc, b_w;
 };
 
 extern "C" {
@@ -887,7 +887,6 @@ int vo_vocab_create(vo_vocab **out, int n_nodes, int depth_L, const int32_t *chi
   if ((rc = up(v->b_cs, child_start, (size_t)(n_nodes + 1) * 4)) != VO_OK || (rc = up(v->b_ch, children, (size_t)n_children * 4)) != VO_OK ||
       (rc = up(v->b_wid, word_id, (size_t)n_nodes * 4)) != VO_OK || (rc = up(v->b_desc, node_desc, (size_t)n_nodes * 32)) != VO_OK ||
       (rc = up(v->b_w, node_weight, (size_t)n_nodes * 8)) != VO_OK) {
-    for (vo::DevBuf *b : {&v->b_cs, &v->b_ch, &v->b_wid, &v->b_desc, &v->b_w}) b->release();
     delete v;
     return rc;
   }
@@ -898,11 +897,7 @@ int vo_vocab_create(vo_vocab **out, int n_nodes, int depth_L, const int32_t *chi
   return VO_OK;
 }
 
-void vo_vocab_destroy(vo_vocab *v) {
-  if (!v) return;
-  for (vo::DevBuf *b : {&v->b_cs, &v->b_ch, &v->b_wid, &v->b_desc, &v->b_w}) b->release();
-  delete v;
-}
+void vo_vocab_destroy(vo_vocab *v) { delete v; }
 
 int vo_bow_transform(const vo_vocab *v, int n, const uint8_t *desc, int levelsup, int32_t *word_id, double *weight,
                      int32_t *node_id) {
@@ -971,7 +966,8 @@ int vo::bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int
   // Frame::computeBow (frame.cpp:248-253): the node of every feature at level L - levelsup, straight from the store's slots
   thread_local vo::ScratchBuf t_w, t_wt, t_node, t_img;
   thread_local vo::PinnedBuf t_stage, t_up;
-  vo::DevBuf &d_w = own ? own->w : t_w, &d_wt = own ? own->wt : t_wt, &d_node = own ? own->node : t_node, &d_img = own ? own->img : t_img;
+  using D = vo::DevBuf;
+  D &d_w = own ? (D &)own->w : t_w, &d_wt = own ? (D &)own->wt : t_wt, &d_node = own ? (D &)own->node : t_node, &d_img = own ? (D &)own->img : t_img;
   vo::PinnedBuf &stage = own ? own->stage : t_stage, &up = own ? own->up : t_up;
   const size_t N = (size_t)B * cap;
   const int NP = B * per;  // pairs: pair p searches frame p / per
@@ -1249,18 +1245,22 @@ int vo::bow_walk_reserve(vo::BowWalkBufs &b, int B, int cap, int per, int NK, hi
     return VO_ERR_CAPACITY;
   }
   const size_t N = (size_t)B * cap, P = (size_t)B * per;
-  VO_CHECK(b.w.reserve(N * 4));
-  VO_CHECK(b.wt.reserve(N * 8));
-  VO_CHECK(b.node.reserve(N * 4));
-  VO_CHECK(b.fv_nn.reserve((size_t)B * 4 + 64));
-  VO_CHECK(b.fv_node.reserve(N * 4));
-  VO_CHECK(b.fv_start.reserve((size_t)B * (cap + 1) * 4));
-  VO_CHECK(b.fv_feat.reserve(N * 4));
-  VO_CHECK(b.queries.reserve(P * NK * 16));
-  VO_CHECK(b.claims.reserve(P * NK * 16));
-  VO_CHECK(b.args.reserve(P * sizeof(NodeArgs)));
-  VO_CHECK(b.ones.reserve((size_t)cap + 64));
-  hipLaunchKernelGGL(k_fill_u8, dim3((cap + 255) / 256), dim3(256), 0, st, b.ones.as<uint8_t>(), cap, (uint8_t)1);
+  VO_CHECK(b.mem.build(
+      [&](vo::Arena &a) {
+        a.take(b.w, N * 4);
+        a.take(b.wt, N * 8);
+        a.take(b.node, N * 4);
+        a.take(b.fv_nn, (size_t)B * 4 + 64);
+        a.take(b.fv_node, N * 4);
+        a.take(b.fv_start, (size_t)B * (cap + 1) * 4);
+        a.take(b.fv_feat, N * 4);
+        a.take(b.queries, P * NK * 16);
+        a.take(b.claims, P * NK * 16);
+        a.take(b.args, P * sizeof(NodeArgs));
+        a.take(b.ones, (size_t)cap + 64);
+      },
+      "BoW search on resident frames"));
+  hipLaunchKernelGGL(k_fill_u8, dim3((cap + 255) / 256), dim3(256), 0, st, b.ones, cap, (uint8_t)1);
   VO_HIP_CHECK(hipGetLastError());
   b.B = B, b.cap = cap, b.per = per, b.NK = NK;
   return VO_OK;
@@ -1277,10 +1277,10 @@ int vo::bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int le
   const size_t N = (size_t)B * b.cap;
   // Frame::computeBow (frame.cpp:248-253), as bow_search_resident runs it
   hipLaunchKernelGGL(k_bow_transform, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, v->V, (int)N,
-                     reinterpret_cast<const uint32_t *>(fs.desc), levelsup, b.w.as<int>(), b.wt.as<double>(), b.node.as<int>());
+                     reinterpret_cast<const uint32_t *>(fs.desc), levelsup, b.w, b.wt, b.node);
   VO_HIP_CHECK(hipGetLastError());
   if (ev0) VO_HIP_CHECK(hipEventRecord(ev0, st));
-  FeatVecArgs A{fs.n, 0, b.cap, b.node.as<int>(), b.fv_nn.as<int>(), 1, b.fv_node.as<int>(), b.fv_start.as<int>(), b.fv_feat.as<int>()};
+  FeatVecArgs A{fs.n, 0, b.cap, b.node, b.fv_nn, 1, b.fv_node, b.fv_start, b.fv_feat};
   VO_CHECK(launch_featvec(A, B, st));
   if (ev1) VO_HIP_CHECK(hipEventRecord(ev1, st));
   return VO_OK;
@@ -1304,8 +1304,8 @@ int vo::bow_walk_replay(vo_frames *frames, int B, int per, const vo::KfStoreView
   BowWalkArgs A{};
   A.per = per, A.cap = b.cap, A.NK = b.NK, A.check_rot = check_rot, A.ratio = ratio, A.S = S, A.pair_kf = dev_pair_kf;
   A.fn = fs.n, A.fdesc = fs.desc, A.fangle = fs.angle;
-  A.fv_nn = b.fv_nn.as<int>(), A.fv_node = b.fv_node.as<int>(), A.fv_start = b.fv_start.as<int>(), A.fv_feat = b.fv_feat.as<uint32_t>();
-  A.queries = b.queries.as<int4>(), A.claims = b.claims.as<int4>(), A.args = b.args.as<NodeArgs>(), A.ones = b.ones.as<uint8_t>();
+  A.fv_nn = b.fv_nn, A.fv_node = b.fv_node, A.fv_start = b.fv_start, A.fv_feat = reinterpret_cast<const uint32_t *>(b.fv_feat);
+  A.queries = b.queries, A.claims = b.claims, A.args = reinterpret_cast<NodeArgs *>(b.args), A.ones = b.ones;
   A.match = dev_assigned, A.n_matches = dev_n_matches;
   if (ev0) VO_HIP_CHECK(hipEventRecord(ev0, st));
   hipLaunchKernelGGL(k_bow_walk, dim3((unsigned)NP), dim3(64), 0, st, A);
@@ -1314,7 +1314,7 @@ int vo::bow_walk_replay(vo_frames *frames, int B, int per, const vo::KfStoreView
   // (the frames' feature counts stay on the device: the taken[] / tmpb[] arrays are sized for the store's capacity)
   const size_t lds = (((size_t)b.cap + 15) & ~(size_t)15) * 5;
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
-  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)NP), dim3(64), lds, st, b.args.as<const NodeArgs>());
+  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)NP), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(b.args));
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }

@@ -41,18 +41,18 @@ struct RelocDev {
   const int *fn;
   const float *X, *Y, *UR;
   const int *OCT;
-  const float *sf;
+  float *sf;
   // candidates [B * MC][NK]
   const int *n_cand;      // [B]
-  const int *kf_n;        // [B * MC]
-  const uint8_t *kf_bad;  // [B * MC]
-  const uint8_t *kf_flags;
-  const double *kf_point;
-  const int *kf_id;
-  const float *kf_mind, *kf_maxd;
+  int *kf_n;              // [B * MC]
+  uint8_t *kf_bad;        // [B * MC]
+  uint8_t *kf_flags;
+  double *kf_point;
+  int *kf_id;
+  float *kf_mind, *kf_maxd;
   // front
-  const int *bow_assigned;  // [B * MC][cap]
-  const int *bow_n;         // [B * MC]
+  int *bow_assigned;  // [B * MC][cap]
+  int *bow_n;         // [B * MC]
   int *cnt, *off;           // [B * MC], [B * MC + 1]
   float *p3, *p2;
   int *src;
@@ -575,32 +575,98 @@ struct vo::Reloc {
   const vo_vocab *vocab = nullptr;
   bool have = false;
   std::vector<CandHost> cands;  // [B * MC] (host: the common-node walk reads them)
-  DevBuf sf, n_cand, kf_n, kf_bad, kf_flags, kf_point, kf_id, kf_pdesc, kf_mind, kf_maxd, kf_angle;
-  DevBuf bow_assigned, bow_n, cnt, off, p3, p2, src, pnp_T, pnp_mask, pnp_n, pnp_status, pnp_ws, dbg_mask;
-  DevBuf rec, fid, found, out_bow, out_pnp, out_code, nq, qflags, qu, qv, qlevel, ninl_solve, winner;
+  // The arrays, all sized from (B, cap, MC, NK) when the object is created: one block, laid out by layout().  `d` is the
+  // kernels' view with this object's half filled in for good (reloc_dev adds the call's half); the arrays that no kernel reads
+  // through RelocDev follow it.
+  Arena mem;
+  RelocDev d{};
+  int *n_cand = nullptr, *winner = nullptr;  // [B] the counts vo_tracker_set_reloc_candidates uploaded; [B] k_reloc_finish's
+  uint8_t *kf_pdesc = nullptr, *pnp_ws = nullptr;
+  float *kf_angle = nullptr;
+  size_t pnp_ws_bytes = 0;
+  void layout(Arena &a);
   BowResidentBufs bow;
-  PinnedBuf stage;
-  // the store routes: sized by reloc_store_prepare on their first call
+  OwnedPinnedBuf stage;
+  // the store routes: their arrays are laid out by reloc_store_prepare on the first call of a store route (`s`: nc .. err and
+  // the candidate arrays are set then, the rest per call), the database query's on the first call with a database
   bool store_ready = false, store_db = false, last_store = false;
   int ids_lds_slots = 0, ids_gstride = 0;
   BowWalkBufs walk;
-  DevBuf s_nc, s_nc_true, s_walked, s_pair_kf, s_l2g, s_fid_g, s_err, s_keys;
-  DevBuf q_fstart, q_w, q_wt, q_bstart, q_bw, q_bv, q_nc, q_cand;  // the database query
-  std::vector<DevBuf *> all() {
-    std::vector<DevBuf *> v = base();
-    for (DevBuf *b : walk.all()) v.push_back(b);
-    for (DevBuf *b : {&s_nc, &s_nc_true, &s_walked, &s_pair_kf, &s_l2g, &s_fid_g, &s_err, &s_keys, &q_fstart, &q_w, &q_wt, &q_bstart,
-                      &q_bw, &q_bv, &q_nc, &q_cand})
-      v.push_back(b);
-    return v;
-  }
-  std::vector<DevBuf *> base() {
-    return {&sf, &n_cand, &kf_n, &kf_bad, &kf_flags, &kf_point, &kf_id, &kf_pdesc, &kf_mind, &kf_maxd, &kf_angle, &bow_assigned,
-            &bow_n, &cnt, &off, &p3, &p2, &src, &pnp_T, &pnp_mask, &pnp_n, &pnp_status, &pnp_ws, &dbg_mask, &rec, &fid, &found,
-            &out_bow, &out_pnp, &out_code, &nq, &qflags, &qu, &qv, &qlevel, &ninl_solve, &winner, &bow.w, &bow.wt, &bow.node,
-            &bow.img};
-  }
+  Arena store_mem, db_mem;
+  StoreDev s{};
+  unsigned long long *s_keys = nullptr;
+  struct {
+    int *fstart, *w, *bstart, *bw, *nc, *cand;
+    double *wt, *bv;
+  } q{};
+  void layout_store(Arena &a);
+  void layout_db(Arena &a);
 };
+
+void vo::Reloc::layout(Arena &a) {
+  const size_t P = (size_t)B * MC, PK = P * NK, PC = P * cap, Bc = (size_t)B * cap;
+  a.take(d.sf, 64);
+  a.take(n_cand, B * 4 + 64);
+  a.take(d.kf_n, P * 4 + 64);
+  a.take(d.kf_bad, P + 64);
+  a.take(d.kf_flags, PK);
+  a.take(d.kf_point, PK * 24);
+  a.take(d.kf_id, PK * 4);
+  a.take(kf_pdesc, PK * 32);
+  a.take(d.kf_mind, PK * 4);
+  a.take(d.kf_maxd, PK * 4);
+  a.take(kf_angle, PK * 4);
+  a.take(d.bow_assigned, PC * 4);
+  a.take(d.bow_n, P * 4 + 64);
+  a.take(d.cnt, P * 4 + 64);
+  a.take(d.off, P * 4 + 64);
+  a.take(d.p3, PC * 12);
+  a.take(d.p2, PC * 8);
+  a.take(d.src, PC * 4);
+  a.take(d.pnp_T, P * 96);
+  a.take(d.pnp_mask, PC);
+  a.take(d.pnp_n, P * 4 + 64);
+  a.take(d.pnp_status, P * 4 + 64);
+  a.take(pnp_ws, pnp_ws_bytes = vo_pnp_workspace_bytes((int)P, 100));
+  a.take(d.dbg_mask, PC);
+  a.take(d.rec, (size_t)B * kRecInts * 4);
+  a.take(d.fid, Bc * 4);
+  a.take(d.found, PK);
+  a.take(d.out_bow, P * 4);
+  a.take(d.out_pnp, P * 4);
+  a.take(d.out_code, P * 4);
+  a.take(d.nq, B * 4 + 64);
+  a.take(d.qflags, PK);
+  a.take(d.qu, PK * 4);
+  a.take(d.qv, PK * 4);
+  a.take(d.qlevel, PK * 4);
+  a.take(d.ninl_solve, B * 4 + 64);
+  a.take(winner, B * 4 + 64);
+}
+
+void vo::Reloc::layout_store(Arena &a) {
+  const size_t P = (size_t)B * MC, PK = P * NK, Bc = (size_t)B * cap;
+  a.take(s.nc, B * 4 + 64);
+  a.take(s.nc_true, B * 4 + 64);
+  a.take(s.walked, P * 4 + 64);
+  a.take(s.pair_kf, P * 4 + 64);
+  a.take(s.l2g, PK * 4);
+  a.take(s.fid_g, Bc * 4);
+  a.take(s.err, 64);
+  if (ids_gstride) a.take(s_keys, (size_t)B * ids_gstride * 8);  // (the id compaction's keys, when they do not fit in LDS)
+}
+
+void vo::Reloc::layout_db(Arena &a) {
+  const size_t P = (size_t)B * MC, Bc = (size_t)B * cap;
+  a.take(q.fstart, B * 4 + 64);
+  a.take(q.w, Bc * 4);
+  a.take(q.wt, Bc * 8);
+  a.take(q.bstart, B * 4 + 64);
+  a.take(q.bw, Bc * 4);
+  a.take(q.bv, Bc * 8);
+  a.take(q.nc, B * 4 + 64);
+  a.take(q.cand, P * 4 + 64);
+}
 
 namespace {
 RelocDev reloc_dev(vo::Reloc *r, const vo::RelocShared &S, const int *n_cand);
@@ -620,51 +686,15 @@ int reloc_create(Reloc **out, int B, int cap, int max_cand, int max_feat, const 
   if (!r) return VO_ERR_HIP;
   r->B = B, r->cap = cap, r->MC = max_cand, r->NK = max_feat, r->n_levels = n_levels;
   memcpy(r->sf_host, sf, (size_t)n_levels * 4);
-  const size_t P = (size_t)B * max_cand, PK = P * max_feat, PC = P * cap, Bc = (size_t)B * cap;
-  auto alloc = [&]() -> int {
-    VO_CHECK(r->sf.reserve(64));
-    VO_CHECK(r->n_cand.reserve(B * 4 + 64));
-    VO_CHECK(r->kf_n.reserve(P * 4 + 64));
-    VO_CHECK(r->kf_bad.reserve(P + 64));
-    VO_CHECK(r->kf_flags.reserve(PK));
-    VO_CHECK(r->kf_point.reserve(PK * 24));
-    VO_CHECK(r->kf_id.reserve(PK * 4));
-    VO_CHECK(r->kf_pdesc.reserve(PK * 32));
-    VO_CHECK(r->kf_mind.reserve(PK * 4));
-    VO_CHECK(r->kf_maxd.reserve(PK * 4));
-    VO_CHECK(r->kf_angle.reserve(PK * 4));
-    VO_CHECK(r->bow_assigned.reserve(PC * 4));
-    VO_CHECK(r->bow_n.reserve(P * 4 + 64));
-    VO_CHECK(r->cnt.reserve(P * 4 + 64));
-    VO_CHECK(r->off.reserve(P * 4 + 64));
-    VO_CHECK(r->p3.reserve(PC * 12));
-    VO_CHECK(r->p2.reserve(PC * 8));
-    VO_CHECK(r->src.reserve(PC * 4));
-    VO_CHECK(r->pnp_T.reserve(P * 96));
-    VO_CHECK(r->pnp_mask.reserve(PC));
-    VO_CHECK(r->pnp_n.reserve(P * 4 + 64));
-    VO_CHECK(r->pnp_status.reserve(P * 4 + 64));
-    VO_CHECK(r->pnp_ws.reserve(vo_pnp_workspace_bytes((int)P, 100)));
-    VO_CHECK(r->dbg_mask.reserve(PC));
-    VO_CHECK(r->rec.reserve((size_t)B * kRecInts * 4));
-    VO_CHECK(r->fid.reserve(Bc * 4));
-    VO_CHECK(r->found.reserve(PK));
-    VO_CHECK(r->out_bow.reserve(P * 4));
-    VO_CHECK(r->out_pnp.reserve(P * 4));
-    VO_CHECK(r->out_code.reserve(P * 4));
-    VO_CHECK(r->nq.reserve(B * 4 + 64));
-    VO_CHECK(r->qflags.reserve(PK));
-    VO_CHECK(r->qu.reserve(PK * 4));
-    VO_CHECK(r->qv.reserve(PK * 4));
-    VO_CHECK(r->qlevel.reserve(PK * 4));
-    VO_CHECK(r->ninl_solve.reserve(B * 4 + 64));
-    VO_CHECK(r->winner.reserve(B * 4 + 64));
+  r->d.B = B, r->d.cap = cap, r->d.MC = max_cand, r->d.NK = max_feat;
+  auto fill = [&]() -> int {
+    VO_CHECK(r->mem.build([&](Arena &a) { r->layout(a); }, "relocalisation route"));
     float sf16[16] = {0};
     memcpy(sf16, sf, (size_t)n_levels * 4);
-    VO_HIP_CHECK(hipMemcpy(r->sf.p, sf16, 64, hipMemcpyHostToDevice));
+    VO_HIP_CHECK(hipMemcpy(r->d.sf, sf16, 64, hipMemcpyHostToDevice));
     return VO_OK;
   };
-  const int rc = alloc();
+  const int rc = fill();
   if (rc != VO_OK) {
     reloc_destroy(r);
     return rc;
@@ -673,11 +703,7 @@ int reloc_create(Reloc **out, int B, int cap, int max_cand, int max_feat, const 
   return VO_OK;
 }
 
-void reloc_destroy(Reloc *r) {
-  if (!r) return;
-  for (DevBuf *b : r->all()) b->release();
-  delete r;
-}
+void reloc_destroy(Reloc *r) { delete r; }
 
 int reloc_set_candidates(Reloc *r, const vo_vocab *vocab, int max_cand, const int32_t *n_cand, const vo_reloc_candidate *cands,
                          hipStream_t st) {
@@ -760,19 +786,19 @@ int reloc_set_candidates(Reloc *r, const vo_vocab *vocab, int max_cand, const in
       H.view.n_nodes = v->n_nodes, H.view.node_id = reinterpret_cast<const uint32_t *>(H.node_id.data());
       H.view.start = H.start.data(), H.view.feat = H.feat.data();
     }
-  auto up = [&](DevBuf &d, size_t off, size_t bytes) -> int {
-    VO_HIP_CHECK(hipMemcpyAsync(d.p, h + off, bytes, hipMemcpyHostToDevice, st));
+  auto up = [&](void *d, size_t off, size_t bytes) -> int {
+    VO_HIP_CHECK(hipMemcpyAsync(d, h + off, bytes, hipMemcpyHostToDevice, st));
     return VO_OK;
   };
   VO_CHECK(up(r->n_cand, o_nc, (size_t)B * 4));
-  VO_CHECK(up(r->kf_n, o_n, P * 4));
-  VO_CHECK(up(r->kf_bad, o_bad, P));
-  VO_CHECK(up(r->kf_flags, o_fl, PK));
-  VO_CHECK(up(r->kf_id, o_id, PK * 4));
-  VO_CHECK(up(r->kf_mind, o_mind, PK * 4));
-  VO_CHECK(up(r->kf_maxd, o_maxd, PK * 4));
+  VO_CHECK(up(r->d.kf_n, o_n, P * 4));
+  VO_CHECK(up(r->d.kf_bad, o_bad, P));
+  VO_CHECK(up(r->d.kf_flags, o_fl, PK));
+  VO_CHECK(up(r->d.kf_id, o_id, PK * 4));
+  VO_CHECK(up(r->d.kf_mind, o_mind, PK * 4));
+  VO_CHECK(up(r->d.kf_maxd, o_maxd, PK * 4));
   VO_CHECK(up(r->kf_angle, o_ang, PK * 4));
-  VO_CHECK(up(r->kf_point, o_pt, PK * 24));
+  VO_CHECK(up(r->d.kf_point, o_pt, PK * 24));
   VO_CHECK(up(r->kf_pdesc, o_pd, PK * 32));
   VO_HIP_CHECK(hipStreamSynchronize(st));  // the caller's arrays and the staging block are free again
   r->vocab = vocab;
@@ -794,10 +820,10 @@ int reloc_run(Reloc *r, const RelocShared &S) {
     const CandHost &k = r->cands[p];
     kfs[p] = RefKeyFrame{k.n, k.valid.data(), k.desc.data(), k.angle.data(), &k.view};
   }
-  VO_CHECK(bow_search_resident(r->vocab, S.frames, 0, B, kfs.data(), 0.75f, 1, 3, r->bow_assigned.as<int32_t>(), r->cap,
-                               r->bow_n.as<int32_t>(), st, MC, &r->bow));
+  VO_CHECK(bow_search_resident(r->vocab, S.frames, 0, B, kfs.data(), 0.75f, 1, 3, r->d.bow_assigned, r->cap, r->d.bow_n, st, MC,
+                               &r->bow));
   r->last_store = false;
-  const RelocDev D = reloc_dev(r, S, r->n_cand.as<int>());
+  const RelocDev D = reloc_dev(r, S, r->n_cand);
   return reloc_tail(r, S, D);
 }
 
@@ -805,24 +831,13 @@ int reloc_run(Reloc *r, const RelocShared &S) {
 
 namespace {
 
-// the device view of a route: the Reloc object's arrays and the tracker's (n_cand: the per-frame counts the walk obeys)
+// the device view of a route: the Reloc object's arrays (set when it was created) and the call's -- the per-frame counts the
+// walk obeys, the frame store, the tracker's arrays
 RelocDev reloc_dev(vo::Reloc *r, const vo::RelocShared &S, const int *n_cand) {
   const vo::FrameStoreView fs = vo::frame_store_view(S.frames);
-  const int B = r->B, MC = r->MC, NK = r->NK;
-  RelocDev D{};
-  D.B = B, D.cap = r->cap, D.MC = MC, D.NK = NK;
-  D.fn = fs.n, D.X = fs.x, D.Y = fs.y, D.UR = fs.uright, D.OCT = fs.octave, D.sf = r->sf.as<float>();
-  D.n_cand = n_cand, D.kf_n = r->kf_n.as<int>(), D.kf_bad = r->kf_bad.as<uint8_t>();
-  D.kf_flags = r->kf_flags.as<uint8_t>(), D.kf_point = r->kf_point.as<double>(), D.kf_id = r->kf_id.as<int>();
-  D.kf_mind = r->kf_mind.as<float>(), D.kf_maxd = r->kf_maxd.as<float>();
-  D.bow_assigned = r->bow_assigned.as<int>(), D.bow_n = r->bow_n.as<int>(), D.cnt = r->cnt.as<int>(), D.off = r->off.as<int>();
-  D.p3 = r->p3.as<float>(), D.p2 = r->p2.as<float>(), D.src = r->src.as<int>(), D.pnp_T = r->pnp_T.as<double>();
-  D.pnp_mask = r->pnp_mask.as<uint8_t>(), D.pnp_n = r->pnp_n.as<int>(), D.pnp_status = r->pnp_status.as<int>();
-  D.dbg_mask = r->dbg_mask.as<uint8_t>();
-  D.rec = r->rec.as<int>(), D.fid = r->fid.as<int>(), D.found = r->found.as<uint8_t>();
-  D.out_bow = r->out_bow.as<int>(), D.out_pnp = r->out_pnp.as<int>(), D.out_code = r->out_code.as<int>();
-  D.nq = r->nq.as<int>(), D.qflags = r->qflags.as<uint8_t>(), D.qu = r->qu.as<float>(), D.qv = r->qv.as<float>();
-  D.qlevel = r->qlevel.as<int>(), D.ninl_solve = r->ninl_solve.as<int>();
+  RelocDev D = r->d;
+  D.fn = fs.n, D.X = fs.x, D.Y = fs.y, D.UR = fs.uright, D.OCT = fs.octave;
+  D.n_cand = n_cand;
   D.pose = S.pose, D.fpoint = S.fpoint, D.fhas = S.fhas, D.foutl = S.foutl, D.pts = S.pts, D.obs = S.obs, D.isg = S.isg;
   D.ranges = S.ranges, D.index = S.index, D.outlier = S.outlier, D.assigned = S.assigned, D.nm = S.nm;
   return D;
@@ -838,7 +853,7 @@ int reloc_tail(vo::Reloc *r, const vo::RelocShared &S, const RelocDev &D) {
   hipLaunchKernelGGL(k_reloc_gather, dim3(P), dim3(256), 0, st, D);
   VO_HIP_CHECK(hipGetLastError());
   VO_CHECK(vo_pnp_ransac_dev(P, D.off, D.p3, D.p2, S.cam5, 100, 8.0f, 0.99, D.pnp_T, D.pnp_mask, D.pnp_n, D.pnp_status, nullptr,
-                             r->pnp_ws.p, r->pnp_ws.bytes, st));
+                             r->pnp_ws, r->pnp_ws_bytes, st));
   hipLaunchKernelGGL(k_reloc_pnp_mask, dim3(P), dim3(256), 0, st, D);
   // ---- dependent tail
   vo_guided_queries q{};
@@ -855,7 +870,7 @@ int reloc_tail(vo::Reloc *r, const vo::RelocShared &S, const RelocDev &D) {
     VO_HIP_CHECK(hipGetLastError());
     const size_t ro = (size_t)rd * NK;  // query q of frame f = feature q of pair f * MC + rd: stride MC * NK from here
     q.flags = D.qflags + ro, q.u = D.qu + ro, q.v = D.qv + ro, q.level = D.qlevel + ro;
-    q.angle = r->kf_angle.as<float>() + ro, q.desc = r->kf_pdesc.as<uint8_t>() + ro * 32;
+    q.angle = r->kf_angle + ro, q.desc = r->kf_pdesc + ro * 32;
     gp.radius = radius, gp.dist_threshold = dist_threshold;
     VO_CHECK(vo_match_guided_dev(S.frames, 0, B, &q, &gp, S.fhas, S.assigned, nullptr, S.nm, 0, st));
     hipLaunchKernelGGL(k_reloc_after_search, dim3(B), dim3(256), 0, st, D, rd, which);
@@ -875,8 +890,7 @@ int reloc_tail(vo::Reloc *r, const vo::RelocShared &S, const RelocDev &D) {
     hipLaunchKernelGGL(k_reloc_after_solve, dim3(B), dim3(256), 0, st, D, rd, 3);
     VO_HIP_CHECK(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_reloc_finish, dim3((B + 255) / 256), dim3(256), 0, st, D, r->winner.as<int>(), S.resblk, S.orb_err,
-                     S.guided_err);
+  hipLaunchKernelGGL(k_reloc_finish, dim3((B + 255) / 256), dim3(256), 0, st, D, r->winner, S.resblk, S.orb_err, S.guided_err);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
@@ -889,14 +903,14 @@ const void *reloc_selector(const Reloc *r, int what, size_t *bytes) {
   if (!r) return nullptr;
   const size_t B = r->B, P = B * r->MC;
   switch (what) {
-    case VO_TRACKER_RELOC_WINNER: *bytes = B * 4; return r->winner.p;
-    case VO_TRACKER_RELOC_POINT_IDS: *bytes = B * r->cap * 4; return r->last_store ? r->s_fid_g.p : r->fid.p;
-    case VO_TRACKER_RELOC_BOW_MATCHES: *bytes = P * 4; return r->out_bow.p;
-    case VO_TRACKER_RELOC_PNP_INLIERS: *bytes = P * 4; return r->out_pnp.p;
-    case VO_TRACKER_RELOC_OUTCOME: *bytes = P * 4; return r->out_code.p;
-    case VO_TRACKER_RELOC_PNP_MASK: *bytes = P * r->cap; return r->dbg_mask.p;
-    case VO_TRACKER_RELOC_CANDIDATES: *bytes = P * 4; return r->last_store ? r->s_walked.p : nullptr;
-    case VO_TRACKER_RELOC_N_CANDIDATES: *bytes = B * 4; return r->last_store ? r->s_nc_true.p : nullptr;
+    case VO_TRACKER_RELOC_WINNER: *bytes = B * 4; return r->winner;
+    case VO_TRACKER_RELOC_POINT_IDS: *bytes = B * r->cap * 4; return r->last_store ? r->s.fid_g : r->d.fid;
+    case VO_TRACKER_RELOC_BOW_MATCHES: *bytes = P * 4; return r->d.out_bow;
+    case VO_TRACKER_RELOC_PNP_INLIERS: *bytes = P * 4; return r->d.out_pnp;
+    case VO_TRACKER_RELOC_OUTCOME: *bytes = P * 4; return r->d.out_code;
+    case VO_TRACKER_RELOC_PNP_MASK: *bytes = P * r->cap; return r->d.dbg_mask;
+    case VO_TRACKER_RELOC_CANDIDATES: *bytes = P * 4; return r->last_store ? r->s.walked : nullptr;
+    case VO_TRACKER_RELOC_N_CANDIDATES: *bytes = B * 4; return r->last_store ? r->s.nc_true : nullptr;
     default: return nullptr;
   }
 }
@@ -904,17 +918,8 @@ const void *reloc_selector(const Reloc *r, int what, size_t *bytes) {
 // ---- the store routes ------------------------------------------------------------------------------------------
 int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st) {
   if (!r) return VO_ERR_INVALID;
-  const size_t B = r->B, P = B * r->MC, PK = P * r->NK, Bc = B * r->cap;
   if (!r->store_ready) {
     VO_CHECK(bow_walk_reserve(r->walk, r->B, r->cap, r->MC, r->NK, st));
-    VO_CHECK(r->s_nc.reserve(B * 4 + 64));
-    VO_CHECK(r->s_nc_true.reserve(B * 4 + 64));
-    VO_CHECK(r->s_walked.reserve(P * 4 + 64));
-    VO_CHECK(r->s_pair_kf.reserve(P * 4 + 64));
-    VO_CHECK(r->s_l2g.reserve(PK * 4));
-    VO_CHECK(r->s_fid_g.reserve(Bc * 4));
-    VO_CHECK(r->s_err.reserve(64));
-    VO_HIP_CHECK(hipMemsetAsync(r->s_err.p, 0, 64, st));
     // the id compaction sorts the power of two above MC * NK keys per frame: in LDS up to 128 KiB, else in a slab
     const int np2 = pow2_ceil(r->MC * r->NK);
     if ((size_t)np2 * 8 <= 128 * 1024) {
@@ -923,19 +928,17 @@ int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st) {
         VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_reloc_local_ids, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
     } else {
       r->ids_lds_slots = 0, r->ids_gstride = np2;
-      VO_CHECK(r->s_keys.reserve(B * (size_t)np2 * 8));
     }
+    VO_CHECK(r->store_mem.build([&](Arena &a) { r->layout_store(a); }, "store route"));
+    VO_HIP_CHECK(hipMemsetAsync(r->s.err, 0, 64, st));
+    // the candidate arrays the gather writes in place of vo_tracker_set_reloc_candidates
+    StoreDev &T = r->s;
+    T.kf_n = r->d.kf_n, T.kf_bad = r->d.kf_bad, T.kf_flags = r->d.kf_flags, T.kf_point = r->d.kf_point, T.kf_id = r->d.kf_id;
+    T.kf_pdesc = r->kf_pdesc, T.kf_mind = r->d.kf_mind, T.kf_maxd = r->d.kf_maxd, T.kf_angle = r->kf_angle;
     r->store_ready = true;
   }
   if (with_db && !r->store_db) {
-    VO_CHECK(r->q_fstart.reserve(B * 4 + 64));
-    VO_CHECK(r->q_w.reserve(Bc * 4));
-    VO_CHECK(r->q_wt.reserve(Bc * 8));
-    VO_CHECK(r->q_bstart.reserve(B * 4 + 64));
-    VO_CHECK(r->q_bw.reserve(Bc * 4));
-    VO_CHECK(r->q_bv.reserve(Bc * 8));
-    VO_CHECK(r->q_nc.reserve(B * 4 + 64));
-    VO_CHECK(r->q_cand.reserve(P * 4 + 64));
+    VO_CHECK(r->db_mem.build([&](Arena &a) { r->layout_db(a); }, "store route with a database"));
     r->store_db = true;
   }
   return VO_OK;
@@ -960,38 +963,31 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
   const int *n_cand = A.dev_n_cand, *cand = A.dev_cand;
   int stride = A.cand_stride;
   if (A.db) {
-    hipLaunchKernelGGL(k_reloc_word_start, dim3(1), dim3(256), 0, st, B, r->cap, fs.n, r->q_fstart.as<int>());
-    hipLaunchKernelGGL(k_reloc_word_pack, dim3(B), dim3(256), 0, st, r->cap, fs.n, (const int *)r->q_fstart.as<int>(),
-                       (const int *)r->walk.w.as<int>(), (const double *)r->walk.wt.as<double>(), r->q_w.as<int>(), r->q_wt.as<double>());
+    hipLaunchKernelGGL(k_reloc_word_start, dim3(1), dim3(256), 0, st, B, r->cap, fs.n, r->q.fstart);
+    hipLaunchKernelGGL(k_reloc_word_pack, dim3(B), dim3(256), 0, st, r->cap, fs.n, (const int *)r->q.fstart, (const int *)r->walk.w,
+                       (const double *)r->walk.wt, r->q.w, r->q.wt);
     VO_HIP_CHECK(hipGetLastError());
-    VO_CHECK(vo_bow_vector_dev(B, B * r->cap, r->q_fstart.as<int>(), r->q_w.as<int>(), r->q_wt.as<double>(), r->q_bstart.as<int>(),
-                               r->q_bw.as<int>(), r->q_bv.as<double>(), st));
-    VO_CHECK(kfdb_query_reloc_on(A.db, st, B, r->q_bstart.as<int>(), r->q_bw.as<int>(), r->q_bv.as<double>(), A.dev_stale, MC,
-                                 r->q_nc.as<int>(), r->q_cand.as<int>()));
-    n_cand = r->q_nc.as<int>(), cand = r->q_cand.as<int>(), stride = MC;
+    VO_CHECK(vo_bow_vector_dev(B, B * r->cap, r->q.fstart, r->q.w, r->q.wt, r->q.bstart, r->q.bw, r->q.bv, st));
+    VO_CHECK(kfdb_query_reloc_on(A.db, st, B, r->q.bstart, r->q.bw, r->q.bv, A.dev_stale, MC, r->q.nc, r->q.cand));
+    n_cand = r->q.nc, cand = r->q.cand, stride = MC;
   }
   // ---- the candidates out of the store, their ids made dense
   VO_CHECK(kfstore_order_before(A.store, st));
-  const RelocDev D = reloc_dev(r, S, r->s_nc.as<int>());
-  StoreDev T{};
+  const RelocDev D = reloc_dev(r, S, r->s.nc);
+  StoreDev T = r->s;
   T.S = kfstore_view(A.store), T.n_cand_in = n_cand, T.cand_in = cand, T.cand_stride = stride;
-  T.nc = r->s_nc.as<int>(), T.nc_true = r->s_nc_true.as<int>(), T.walked = r->s_walked.as<int>(), T.pair_kf = r->s_pair_kf.as<int>();
-  T.kf_n = r->kf_n.as<int>(), T.kf_bad = r->kf_bad.as<uint8_t>(), T.kf_flags = r->kf_flags.as<uint8_t>();
-  T.kf_point = r->kf_point.as<double>(), T.kf_id = r->kf_id.as<int>(), T.kf_pdesc = r->kf_pdesc.as<uint8_t>();
-  T.kf_mind = r->kf_mind.as<float>(), T.kf_maxd = r->kf_maxd.as<float>(), T.kf_angle = r->kf_angle.as<float>();
-  T.l2g = r->s_l2g.as<int>(), T.fid_g = r->s_fid_g.as<int>(), T.err = r->s_err.as<int>();
   VO_CHECK(mark(2));
   hipLaunchKernelGGL(k_kfstore_gather, dim3(P), dim3(256), 0, st, D, T);
   VO_HIP_CHECK(hipGetLastError());
   VO_CHECK(mark(3));
   VO_CHECK(mark(4));
   hipLaunchKernelGGL(k_reloc_local_ids, dim3(B), dim3(256), (size_t)r->ids_lds_slots * 8, st, MC, NK, (const int *)T.nc,
-                     (const int *)T.kf_n, (const uint8_t *)T.kf_flags, T.kf_id, T.l2g, r->s_keys.as<unsigned long long>(),
+                     (const int *)T.kf_n, (const uint8_t *)T.kf_flags, T.kf_id, T.l2g, r->s_keys,
                      r->ids_gstride, r->ids_lds_slots);
   VO_HIP_CHECK(hipGetLastError());
   VO_CHECK(mark(5));
   // ---- searchByBoW of every pair: the common-node walk and the replay
-  VO_CHECK(bow_walk_replay(S.frames, B, MC, T.S, T.pair_kf, 0.75f, 1, r->walk, r->bow_assigned.as<int32_t>(), r->bow_n.as<int32_t>(), st,
+  VO_CHECK(bow_walk_replay(S.frames, B, MC, T.S, T.pair_kf, 0.75f, 1, r->walk, D.bow_assigned, D.bow_n, st,
                            ev ? ev[6] : nullptr, ev ? ev[7] : nullptr));
   VO_CHECK(reloc_tail(r, S, D));
   hipLaunchKernelGGL(k_reloc_store_finish, dim3(B), dim3(256), 0, st, D, T, S.resblk);
@@ -999,7 +995,7 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
   return kfstore_order_after(A.store, st);
 }
 
-const int *reloc_store_error_flag(const Reloc *r) { return r && r->store_ready ? r->s_err.as<int>() : nullptr; }
+const int *reloc_store_error_flag(const Reloc *r) { return r && r->store_ready ? r->s.err : nullptr; }
 bool reloc_last_was_store(const Reloc *r) { return r && r->last_store; }
 
 }  // namespace vo

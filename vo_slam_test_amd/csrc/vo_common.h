@@ -89,6 +89,56 @@ struct PinnedBuf {
   uint8_t *data() const { return reinterpret_cast<uint8_t *>(p); }
 };
 
+// ---- memory of a handle: freed when the handle is deleted, after its streams have drained.  The
+// types above stay as they are for per-thread and static scratch, which is never freed.
+struct OwnedDevBuf : DevBuf {
+  OwnedDevBuf() = default;
+  OwnedDevBuf(const OwnedDevBuf &) = delete;
+  OwnedDevBuf &operator=(const OwnedDevBuf &) = delete;
+  ~OwnedDevBuf() { release(); }
+};
+struct OwnedPinnedBuf : PinnedBuf {
+  OwnedPinnedBuf() = default;
+  OwnedPinnedBuf(const OwnedPinnedBuf &) = delete;
+  OwnedPinnedBuf &operator=(const OwnedPinnedBuf &) = delete;
+  ~OwnedPinnedBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+};
+
+// One device block for a set of arrays whose sizes are fixed when the set is created.  A layout function names every
+// array once -- take(field of the handle's view struct, bytes) -- and build() runs it twice: the first pass measures, one
+// hipMalloc follows, the second pass hands out the addresses.  Every array starts on a 4 KiB boundary (no less aligned
+// than an allocation of its own); its byte count, slack included, is the caller's.
+struct Arena {
+  uint8_t *block = nullptr;
+  size_t bytes = 0, at = 0;
+  Arena() = default;
+  Arena(const Arena &) = delete;
+  Arena &operator=(const Arena &) = delete;
+  ~Arena() {
+    if (block) (void)hipFree(block);
+  }
+  template <class T>
+  void take(T *&field, size_t n) {
+    field = block ? reinterpret_cast<T *>(block + at) : nullptr;
+    at += (n + 4095) & ~(size_t)4095;
+  }
+  template <class Layout>
+  int build(Layout &&layout, const char *what) {
+    if (block) (void)hipFree(block);  // (a set laid out again, e.g. after a failed first attempt)
+    block = nullptr, at = 0, layout(*this);
+    const size_t need = at;
+    VO_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&block), need ? need : 4096));
+    bytes = need, at = 0, layout(*this);
+    if (at != need) {  // the two passes disagree: an array would overlap its neighbour
+      set_error("%s: the array layout measured %zu bytes and assigned %zu", what, need, at);
+      return VO_ERR_HIP;
+    }
+    return VO_OK;
+  }
+};
+
 constexpr int kWave = 64;
 
 // Per host thread: a non-blocking stream for the stateless entry points (vo_hamming_matrix, vo_pose_only_solve,
@@ -155,9 +205,9 @@ struct RefKeyFrame {
 // owns dev_assigned [p][cap], dev_n_matches [p]; a pair with n == 0 matches nothing.  With `own` the call works in the
 // caller's buffers instead of the calling thread's and does NOT synchronise at its end: the caller must not call again
 // before the stream has drained (the synchronisation up front does that for calls on the same stream).
-struct BowResidentBufs {
-  DevBuf w, wt, node, img;
-  PinnedBuf stage, up;
+struct BowResidentBufs {  // (a handle's: the calling thread's own set is bow_search_resident's)
+  OwnedDevBuf w, wt, node, img;
+  OwnedPinnedBuf stage, up;
 };
 int bow_search_resident(const vo_vocab *v, vo_frames *frames, int slot0, int B, const RefKeyFrame *kfs, float ratio, int check_rot,
                         int levelsup, int32_t *dev_assigned, int cap, int32_t *dev_n_matches, hipStream_t st, int per = 1,
@@ -241,10 +291,11 @@ int kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const int32_
 // argument block; k_node_replay runs as in bow_search_resident.  All buffers are sized once from (B, cap, per, NK).
 struct BowWalkBufs {
   int B = 0, cap = 0, per = 0, NK = 0;
-  DevBuf w, wt, node;                          // [B][cap] word, weight, node of every feature slot
-  DevBuf fv_nn, fv_node, fv_start, fv_feat;    // the frames' FeatureVectors: [B], [B][cap], [B][cap + 1], [B][cap]
-  DevBuf queries, claims, args, ones;          // [B * per][NK] int4 x 2, [B * per] argument blocks, [cap] ones
-  std::vector<DevBuf *> all() { return {&w, &wt, &node, &fv_nn, &fv_node, &fv_start, &fv_feat, &queries, &claims, &args, &ones}; }
+  Arena mem;
+  int *w, *node, *fv_nn, *fv_node, *fv_start, *fv_feat;  // [B][cap] word and node of every feature slot; the frames' FeatureVectors:
+  double *wt;                                            // [B], [B][cap], [B][cap + 1], [B][cap]; [B][cap] weight
+  int4 *queries, *claims;                                // [B * per][NK] each
+  uint8_t *args, *ones;                                  // [B * per] argument blocks (match.hip's NodeArgs), [cap] ones
 };
 int bow_walk_reserve(BowWalkBufs &b, int B, int cap, int per, int NK, hipStream_t st);
 int bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int levelsup, BowWalkBufs &b, hipStream_t st,

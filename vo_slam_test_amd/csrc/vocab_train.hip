@@ -373,10 +373,7 @@ struct Seg {
 };
 
 struct Work {  // device buffers of one training call (a one-off: released when it ends)
-  vo::DevBuf d[24];
-  ~Work() {
-    for (auto &b : d) b.release();
-  }
+  vo::OwnedDevBuf d[24];
 };
 
 int train_resident(int n, const uint8_t *d_desc, int n_images, const int32_t *h_off, const int32_t *d_off, int k, int L,
@@ -572,12 +569,11 @@ int vo_vocab_train(int n_desc, const uint8_t *desc, int n_images, const int32_t 
   VO_CHECK(check_offsets(W, n_desc, n_images, image_offsets));
   VO_CHECK(vo::ensure_device());
   hipStream_t st = vo::thread_stream();
-  vo::DevBuf d_desc, d_off;
+  vo::OwnedDevBuf d_desc, d_off;  // (released on return, behind the synchronisation)
   int rc = vo::upload(d_desc, desc, (size_t)n_desc * 32, st, W);
   if (rc == VO_OK) rc = vo::upload(d_off, image_offsets, (size_t)(n_images + 1) * 4, st, W);
   if (rc == VO_OK) rc = train_resident(n_desc, d_desc.as<uint8_t>(), n_images, image_offsets, d_off.as<int32_t>(), k, L, seed, st, out, info);
   (void)hipStreamSynchronize(st);
-  d_desc.release(), d_off.release();
   return rc;
 }
 
