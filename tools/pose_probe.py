@@ -33,10 +33,10 @@ try:
     import oracle_lib as orc
     poses, outl, inl = d_pose.cpu().numpy(), d_out.cpu().numpy().reshape(len(probs), 1000), d_inl.cpu().numpy()
     worst = 0.0
-    for i in range(min(16, len(base))):
+    for i in range(min(16, len(probs))):
         opose, ooutl, oninl, _, _ = orc.pose_only(base[i])
         worst = max(worst, float(np.abs(poses[i] - opose).max()))
         assert inl[i] == oninl and np.array_equal(outl[i], ooutl), ("mask / inlier mismatch", i)
-    print("parity with the oracle on 16 problems: max |pose diff| %.3e, masks identical" % worst)
+    print("parity with the oracle on the first problems (16 at the most): max |pose diff| %.3e, masks identical" % worst)
 except ImportError as e:  # noqa: BLE001
     print("oracle not available:", e)

@@ -27,12 +27,20 @@ for rep in range(3):
 sums = (vo.LmSummary * (2 * len(probs))).from_buffer_copy(np.ascontiguousarray(d_sum.cpu().numpy()).tobytes())
 tot = np.zeros(5)
 its = 0
-for s in sums:
+out = np.zeros(4)  # outside the LM loops: entry -> round 0, round 0 -> round 1's first iteration, behind round 1, whole kernel
+for k, s in enumerate(sums):
     tot += np.array([s.initial_cost, s.final_cost, s.final_radius, s.reserved, s.accepted], float)
-    its += s.iterations
+    its += s.iterations & 0xff
+    out[k % 2 * 2] += s.termination
+    out[3 if k % 2 == 0 else 1] += s.iterations >> 8
 names = ["solve (read sums, scale, damp, 6x6 Cholesky, model)", "plus (exp, compose, log)", "pass over the observations",
          "28-sum reduction + read-back", "tests, radius update"]
 print(f"{nf} frames x 1000 observations, {its} LM iterations in all; shader-clock cycles per iteration:")
 for n, t in zip(names, tot):
     print(f"  {n:55s} {t / its:9.0f}")
 print(f"  {'sum':55s} {tot.sum() / its:9.0f}")
+print(f"shader-clock cycles per frame ({its / nf:.2f} LM iterations):")
+for n, t in zip(["kernel entry to round 0's solve", "round 0's loop to round 1's first iteration (classification, linearisation at x0)",
+                 "classification behind round 1", "whole kernel"], out):
+    print(f"  {n:85s} {t / nf:9.0f}")
+print(f"  {'inside the two LM loops':85s} {tot.sum() / nf:9.0f}")

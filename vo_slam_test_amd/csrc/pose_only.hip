@@ -1,12 +1,14 @@
 // pose_only.hip -- pose-only bundle adjustment on gfx950 (MI355X), FP64.
 // Replaces myslam::Optimizer::solvePoseOnlySE3 (reference src/optimizer_ceres.cpp:157-314) together with the Ceres
 // solve it delegates to (TrustRegionMinimizer + LevenbergMarquardtStrategy on one 6-dof pose; contract in DESIGN.md).
-// One launch of k_pose_only per batch of frames: both LM rounds and the chi2 classification between them.
+// One launch of k_pose_only per batch of frames: both LM rounds; the chi2 classification between them rides on round 1's
+// first linearisation pass, the one behind round 1 runs on the passes' look-ahead.
 #include "ba_math.h"
 #include "vo_common.h"
 #include "wave_ops.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -90,11 +92,60 @@ __device__ __forceinline__ void pose_obs_term(const PoseCache &P, const double (
   acc[26] = __builtin_fma(x, m1, __builtin_fma(-y, m0, acc[26]));
 }
 
+// float chi2 test of optimizer_ceres.cpp:262-303 (Q-B2: deliberately float)
+__device__ __forceinline__ bool pose_chi2_outlier(const double pc[3], double ou, double ov, double our, float fx,
+                                                  float fy, float cx, float cy, float bf, double isg) {
+  const double x = pc[0], y = pc[1], z = pc[2];
+  const float invz = (float)(1.0f / z);
+  const float u = (float)(fx * x * invz + cx);
+  const float v = (float)(fy * y * invz + cy);
+  const float eu = (float)(u - ou), ev = (float)(v - ov);
+  const float e2 = eu * eu + ev * ev;
+  const float is2 = (float)(isg * isg);
+  if (our < 0) return !(e2 * is2 < 5.991f);
+  const float ur = u - bf * invz;
+  const float eur = (float)(ur - our);
+  return !((e2 + eur * eur) * is2 < 7.815f);
+}
+
+// The classification of a round: Tcw = exp(pose) (Sophus quaternion form, :256-257) and the float intrinsics.  The
+// pose is the same in every lane: it is kept in scalar registers (a pass that classifies while it linearises has no
+// fourteen vector registers to spare).
+struct PoseCls {
+  Se3 T;
+  float fx, fy, cx, cy, bf;
+};
+__device__ __forceinline__ PoseCls pose_cls(const double x[6], const Cam &K) {
+  const Se3 T = se3_exp(x);
+  PoseCls C;
+#pragma unroll
+  for (int a = 0; a < 4; a++) C.T.q[a] = readlane_f64(T.q[a], 0);
+#pragma unroll
+  for (int a = 0; a < 3; a++) C.T.t[a] = readlane_f64(T.t[a], 0);
+  C.fx = (float)K.fx, C.fy = (float)K.fy, C.cx = (float)K.cx, C.cy = (float)K.cy, C.bf = (float)K.bf;
+  return C;
+}
+__device__ __forceinline__ bool pose_is_outlier(const PoseCls &C, const double (&pw)[3], double ou, double ov, double our, double is) {
+  double rp[3], pc[3];
+  quat_rotate(C.T.q, pw, rp);
+  pc[0] = rp[0] + C.T.t[0], pc[1] = rp[1] + C.T.t[1], pc[2] = rp[2] + C.T.t[2];
+  return pose_chi2_outlier(pc, ou, ov, our, C.fx, C.fy, C.cx, C.cy, C.bf, is);
+}
+
+// What a linearisation pass does with the flag array:
+//   kPassAll       round 0: every observation takes part; no flag byte is loaded (the caller's buffer is not even cleared)
+//   kPassFlags     round 1: flagged observations are skipped
+//   kPassClassify  round 1's first pass, at x0: classifies every observation it holds at round 0's result, stores the
+//                  flag and uses it as the skip bit -- round 0's classification read the same observations that this pass
+//                  reads right behind it, in a loop of its own that waited for every load it issued
+enum PosePass { kPassAll, kPassFlags, kPassClassify };
+
 // A batch of observations of the one-wavefront form: ND trips of 64, in registers.
 struct PoseOb { double pw[3], ou, ov, our, is; unsigned skip; };
 // The loads take the wave-uniform bases from scalar registers and a 32-bit byte offset per lane (an int index costs
-// twelve 64-bit address operations per observation); unconditional, the raw flag byte included: a bool would be
+// twelve 64-bit address operations per observation); unconditional, the raw flag byte (FLAGS) included: a bool would be
 // compared, i.e. waited for, where it is loaded.
+template <bool FLAGS>
 __device__ __forceinline__ void pose_request(const ObsView &V, unsigned base, unsigned last, PoseOb (&o)[kPoseNd]) {
   const unsigned lane = threadIdx.x;
   const VO_GLOBAL char *bp = (const VO_GLOBAL char *)V.pts, *bo = (const VO_GLOBAL char *)V.obs, *bi = (const VO_GLOBAL char *)V.isg;
@@ -108,19 +159,21 @@ __device__ __forceinline__ void pose_request(const ObsView &V, unsigned base, un
     o[k].ou = *(const VO_GLOBAL double *)(bo + o24), o[k].ov = *(const VO_GLOBAL double *)(bo + o24 + 8);
     o[k].our = *(const VO_GLOBAL double *)(bo + o24 + 16);
     o[k].is = *(const VO_GLOBAL double *)(bi + o8);
-    o[k].skip = bs[i];
+    o[k].skip = FLAGS ? bs[i] : 0u;
   }
 }
 
-// One linearisation pass over the observations that are not flagged.  WAVE (one wavefront per frame, nothing else on
+// One linearisation pass over the observations that take part (PosePass).  WAVE (one wavefront per frame, nothing else on
 // its SIMD to run while a load is in flight): observations travel in batches of four trips, one batch ahead of their
 // use, into two register sets that swap roles in a loop unrolled by two (no "next becomes current" copies: 14 moves
 // per observation).  `first` holds batch 0 on entry -- requested by the previous pass behind its last trip, so that it
 // travels during the reduction and the 6 x 6 solve (the observations of a round do not change; a pass that requests
-// its own first batch waits for it once per LM iteration) -- and again on exit.
-template <bool WAVE>
+// its own first batch waits for it once per LM iteration) -- and again on exit; its flag bytes are there only where the
+// next pass wants them (a classifying pass re-reads the ones it has just stored: same lane, same address, program order).
+// kPassClassify adds its inliers to cnt: the wavefront's total (WAVE) or the lane's own (256-thread form).
+template <bool WAVE, PosePass PASS>
 __device__ __forceinline__ void pose_accumulate(const PoseCache &P, int n, const ObsView &V, const Cam &K, double hm, double hs,
-                                                double (&acc)[28], PoseOb (&first)[kPoseNd]) {
+                                                double (&acc)[28], PoseOb (&first)[kPoseNd], const PoseCls *C, int &cnt) {
 #pragma unroll
   for (int i = 0; i < 28; i++) acc[i] = 0;
   if (WAVE) {
@@ -128,27 +181,89 @@ __device__ __forceinline__ void pose_accumulate(const PoseCache &P, int n, const
     constexpr int ND = kPoseNd;
     auto eval = [&](unsigned base, const PoseOb (&o)[ND]) {
 #pragma unroll
-      for (int k = 0; k < ND; k++)
-        if (base + 64u * k + lane <= last && !o[k].skip) pose_obs_term(P, o[k].pw, o[k].ou, o[k].ov, o[k].our, o[k].is, K, hm, hs, acc);
+      for (int k = 0; k < ND; k++) {
+        const unsigned i = base + 64u * k + lane;
+        bool use = i <= last;
+        if (PASS == kPassFlags) use = use && !o[k].skip;
+        if (PASS == kPassClassify) {
+          const bool out = pose_is_outlier(*C, o[k].pw, o[k].ou, o[k].ov, o[k].our, o[k].is);
+          if (use) V.outlier[i] = out ? 1 : 0;
+          use = use && !out;
+          cnt += __popcll(__ballot(use));
+        }
+        if (use) pose_obs_term(P, o[k].pw, o[k].ou, o[k].ov, o[k].our, o[k].is, K, hm, hs, acc);
+      }
     };
     PoseOb B[ND];
 #pragma unroll 1
     for (unsigned base = 0; base <= last; base += 2 * ND * 64) {
-      pose_request(V, base + ND * 64, last, B);
+      pose_request<PASS == kPassFlags>(V, base + ND * 64, last, B);
       eval(base, first);
       const unsigned nb = base + 2 * ND * 64;
-      pose_request(V, nb > last ? 0u : nb, last, first);  // behind the last trip: batch 0 for the next pass (0.2275 -> 0.2235 ms)
+      pose_request<PASS != kPassAll>(V, nb > last ? 0u : nb, last, first);  // behind the last trip: batch 0 for the next pass (0.2275 -> 0.2235 ms)
       eval(base + ND * 64, B);  // (a batch wholly past the end evaluates nothing: every lane fails the range test)
     }
     return;
   }
 #pragma unroll 1
   for (int i = threadIdx.x; i < n; i += (int)blockDim.x) {
-    if (V.outlier[i]) continue;
+    if (PASS == kPassFlags && V.outlier[i]) continue;
     double pw[3], ou, ov, our, is;
     V.get(i, pw, ou, ov, our, is);
+    if (PASS == kPassClassify) {
+      const bool out = pose_is_outlier(*C, pw, ou, ov, our, is);
+      V.outlier[i] = out ? 1 : 0;
+      if (out) continue;
+      cnt++;
+    }
     pose_obs_term(P, pw, ou, ov, our, is, K, hm, hs, acc);
   }
+}
+
+// The classification behind round 1: every observation against C, flags stored, inliers counted (WAVE: the wavefront's
+// total; otherwise the lane's own).  No load is waited for in the trip that issues it: the one-wavefront form finds
+// batch 0 in `first` (the last pass requested it) and keeps one batch of four trips in flight like a pass does; the
+// 256-thread form requests a lane's next observation before it tests the present one.
+template <bool WAVE>
+__device__ __forceinline__ int pose_classify_all(int n, const ObsView &V, const PoseCls &C, PoseOb (&first)[kPoseNd]) {
+  int cnt = 0;
+  if (WAVE) {
+    const unsigned lane = threadIdx.x, last = (unsigned)(n - 1);
+    constexpr int ND = kPoseNd;
+    auto cls = [&](unsigned base, const PoseOb (&o)[ND]) {
+#pragma unroll
+      for (int k = 0; k < ND; k++) {
+        const unsigned i = base + 64u * k + lane;
+        const bool out = pose_is_outlier(C, o[k].pw, o[k].ou, o[k].ov, o[k].our, o[k].is);
+        if (i <= last) V.outlier[i] = out ? 1 : 0;
+        cnt += __popcll(__ballot(i <= last && !out));
+      }
+    };
+    PoseOb B[ND];
+#pragma unroll 1
+    for (unsigned base = 0; base <= last; base += 2 * ND * 64) {
+      pose_request<false>(V, base + ND * 64, last, B);
+      cls(base, first);
+      const unsigned nb = base + 2 * ND * 64;
+      if (nb <= last) pose_request<false>(V, nb, last, first);
+      cls(base + ND * 64, B);
+    }
+    return cnt;
+  }
+  const int stride = (int)blockDim.x;
+  int i = threadIdx.x;
+  double pw[3], ou, ov, our, is;
+  if (i < n) V.get(i, pw, ou, ov, our, is);
+#pragma unroll 1
+  for (; i < n; i += stride) {
+    double npw[3], nou, nov, nour, nis;
+    V.get(min(i + stride, n - 1), npw, nou, nov, nour, nis);  // past the end: a harmless re-read
+    const bool out = pose_is_outlier(C, pw, ou, ov, our, is);
+    V.outlier[i] = out ? 1 : 0;
+    cnt += out ? 0 : 1;
+    pw[0] = npw[0], pw[1] = npw[1], pw[2] = npw[2], ou = nou, ov = nov, our = nour, is = nis;
+  }
+  return cnt;
 }
 
 // 6 x 6 SPD solve on the packed lower triangle (row by row: 00 10 11 20 21 22 ...), in place; b := A^-1 b.  Fully
@@ -280,8 +395,13 @@ struct PoseLds {
 
 // -DVO_POSE_STAMPS (tools/pose_stamps.py): shader-clock cycles per phase of the LM loop, summed over the iterations and
 // handed back in the summary's fields (initial_cost = solve, final_cost = plus, final_radius = pass, reserved = reduction,
-// accepted = tests) -- a developer build, never the product.
+// accepted = tests) -- a developer build, never the product.  What lies outside the LM loops travels in the fields that
+// are left: termination of the first summary = kernel entry to round 0's solve, of the second = the classification
+// behind round 1; bits 8.. of the second summary's iterations = end of round 0's loop to the first iteration of round 1
+// (the classification at round 0's result and round 1's first linearisation, in one pass or in two), of the first's = the
+// whole kernel.
 #ifdef VO_POSE_STAMPS
+#define POSE_NOW(var, dep) asm volatile("s_memtime %0\n s_waitcnt lgkmcnt(0)" : "=s"(var), "+v"(dep)::"memory")
 #define POSE_STAMP(slot, dep)                                                                            \
   do {                                                                                                   \
     unsigned long long t_;                                                                               \
@@ -297,9 +417,15 @@ struct PoseLds {
 // trial step accumulates the candidate's sums while the solve's temporaries are dead and vice versa (round 2 kept
 // two sets of 28 accumulators next to a 6 x 6 system in every lane: 256 VGPR + 251 AGPR).  Every thread carries the
 // (uniform) trust-region scalars in registers.
-template <bool WAVE>
-__device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, double hm, double hs, int max_it, PoseLds<WAVE> &S,
-                        vo_lm_summary *sum) {
+//
+// ROUND 0 (Huber): no pass looks at the flag array.  ROUND 1 (plain): the first pass, at x0, is the classification at
+// round 0's result C as well (kPassClassify) and leaves the inlier count in inl; below 10 (:306-307) the linearisation is
+// dropped, nothing else is done and false comes back: the frame keeps round 0's pose.  `first` is batch 0 of the
+// observations on entry and on exit (one-wavefront form).
+template <bool WAVE, int ROUND>
+__device__ __forceinline__ bool pose_lm(double x[6], int n, const ObsView &V, const Cam &K, double hm, double hs, int max_it,
+                                        PoseLds<WAVE> &S, PoseOb (&first)[kPoseNd], const PoseCls *C, int *s_cnt, int &inl,
+                                        vo_lm_summary *sum, unsigned long long *t_loop_) {
   // exp(x) is kept across the iterations (an accepted candidate's exp is the product se3_plus forms anyway) and the
   // residuals are evaluated from it: rotation matrix from the unit quaternion, t = V * upsilon -- what
   // se3TransPoint(x) computes through sin / cos of |omega|, up to rounding; no trigonometry per evaluation.
@@ -308,11 +434,11 @@ __device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, doub
   unsigned long long st_[5] = {0, 0, 0, 0, 0}, tp_ = 0;
 #endif
   bool in_loop_ = false;  // (stamps)
-  PoseOb first[kPoseNd];  // batch 0 of the next pass (one-wavefront form)
-  if (WAVE) pose_request(V, 0, (unsigned)(n - 1), first);
-  auto linearize = [&](const Se3 &T, double *dst) {  // sums of the linearisation at T -> dst (LDS)
+  int cnt = 0;
+  constexpr PosePass kFirstPass = ROUND == 0 ? kPassAll : kPassClassify, kLoopPass = ROUND == 0 ? kPassAll : kPassFlags;
+  auto linearize = [&](auto pass, const Se3 &T, double *dst) {  // sums of the linearisation at T -> dst (LDS)
     double v[28];
-    pose_accumulate<WAVE>(pose_cache_se3(T), n, V, K, hm, hs, v, first);
+    pose_accumulate<WAVE, decltype(pass)::value>(pose_cache_se3(T), n, V, K, hm, hs, v, first, C, cnt);
     POSE_STAMP(in_loop_ ? 2 : -1, v[27]);
     if (WAVE) {
       wave_reduce28<true>(v, S.red, dst);
@@ -336,7 +462,18 @@ __device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, doub
   };
   // the linearisation at x and the one at the candidate swap roles when a step is accepted (no copy)
   double *cur = S.acc, *cnd = S.cand;
-  linearize(Tx, cur);
+  linearize(std::integral_constant<PosePass, kFirstPass>(), Tx, cur);
+  if (ROUND == 1) {
+    if (WAVE) {
+      inl = cnt;
+    } else {
+      for (int o = 32; o >= 1; o >>= 1) cnt += __shfl_xor(cnt, o);
+      if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+      __syncthreads();
+      inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
+    }
+    if (inl < 10) return false;
+  }
   double scale[6];
 #pragma unroll
   for (int a = 0; a < 6; a++) scale[a] = 1.0 / (1.0 + sqrt(cur[tri_u(a, a)]));
@@ -363,6 +500,9 @@ __device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, doub
     }
     in_loop_ = true;
     POSE_STAMP(-1, x_cost);
+#ifdef VO_POSE_STAMPS
+    if (t_loop_ && it == 1) *t_loop_ = tp_;
+#endif
     double h[27];  // one batch of LDS reads: the gradient test and the normal equations use the same values
 #pragma unroll
     for (int i = 0; i < 27; i++) h[i] = cur[i];
@@ -433,7 +573,7 @@ __device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, doub
     POSE_STAMP(1, xc[0]);
     // The candidate is linearised completely in the same pass (its cost is one of the 28 sums): an
     // accepted step -- the common case -- then needs no second sweep over the observations.
-    linearize(Tc, cnd);
+    linearize(std::integral_constant<PosePass, kLoopPass>(), Tc, cnd);
     double cand = cnd[27];
     POSE_STAMP(3, cand);
     if (!isfinite(cand)) cand = 1.7976931348623157e308;
@@ -486,22 +626,7 @@ __device__ void pose_lm(double x[6], int n, const ObsView &V, const Cam &K, doub
     sum->reserved = (int)st_[3], sum->accepted = (int)st_[4];
 #endif
   }
-}
-
-// float chi2 test of optimizer_ceres.cpp:262-303 (Q-B2: deliberately float)
-__device__ __forceinline__ bool pose_chi2_outlier(const double pc[3], double ou, double ov, double our, float fx,
-                                                  float fy, float cx, float cy, float bf, double isg) {
-  const double x = pc[0], y = pc[1], z = pc[2];
-  const float invz = (float)(1.0f / z);
-  const float u = (float)(fx * x * invz + cx);
-  const float v = (float)(fy * y * invz + cy);
-  const float eu = (float)(u - ou), ev = (float)(v - ov);
-  const float e2 = eu * eu + ev * ev;
-  const float is2 = (float)(isg * isg);
-  if (our < 0) return !(e2 * is2 < 5.991f);
-  const float ur = u - bf * invz;
-  const float eur = (float)(ur - our);
-  return !((e2 + eur * eur) * is2 < 7.815f);
+  return true;
 }
 
 // ranges != 0: problem p owns observations [offsets[2p], offsets[2p] + offsets[2p+1]) (frames at a fixed stride,
@@ -519,7 +644,6 @@ __global__ __launch_bounds__(WAVE ? 64 : 256) void k_pose_only(const int *offset
   const int o0 = ranges ? offsets[2 * p] : offsets[p], n = ranges ? offsets[2 * p + 1] : offsets[p + 1] - o0;
   pts += 3 * (long long)o0, obs += 3 * (long long)o0, isg += o0, outlier += o0;
   Cam K{cam5[0], cam5[1], cam5[2], cam5[3], cam5[4]};
-  const float fx = (float)K.fx, fy = (float)K.fy, cx = (float)K.cx, cy = (float)K.cy, bf = (float)K.bf;
   double x0[6], x[6];
   for (int a = 0; a < 6; a++) x0[a] = x[a] = poses[6 * p + a];
   if (n <= 0) {  // :204-205
@@ -527,39 +651,55 @@ __global__ __launch_bounds__(WAVE ? 64 : 256) void k_pose_only(const int *offset
     return;
   }
   const ObsView V{(const VO_GLOBAL double *)pts, (const VO_GLOBAL double *)obs, (const VO_GLOBAL double *)isg, (VO_GLOBAL uint8_t *)outlier};
-  const int stride = WAVE ? 64 : (int)blockDim.x;
-  for (int i = threadIdx.x; i < n; i += stride) outlier[i] = 0;
-  __syncthreads();
+  // The flag array is written, never cleared: round 0 does not look at it, and round 1's first pass stores every byte
+  // before anything reads one.
+#ifdef VO_POSE_STAMPS
+  unsigned long long t_in_ = 0, t_a_ = 0, t_b_ = 0, t_c_ = 0, t_end_ = 0, t_l1_ = 0;
+  unsigned long long *const tl1_ = &t_l1_;  // (a frame that leaves after round 0 hands back no outer stamps: its second summary is zeroed)
+  POSE_NOW(t_in_, x[0]);
+#else
+  unsigned long long *const tl1_ = nullptr;
+#endif
+  PoseOb first[kPoseNd];  // batch 0 of the frame's observations: every pass finds it in flight or arrived (one-wavefront form)
+  if (WAVE) pose_request<false>(V, 0, (unsigned)(n - 1), first);
   int inl = 0;
-  for (int round = 0; round < 2; round++) {
-    for (int a = 0; a < 6; a++) x[a] = x0[a];  // :215
-    const double hm = round == 0 ? (double)sqrtf(5.991f) : 0.0;
-    const double hs = round == 0 ? (double)sqrtf(7.815f) : 0.0;
-    pose_lm<WAVE>(x, n, V, K, hm, hs, 10, S, sums ? &sums[2 * p + round] : nullptr);
-    __syncthreads();
-    // classification with Tcw = exp(pose) (Sophus quaternion form, :256-257)
-    const Se3 T = se3_exp(x);
-    int local = 0;
-#pragma unroll 1
-    for (int i = threadIdx.x; i < n; i += stride) {
-      double rp[3], pc[3], pw[3], ou, ov, our, is;
-      V.get(i, pw, ou, ov, our, is);
-      quat_rotate(T.q, pw, rp);
-      pc[0] = rp[0] + T.t[0], pc[1] = rp[1] + T.t[1], pc[2] = rp[2] + T.t[2];
-      const bool out = pose_chi2_outlier(pc, ou, ov, our, fx, fy, cx, cy, bf, is);
-      outlier[i] = out ? 1 : 0;
-      local += out ? 0 : 1;
+#ifdef VO_POSE_STAMPS
+  POSE_NOW(t_a_, x[0]);
+#endif
+  pose_lm<WAVE, 0>(x, n, V, K, (double)sqrtf(5.991f), (double)sqrtf(7.815f), 10, S, first, nullptr, s_cnt, inl,
+                   sums ? &sums[2 * p] : nullptr, nullptr);
+#ifdef VO_POSE_STAMPS
+  POSE_NOW(t_b_, x[0]);
+#endif
+  // round 1 starts from x0 again (:215); its first pass classifies at round 0's result
+  const PoseCls C0 = pose_cls(x, K);
+  if (pose_lm<WAVE, 1>(x0, n, V, K, 0.0, 0.0, 10, S, first, &C0, s_cnt, inl, sums ? &sums[2 * p + 1] : nullptr, tl1_)) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) x[a] = x0[a];
+#ifdef VO_POSE_STAMPS
+    POSE_NOW(t_c_, x[0]);
+#endif
+    const PoseCls C1 = pose_cls(x, K);
+    int local = pose_classify_all<WAVE>(n, V, C1, first);
+    if (WAVE) {
+      inl = local;
+    } else {
+      for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o);
+      __syncthreads();  // round 1's count has been read
+      if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = local;
+      __syncthreads();
+      inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
     }
-    for (int o = 32; o >= 1; o >>= 1) local += __shfl_xor(local, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = local;
-    __syncthreads();
-    inl = s_cnt[0] + s_cnt[1] + s_cnt[2] + s_cnt[3];
-    __syncthreads();
-    if (inl < 10) {  // :306-307
-      if (round == 0 && sums && threadIdx.x == 0) memset(&sums[2 * p + 1], 0, sizeof(vo_lm_summary));
-      break;
+#ifdef VO_POSE_STAMPS
+    double dep_ = (double)inl;
+    POSE_NOW(t_end_, dep_);
+    if (sums && threadIdx.x == 0) {
+      sums[2 * p].termination = (int)(t_a_ - t_in_), sums[2 * p + 1].termination = (int)(t_end_ - t_c_);
+      sums[2 * p].iterations |= (int)(t_end_ - t_in_) << 8, sums[2 * p + 1].iterations |= (int)(t_l1_ - t_b_) << 8;
     }
+#endif
+  } else if (sums && threadIdx.x == 0) {
+    memset(&sums[2 * p + 1], 0, sizeof(vo_lm_summary));  // fewer than 10 inliers after round 0: round 1 did not run
   }
   if (threadIdx.x == 0) {
     n_inliers[p] = inl;
