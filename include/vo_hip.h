@@ -782,6 +782,25 @@ int vo_tracker_track_first_dev(vo_tracker *t, const uint8_t *dev_images, int ima
                                const void *dev_depth, int depth_kind, size_t depth_frame_stride, int depth_pitch,
                                const vo_tracker_params *params);
 int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params);
+/* vo_tracker_track_local_map after vo_tracker_relocalize, _store or _db (and their _dev forms): trackLocalMap as the
+ * reference runs it behind a successful relocalization() (visualOdometry.cpp:61, :74, :82-83 -> :726-774, :287-310), on the
+ * frame state the relocalisation left (VO_TRACKER_FEATURE_HAS_POINT / _POINTS / _OUTLIER, VO_TRACKER_RELOC_POINT_IDS).  The
+ * local map is whatever vo_tracker_set_local_map holds: the caller reads the winners (VO_TRACKER_RELOC_*) and builds it
+ * between the two calls; it passes th_radius = 5 (:768; params NULL: 5, 0.8).  vo_tracker_set_local_map_ids: the map-point
+ * id of every local point, ids [batch][n] with n = the local map's n, in the id space VO_TRACKER_RELOC_POINT_IDS reports
+ * (the store's global ids after _store / _db, the dense ids after vo_tracker_relocalize; negative: no id).  A local point
+ * whose id is held by a non-null, non-outlier slot of its frame is skipped (`mp->visualIdxOfFrame_ == frame id`, :753);
+ * the ids belong to the local map they were set for (vo_tracker_set_local_map forgets them), and WITHOUT ids nothing is
+ * skipped after a relocalisation (`link` is not used: the frame's points are no entries of a last-frame list).  The
+ * search's `occupied` is: the slot holds a point with observations -- bit 1 of the key-frame feature's flags, which the
+ * relocalisation routes carry per slot.  The solve runs over all non-null slots, the relocalisation's and the new matches;
+ * vo_tracker_results then returns its pose, n_inliers = its return value, n_tracked = inliers_num_ of :289-303 (not
+ * outlier, and observed), n_matches_local = the search's count; VO_TRACKER_ASSIGNED_LOCAL its assignment, and
+ * VO_TRACKER_RELOC_POINT_IDS includes the new points' ids.  A frame with VO_TRACK_RELOC_FAILED is not touched: every
+ * output keeps the value the relocalisation left, n_matches_local 0.  The decision of :307-310 (< 50 right after a
+ * relocalisation) is the caller's, from n_tracked.  No local map set, or ids with another n: VO_ERR_INVALID before anything
+ * is enqueued.  All enqueued, no synchronisation; on every other route vo_tracker_track_local_map behaves as above. */
+int vo_tracker_set_local_map_ids(vo_tracker *t, int n, const int32_t *ids /*[batch][n]*/);
 /* VisualOdometry::trackRefKeyFrame (visualOdometry.cpp:256-277) -- the route taken when trackWithMotion fails --
  * followed by trackLocalMap (first_stage_only = 0) or on its own (1): Frame construction, Frame::computeBow (vocabulary
  * transform on the device), Matcher(0.7).searchByBoW(keyframe_trackRef_, frame) (k_node_replay, one workgroup per
@@ -792,7 +811,8 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params);
  * (nodes[batch], levelsup 3) and Tcw12 [batch][12] = frame_last_->Tcw_.  It REPLACES the last-frame state
  * (vo_tracker_set_last_frame): the key-frame's map points take the place of frame_last_->mappoints_ for the rest of the
  * pipeline (`link` of vo_tracker_set_local_map then indexes the key-frame's features).  The vocabulary must outlive
- * the tracker's use of it.  The common-node walk is host work: this route synchronises once inside the call. */
+ * the tracker's use of it.  The common-node walk is host work: this route synchronises once inside the call.
+ * vo_tracker_track_ref_keyframe_store below is the same route with the key-frames read from a device store. */
 int vo_tracker_set_ref_keyframe(vo_tracker *t, const vo_vocab *vocab, int n, const double *Tcw12, const double *points,
                                 const uint8_t *flags, const float *angle, const uint8_t *desc,
                                 const vo_bow_view *const *nodes);
@@ -828,7 +848,8 @@ typedef struct {
   const float *angle;        /* [n] unKeypoints_[i].angle */
   const uint8_t *desc;       /* [n][32] descriptors_ */
   const vo_bow_view *nodes;  /* featVec_ (levelsup 3) */
-  const uint8_t *flags;      /* [n] bit 0: the feature's map point exists and is not bad */
+  const uint8_t *flags;      /* [n] bit 0: the feature's map point exists and is not bad; bit 1 (key-frame store only):
+                                observe_cnt_ > 0 */
   const double *points;      /* [n][3] MapPoint::getPose() */
   const int32_t *ids;        /* [n] map point id */
   const uint8_t *point_desc; /* [n][32] MapPoint::getDescriptor() */
@@ -847,7 +868,9 @@ int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int imag
  * number 0, 1, 2 ... -- the numbering of vo_kfdb -- and is never erased.  Every device buffer is sized at creation from
  * (max_keyframes, max_features); one more key-frame, or a key-frame with more features (or more FeatureVector entries)
  * than that, is VO_ERR_CAPACITY and nothing is truncated.  Per key-frame: n, bad; per feature: angle, desc, flags (bit 0:
- * the map point exists and is not bad), points, ids, point_desc, min / max distance; the FeatureVector (levelsup 3) as a
+ * the map point exists and is not bad; bit 1: observe_cnt_ > 0, the meaning vo_tracker_set_ref_keyframe gives it -- the
+ * whole byte is carried by insert, insert_dev and update_points; the relocalisation routes ignore bit 1,
+ * vo_tracker_track_ref_keyframe_store reads it), points, ids, point_desc, min / max distance; the FeatureVector (levelsup 3) as a
  * CSR: node ids ascending, start, feat.  ids are global map-point ids: any non-negative int32 (the route maps them to
  * dense ids per frame itself).  Calls on one handle are serialised by the caller; work is enqueued on the handle's stream
  * (NULL, the legacy stream, until vo_kfstore_set_stream).  A tracker call that reads the store orders itself behind
@@ -903,6 +926,33 @@ int vo_tracker_relocalize_db_dev(vo_tracker *t, vo_kfdb *db, const vo_kfstore *s
                                  const float *dev_stale_score, const uint8_t *dev_images, int image_pitch,
                                  size_t image_frame_stride, const void *dev_depth, int depth_kind, size_t depth_frame_stride,
                                  int depth_pitch, const vo_tracker_params *params);
+/* vo_tracker_set_ref_keyframe + vo_tracker_track_ref_keyframe with the reference key-frames read from a store: the
+ * reference key-frame of frame f is key-frame dev_ref_kf[f] (device memory, [batch]) and its start pose dev_Tcw12
+ * [batch][12] (device memory; frame_last_->Tcw_, rotation row-major + translation).  Frame construction, computeBow, the
+ * frames' FeatureVectors (k_featvec), the key-frames' points and flags gathered from the store into the last-frame arrays
+ * together with the start pose and its se3 logarithm (k_ref_kf_gather), the common-node walk (k_bow_walk, one pair per
+ * frame, Matcher(params->ref_ratio), 0.7 when not positive), k_node_replay and the tail of vo_tracker_track_ref_keyframe:
+ * all enqueued, no host synchronisation, no device-to-host copy, and no allocation after the first store route of the
+ * tracker that needs larger walk buffers than the routes used before it (they are sized for max_last features per
+ * key-frame here, for max_reloc_features on the relocalisation routes, and only ever grow).  The tracker needs no relocalisation route
+ * configured.  The store's max_features must not exceed max_last (VO_ERR_CAPACITY at the call, nothing enqueued).  A
+ * key-frame flagged bad in the store is searched like any other: searchByBoW(KeyFrame*, Frame*) tests the map points
+ * (matcher.cpp:476), never the key-frame.  Bit 1 of the store's flags (observe_cnt_ > 0) is read here, as after
+ * vo_tracker_set_ref_keyframe.  Results are bit-identical to vo_tracker_set_ref_keyframe + vo_tracker_track_ref_keyframe
+ * on the same key-frames.  Like vo_tracker_set_ref_keyframe the call REPLACES the last-frame state, and the reference
+ * key-frame handed to vo_tracker_set_ref_keyframe earlier is gone after it.  A key-frame number outside [0, store size)
+ * is searched as a key-frame without features: that frame gets 0 matches and VO_TRACK_FEW_MATCHES, every other frame's
+ * outputs are valid, and vo_tracker_results reports the condition as sticky VO_ERR_INVALID (the word of the store routes
+ * of relocalisation).  dev_ref_kf and dev_Tcw12 must stay untouched until the stream has passed the call. */
+int vo_tracker_track_ref_keyframe_store(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab,
+                                        const int32_t *dev_ref_kf, const double *dev_Tcw12, const uint8_t *images,
+                                        const void *depth, int depth_kind, const vo_tracker_params *params,
+                                        int first_stage_only);
+int vo_tracker_track_ref_keyframe_store_dev(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab,
+                                            const int32_t *dev_ref_kf, const double *dev_Tcw12, const uint8_t *dev_images,
+                                            int image_pitch, size_t image_frame_stride, const void *dev_depth, int depth_kind,
+                                            size_t depth_frame_stride, int depth_pitch, const vo_tracker_params *params,
+                                            int first_stage_only);
 /* With vo_tracker_set_timing on, a store route records HIP events around its four new stages: 0 k_featvec, 1 the gather
  * from the store, 2 the id compaction, 3 k_bow_walk.  Synchronises and returns the milliseconds of the LAST such call
  * (VO_ERR_INVALID when none has run with timing on).  tools/reloc_db_bench.py. */
@@ -912,7 +962,8 @@ int vo_tracker_get_reloc_timing(vo_tracker *t, double *ms /*VO_TRACKER_RELOC_STA
  * [batch][12]; n_tracked = inliers of the second solve whose map point has observations (inliers_num_,
  * :289-300); n_inliers = the second solve's return value; the two searches' match counts; status bits.
  * Reports sticky stage errors (dropped key-points, exhausted candidate pools) as VO_ERR_CAPACITY, and the two sticky
- * conditions of vo_tracker_relocalize_store / _db (above); the outputs are copied out before it reports. */
+ * conditions of vo_tracker_relocalize_store / _db and vo_tracker_track_ref_keyframe_store (above); the outputs are copied
+ * out before it reports. */
 int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_tracked, int32_t *n_inliers,
                        int32_t *n_matches_last, int32_t *n_matches_local, int32_t *status);
 /* intermediate state of the last batch (tests, shims): [batch][max_features] / [batch][max_local] arrays */

@@ -53,6 +53,7 @@ SYMBOLS = [
     "vo_kfstore_create", "vo_kfstore_destroy", "vo_kfstore_set_stream", "vo_kfstore_size", "vo_kfstore_insert", "vo_kfstore_insert_dev",
     "vo_kfstore_set_bad", "vo_kfstore_update_points", "vo_tracker_relocalize_store", "vo_tracker_relocalize_store_dev",
     "vo_tracker_relocalize_db", "vo_tracker_relocalize_db_dev", "vo_tracker_get_reloc_timing",
+    "vo_tracker_track_ref_keyframe_store", "vo_tracker_track_ref_keyframe_store_dev", "vo_tracker_set_local_map_ids",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -566,8 +567,17 @@ class Tracker:
         pr = self._params(radius, 3.0, 0.8, direction, no_retry)
         check(lib().vo_tracker_track_first(self._h, _p(img), _p(dp), kind, C.byref(pr)), "vo_tracker_track_first")
 
+    def set_local_map_ids(self, ids):
+        """map-point ids [B, n] of the local points set by set_local_map (n = its n), in the id space get(RELOC_POINT_IDS)
+        reports: track_local_map after relocalize* skips the local points whose id the frame already holds"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        check(lib().vo_tracker_set_local_map_ids(self._h, int(ids.shape[1]), _p(ids)), "vo_tracker_set_local_map_ids")
+
     def track_local_map(self, th_radius=3.0, ratio=0.8):
-        """trackLocalMap on the state the first stage left, against the local map set in between"""
+        """trackLocalMap on the state the first stage left, against the local map set in between.  After relocalize /
+        relocalize_dev / relocalize_store / relocalize_db it runs on the frame state the relocalisation left (pass
+        th_radius=5, visualOdometry.cpp:768): set_local_map + set_local_map_ids in between; frames whose relocalisation
+        failed are not touched.  Without a local map set: VoError (VO_ERR_INVALID)."""
         pr = self._params(15.0, th_radius, ratio, 0)
         check(lib().vo_tracker_track_local_map(self._h, C.byref(pr)), "vo_tracker_track_local_map")
 
@@ -593,6 +603,30 @@ class Tracker:
         pr.ref_ratio = float(ref_ratio)
         check(lib().vo_tracker_track_ref_keyframe(self._h, _p(img), _p(dp), kind, C.byref(pr), int(bool(first_stage_only))),
               "vo_tracker_track_ref_keyframe")
+
+    def track_ref_keyframe_store(self, store, vocab, ref_kf, Tcw12, images, depth=None, th_radius=3.0, ratio=0.8, ref_ratio=0.7,
+                                 first_stage_only=False):
+        """vo_tracker_track_ref_keyframe_store[_dev]: trackRefKeyFrame (+ trackLocalMap) with frame f's reference key-frame
+        read from `store` by number.  ref_kf: int32 [B] and Tcw12: float64 [B, 12] DEVICE tensors (frame_last_->Tcw_); images /
+        depth host arrays or device tensors.  Asynchronous: no host step, no synchronisation; results() / get() after."""
+        pr = self._params(15.0, th_radius, ratio, 0)
+        pr.ref_ratio = float(ref_ratio)
+        head = (self._h, store._h, vocab._h, _p(ref_kf), _p(Tcw12))
+        if hasattr(images, "data_ptr"):
+            check(lib().vo_tracker_track_ref_keyframe_store_dev(*head, *self._dev_frames(images, depth), C.byref(pr),
+                                                                int(bool(first_stage_only))), "vo_tracker_track_ref_keyframe_store_dev")
+        else:
+            img, dp, kind = self._host_frames(images, depth)
+            check(lib().vo_tracker_track_ref_keyframe_store(*head, _p(img), _p(dp), kind, C.byref(pr), int(bool(first_stage_only))),
+                  "vo_tracker_track_ref_keyframe_store")
+        self._ref_store_keep = (store, vocab, ref_kf, Tcw12)  # the enqueued kernels read them
+
+    def track_ref_keyframe_dev(self, images, depth=None, th_radius=3.0, ratio=0.8, ref_ratio=0.7, first_stage_only=False):
+        """trackRefKeyFrame (+ trackLocalMap) from device tensors (uint8 [B,H,W]; depth float32 / (u)int16 [B,H,W] or None)"""
+        pr = self._params(15.0, th_radius, ratio, 0)
+        pr.ref_ratio = float(ref_ratio)
+        check(lib().vo_tracker_track_ref_keyframe_dev(self._h, *self._dev_frames(images, depth), C.byref(pr), int(bool(first_stage_only))),
+              "vo_tracker_track_ref_keyframe_dev")
 
     def set_reloc_candidates(self, vocab, candidates):
         """candidates[f] = the frame's candidate key-frames in the order VisualOdometry::relocalization walks them, each a

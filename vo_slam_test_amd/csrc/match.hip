@@ -1150,6 +1150,8 @@ int launch_featvec(const FeatVecArgs &A, int frames, hipStream_t st) {
 // entry), so query list and claim scratch are fixed [pairs][NK] regions.
 struct BowWalkArgs {
   int per, cap, NK, check_rot;
+  int search_bad;  // 0: a key-frame flagged bad matches nothing (relocalisation, :323); 1: it is searched like any other
+                   // (trackRefKeyFrame: searchByBoW tests the map points, matcher.cpp:476, never the key-frame)
   float ratio;
   vo::KfStoreView S;
   const int *pair_kf;  // [pairs] key-frame of the store or -1
@@ -1172,7 +1174,7 @@ __global__ __launch_bounds__(64) void k_bow_walk(BowWalkArgs A) {
   const bool have = k >= 0 && k < A.S.size;
   if (have) {
     const int *head = vo::kf_head(A.S, k);
-    const int n = min(max(head[0], 0), A.NK), bad = head[1], nnA = min(max(head[2], 0), A.NK);
+    const int n = min(max(head[0], 0), A.NK), bad = A.search_bad ? 0 : head[1], nnA = min(max(head[2], 0), A.NK);
     nA = bad ? 0 : n;
     if (!bad && n > 0 && nB > 0 && nnA > 0) {
       const int *nodeA = vo::kf_sec<int>(A.S, k, A.S.o_node), *startA = vo::kf_sec<int>(A.S, k, A.S.o_start);
@@ -1296,13 +1298,14 @@ int vo::featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int
 
 int vo::bow_walk_replay(vo_frames *frames, int B, int per, const vo::KfStoreView &S, const int *dev_pair_kf, float ratio,
                         int check_rot, vo::BowWalkBufs &b, int32_t *dev_assigned, int32_t *dev_n_matches, hipStream_t st,
-                        hipEvent_t ev0, hipEvent_t ev1) {
-  if (!frames || B != b.B || per != b.per || !dev_pair_kf || !dev_assigned || !dev_n_matches) return VO_ERR_INVALID;
+                        hipEvent_t ev0, hipEvent_t ev1, bool search_bad) {
+  if (!frames || B != b.B || per < 1 || per > b.per || !dev_pair_kf || !dev_assigned || !dev_n_matches) return VO_ERR_INVALID;
   if (S.NK > b.NK) return VO_ERR_CAPACITY;
   const vo::FrameStoreView fs = vo::frame_store_view(frames);
   const int NP = B * per;
   BowWalkArgs A{};
   A.per = per, A.cap = b.cap, A.NK = b.NK, A.check_rot = check_rot, A.ratio = ratio, A.S = S, A.pair_kf = dev_pair_kf;
+  A.search_bad = search_bad ? 1 : 0;
   A.fn = fs.n, A.fdesc = fs.desc, A.fangle = fs.angle;
   A.fv_nn = b.fv_nn, A.fv_node = b.fv_node, A.fv_start = b.fv_start, A.fv_feat = reinterpret_cast<const uint32_t *>(b.fv_feat);
   A.queries = b.queries, A.claims = b.claims, A.args = reinterpret_cast<NodeArgs *>(b.args), A.ones = b.ones;

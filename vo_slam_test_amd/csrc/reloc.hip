@@ -73,6 +73,8 @@ struct RelocDev {
   // the tracker's
   double *pose, *fpoint;
   uint8_t *fhas, *foutl;
+  uint8_t *fobs;  // [B][cap] the slot's map point has observations (bit 1 of the source feature's flags): the `occupied` of the
+                  // local-map search behind a relocalisation (matcher.cpp:314)
   double *pts, *obs, *isg;
   int *ranges, *index;
   const uint8_t *outlier;
@@ -207,7 +209,7 @@ __global__ __launch_bounds__(256) void k_reloc_apply(RelocDev D, int r) {
   int *rec = D.rec + (size_t)f * kRecInts;
   const size_t o = (size_t)f * D.cap;
   if (r == 0) {  // a freshly constructed frame (visualOdometry.cpp:57-63): every slot null, outliers_ clear
-    for (int i = tid; i < D.cap; i += 256) D.fid[o + i] = -1, D.fhas[o + i] = 0, D.foutl[o + i] = 0;
+    for (int i = tid; i < D.cap; i += 256) D.fid[o + i] = -1, D.fhas[o + i] = 0, D.foutl[o + i] = 0, D.fobs[o + i] = 0;
     if (tid < 6) D.pose[6 * f + tid] = 0.0;
     if (tid < D.MC) D.out_code[f * D.MC + tid] = kOutNotReached, D.out_bow[f * D.MC + tid] = 0, D.out_pnp[f * D.MC + tid] = 0;
   }
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(256) void k_reloc_apply(RelocDev D, int r) {
         const int i = D.src[o0 + j], a = D.bow_assigned[(size_t)p * D.cap + i];
         const double *P3 = D.kf_point + 3 * (ko + a);
         D.fpoint[3 * (o + i)] = P3[0], D.fpoint[3 * (o + i) + 1] = P3[1], D.fpoint[3 * (o + i) + 2] = P3[2];
-        D.fhas[o + i] = 1;
+        D.fhas[o + i] = 1, D.fobs[o + i] = (D.kf_flags[ko + a] >> 1) & 1u;
         const int id = D.kf_id[ko + a];
         D.fid[o + i] = id;
         if (pass) found[id] = 1;
@@ -282,7 +284,7 @@ __global__ __launch_bounds__(256) void k_reloc_after_solve(RelocDev D, int r, in
     const int i = D.index[start + d];
     const uint8_t out = D.outlier[start + d];
     D.foutl[o + i] = out;
-    if (cull && out) D.fhas[o + i] = 0, D.fid[o + i] = -1;  // :345-349, :377-381
+    if (cull && out) D.fhas[o + i] = 0, D.fobs[o + i] = 0, D.fid[o + i] = -1;  // :345-349, :377-381
   }
   int stage = kIdle, code = -1;
   if (which == 1) {
@@ -394,7 +396,7 @@ __global__ __launch_bounds__(256) void k_reloc_after_search(RelocDev D, int r, i
     if (a < 0) continue;
     const double *P3 = D.kf_point + 3 * (ko + a);
     D.fpoint[3 * (o + i)] = P3[0], D.fpoint[3 * (o + i) + 1] = P3[1], D.fpoint[3 * (o + i) + 2] = P3[2];
-    D.fhas[o + i] = 1, D.fid[o + i] = D.kf_id[ko + a];
+    D.fhas[o + i] = 1, D.fobs[o + i] = (D.kf_flags[ko + a] >> 1) & 1u, D.fid[o + i] = D.kf_id[ko + a];
   }
   const bool solve = rec[kRecInliers] + D.nm[f] >= 50;
   __syncthreads();
@@ -428,7 +430,7 @@ __global__ __launch_bounds__(256) void k_reloc_finish(RelocDev D, int *winner, u
 }
 
 // ---- the store routes: the candidates are key-frame numbers in device memory ------------------
-enum { kErrTooMany = 1, kErrBadId = 2 };  // the sticky word of the store routes
+enum { kErrTooMany = vo::kStoreErrTooMany, kErrBadId = vo::kStoreErrBadId };  // the sticky word of the store routes
 
 struct StoreDev {
   vo::KfStoreView S;
@@ -558,6 +560,106 @@ __global__ __launch_bounds__(256) void k_reloc_word_pack(int cap, const int *fn,
   for (int i = threadIdx.x; i < n; i += 256) ow[o + i] = w[(size_t)f * cap + i], owt[o + i] = wt[(size_t)f * cap + i];
 }
 
+// ---- trackLocalMap behind a relocalisation (vo_tracker_track_local_map after vo_tracker_relocalize*): searchLocalMapPoints
+// (visualOdometry.cpp:726-774) and the second solve with its count (:287-303) on the frame state the walk left.  A frame
+// whose relocalisation failed takes no part: nq[f] = -1 leaves it out of every step and nothing of it is written.
+struct LocalDev {
+  int nq, stride;          // local points per frame, row stride
+  const uint8_t *pf1;      // [B][stride] the local map's flags as set
+  uint8_t *q1_flags;       // [B][stride] out: the flags Frame::isInFrame is run with (0: skipped)
+  const int *ids1;         // [B][stride] map-point ids of the local points, or NULL: nothing is skipped
+  const double *p1;
+  int *fid;                // [B][cap] the frame's ids in the id space VO_TRACKER_RELOC_POINT_IDS reports
+  const int *winner;
+};
+
+// `mp->visualIdxOfFrame_ == frame_curr_->id_` (:753) by id: the ids held by the frame's non-null, non-outlier slots are sorted
+// in LDS (block_sort.h; the power of two above cap keys) and every local point looks its id up by binary search -- cap log cap
+// + n_local log cap per frame instead of the cap x n_local of a scan per point.  Also clears `assigned` for the search.
+__global__ __launch_bounds__(256) void k_reloc_local_prep(RelocDev D, LocalDev L) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long lp_keys[];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const bool active = L.winner[f] >= 0;
+  if (tid == 0) D.nq[f] = active ? L.nq : -1;
+  if (!active) return;
+  const size_t o = (size_t)f * D.cap, lo = (size_t)f * L.stride;
+  const int n = min(max(D.fn[f], 0), D.cap), np2 = vo::pow2_ceil(D.cap);
+  for (int i = tid; i < D.cap; i += 256) D.assigned[o + i] = -1;
+  if (L.ids1) {
+    for (int s_ = tid; s_ < np2; s_ += 256) {
+      unsigned long long key = ~0ull;
+      if (s_ < n && D.fhas[o + s_] && !D.foutl[o + s_] && L.fid[o + s_] >= 0) key = (unsigned long long)(unsigned)L.fid[o + s_];
+      lp_keys[s_] = key;
+    }
+    vo::block_bitonic_sort(lp_keys, np2);
+  }
+  for (int q = tid; q < L.nq; q += 256) {
+    uint8_t pf = L.pf1[lo + q];
+    if ((pf & 1u) && L.ids1) {
+      const int id = L.ids1[lo + q];
+      if (id >= 0) {
+        const unsigned long long key = (unsigned long long)(unsigned)id;
+        int a = 0, b = np2;  // first key >= id
+        while (a < b) {
+          const int mid = (a + b) >> 1;
+          if (lp_keys[mid] < key) a = mid + 1;
+          else b = mid;
+        }
+        if (a < np2 && lp_keys[a] == key) pf = 0;
+      }
+    }
+    L.q1_flags[lo + q] = pf;
+  }
+}
+
+// the search's matches into the frame's slots (matcher.cpp:338-340), then the observation list of the solve over ALL
+// non-null slots (:287)
+__global__ __launch_bounds__(256) void k_reloc_local_gather(RelocDev D, LocalDev L) {
+  __shared__ int wsum[4];
+  __shared__ int s_base;
+  const int f = blockIdx.x, tid = threadIdx.x;
+  const size_t o = (size_t)f * D.cap, lo = (size_t)f * L.stride;
+  if (D.nq[f] < 0) {
+    if (tid == 0) D.ranges[2 * f] = (int)o, D.ranges[2 * f + 1] = -1;
+    return;
+  }
+  const int n = min(max(D.fn[f], 0), D.cap);
+  for (int i = tid; i < n; i += 256) {
+    const int a = D.assigned[o + i];
+    if (a < 0 || a >= L.nq) continue;
+    const double *P3 = L.p1 + 3 * (lo + a);
+    D.fpoint[3 * (o + i)] = P3[0], D.fpoint[3 * (o + i) + 1] = P3[1], D.fpoint[3 * (o + i) + 2] = P3[2];
+    D.fhas[o + i] = 1, D.fobs[o + i] = (L.q1_flags[lo + a] >> 1) & 1u;
+    L.fid[o + i] = L.ids1 ? L.ids1[lo + a] : -1;
+  }
+  __syncthreads();
+  gather_frame(D, f, wsum, &s_base);
+}
+
+// outliers_ of the solve's features, inliers_num_ (:289-303: not outlier, and observed), the frame's record of the result
+// block: pose, n_tracked, n_inliers = the solve's return value, n_matches_local; n_matches_last and the status stay
+__global__ __launch_bounds__(256) void k_reloc_local_count(RelocDev D, uint8_t *resblk) {
+  __shared__ int s4[4];
+  const int f = blockIdx.x, tid = threadIdx.x;
+  if (D.nq[f] < 0) return;
+  const size_t o = (size_t)f * D.cap;
+  const int start = D.ranges[2 * f], count = D.ranges[2 * f + 1];
+  int local = 0;
+  for (int d = tid; d < count; d += 256) {
+    const int i = D.index[start + d];
+    const uint8_t out = D.outlier[start + d];
+    D.foutl[o + i] = out;
+    if (!out && D.fobs[o + i]) local++;
+  }
+  const int total = block_sum(local, s4);
+  if (tid == 0) {
+    double *pd = reinterpret_cast<double *>(resblk + (size_t)f * 72);
+    for (int k = 0; k < 6; k++) pd[k] = D.pose[6 * f + k];
+    int *pi = reinterpret_cast<int *>(resblk + (size_t)f * 72 + 48);
+    pi[0] = total, pi[1] = D.ninl_solve[f], pi[3] = D.nm[f];
+  }
+}
+
 struct CandHost {
   int n = 0;
   std::vector<uint8_t> valid, desc;
@@ -591,7 +693,7 @@ struct vo::Reloc {
   // the candidate arrays are set then, the rest per call), the database query's on the first call with a database
   bool store_ready = false, store_db = false, last_store = false;
   int ids_lds_slots = 0, ids_gstride = 0;
-  BowWalkBufs walk;
+  BowWalkBufs *walk = nullptr;  // the tracker's (reloc_store_prepare)
   Arena store_mem, db_mem;
   StoreDev s{};
   unsigned long long *s_keys = nullptr;
@@ -652,7 +754,6 @@ void vo::Reloc::layout_store(Arena &a) {
   a.take(s.pair_kf, P * 4 + 64);
   a.take(s.l2g, PK * 4);
   a.take(s.fid_g, Bc * 4);
-  a.take(s.err, 64);
   if (ids_gstride) a.take(s_keys, (size_t)B * ids_gstride * 8);  // (the id compaction's keys, when they do not fit in LDS)
 }
 
@@ -838,7 +939,7 @@ RelocDev reloc_dev(vo::Reloc *r, const vo::RelocShared &S, const int *n_cand) {
   RelocDev D = r->d;
   D.fn = fs.n, D.X = fs.x, D.Y = fs.y, D.UR = fs.uright, D.OCT = fs.octave;
   D.n_cand = n_cand;
-  D.pose = S.pose, D.fpoint = S.fpoint, D.fhas = S.fhas, D.foutl = S.foutl, D.pts = S.pts, D.obs = S.obs, D.isg = S.isg;
+  D.pose = S.pose, D.fpoint = S.fpoint, D.fhas = S.fhas, D.foutl = S.foutl, D.fobs = S.fobs, D.pts = S.pts, D.obs = S.obs, D.isg = S.isg;
   D.ranges = S.ranges, D.index = S.index, D.outlier = S.outlier, D.assigned = S.assigned, D.nm = S.nm;
   return D;
 }
@@ -916,10 +1017,10 @@ const void *reloc_selector(const Reloc *r, int what, size_t *bytes) {
 }
 
 // ---- the store routes ------------------------------------------------------------------------------------------
-int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st) {
-  if (!r) return VO_ERR_INVALID;
+int reloc_store_prepare(Reloc *r, BowWalkBufs *walk, int *err, bool with_db, hipStream_t st) {
+  if (!r || !walk || !err) return VO_ERR_INVALID;
+  r->walk = walk, r->s.err = err;
   if (!r->store_ready) {
-    VO_CHECK(bow_walk_reserve(r->walk, r->B, r->cap, r->MC, r->NK, st));
     // the id compaction sorts the power of two above MC * NK keys per frame: in LDS up to 128 KiB, else in a slab
     const int np2 = pow2_ceil(r->MC * r->NK);
     if ((size_t)np2 * 8 <= 128 * 1024) {
@@ -930,7 +1031,6 @@ int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st) {
       r->ids_lds_slots = 0, r->ids_gstride = np2;
     }
     VO_CHECK(r->store_mem.build([&](Arena &a) { r->layout_store(a); }, "store route"));
-    VO_HIP_CHECK(hipMemsetAsync(r->s.err, 0, 64, st));
     // the candidate arrays the gather writes in place of vo_tracker_set_reloc_candidates
     StoreDev &T = r->s;
     T.kf_n = r->d.kf_n, T.kf_bad = r->d.kf_bad, T.kf_flags = r->d.kf_flags, T.kf_point = r->d.kf_point, T.kf_id = r->d.kf_id;
@@ -958,14 +1058,14 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
   r->have = false;  // the candidate arrays are the store's from here: vo_tracker_relocalize needs its candidates set again
   r->last_store = true;
   // ---- Frame::computeBow and the frames' FeatureVectors
-  VO_CHECK(bow_featvec_resident(A.vocab, S.frames, B, 3, r->walk, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
+  VO_CHECK(bow_featvec_resident(A.vocab, S.frames, B, 3, *r->walk, st, ev ? ev[0] : nullptr, ev ? ev[1] : nullptr));
   // ---- Map::detectRelocalizationCandidates: the frames' BoW vectors, the database query
   const int *n_cand = A.dev_n_cand, *cand = A.dev_cand;
   int stride = A.cand_stride;
   if (A.db) {
     hipLaunchKernelGGL(k_reloc_word_start, dim3(1), dim3(256), 0, st, B, r->cap, fs.n, r->q.fstart);
-    hipLaunchKernelGGL(k_reloc_word_pack, dim3(B), dim3(256), 0, st, r->cap, fs.n, (const int *)r->q.fstart, (const int *)r->walk.w,
-                       (const double *)r->walk.wt, r->q.w, r->q.wt);
+    hipLaunchKernelGGL(k_reloc_word_pack, dim3(B), dim3(256), 0, st, r->cap, fs.n, (const int *)r->q.fstart, (const int *)r->walk->w,
+                       (const double *)r->walk->wt, r->q.w, r->q.wt);
     VO_HIP_CHECK(hipGetLastError());
     VO_CHECK(vo_bow_vector_dev(B, B * r->cap, r->q.fstart, r->q.w, r->q.wt, r->q.bstart, r->q.bw, r->q.bv, st));
     VO_CHECK(kfdb_query_reloc_on(A.db, st, B, r->q.bstart, r->q.bw, r->q.bv, A.dev_stale, MC, r->q.nc, r->q.cand));
@@ -987,7 +1087,7 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
   VO_HIP_CHECK(hipGetLastError());
   VO_CHECK(mark(5));
   // ---- searchByBoW of every pair: the common-node walk and the replay
-  VO_CHECK(bow_walk_replay(S.frames, B, MC, T.S, T.pair_kf, 0.75f, 1, r->walk, D.bow_assigned, D.bow_n, st,
+  VO_CHECK(bow_walk_replay(S.frames, B, MC, T.S, T.pair_kf, 0.75f, 1, *r->walk, D.bow_assigned, D.bow_n, st,
                            ev ? ev[6] : nullptr, ev ? ev[7] : nullptr));
   VO_CHECK(reloc_tail(r, S, D));
   hipLaunchKernelGGL(k_reloc_store_finish, dim3(B), dim3(256), 0, st, D, T, S.resblk);
@@ -995,7 +1095,40 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
   return kfstore_order_after(A.store, st);
 }
 
-const int *reloc_store_error_flag(const Reloc *r) { return r && r->store_ready ? r->s.err : nullptr; }
 bool reloc_last_was_store(const Reloc *r) { return r && r->last_store; }
+
+// ---- trackLocalMap behind a relocalisation --------------------------------------------------------------------------
+namespace {
+LocalDev local_dev(Reloc *r, const RelocLocalArgs &L) {
+  return LocalDev{L.nq, L.stride, L.pf1, L.q1_flags, L.ids1, L.p1, r->last_store ? r->s.fid_g : r->d.fid, r->winner};
+}
+}  // namespace
+
+int reloc_local_prep(Reloc *r, const RelocShared &S, const RelocLocalArgs &L, const int **frame_on) {
+  if (!r || !frame_on) return VO_ERR_INVALID;
+  const size_t lds = (size_t)pow2_ceil(r->cap) * 8;
+  if (lds > 128 * 1024) {
+    set_error("vo_tracker_track_local_map: %d feature slots per frame, the id lookup sorts 16384", r->cap);
+    return VO_ERR_CAPACITY;
+  }
+  if (lds > 64 * 1024)
+    VO_HIP_CHECK(hipFuncSetAttribute((const void *)k_reloc_local_prep, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+  const RelocDev D = reloc_dev(r, S, r->n_cand);
+  hipLaunchKernelGGL(k_reloc_local_prep, dim3(r->B), dim3(256), lds, S.st, D, local_dev(r, L));
+  VO_HIP_CHECK(hipGetLastError());
+  *frame_on = D.nq;
+  return VO_OK;
+}
+
+int reloc_local_finish(Reloc *r, const RelocShared &S, const RelocLocalArgs &L) {
+  if (!r) return VO_ERR_INVALID;
+  const RelocDev D = reloc_dev(r, S, r->n_cand);
+  hipLaunchKernelGGL(k_reloc_local_gather, dim3(r->B), dim3(256), 0, S.st, D, local_dev(r, L));
+  VO_HIP_CHECK(hipGetLastError());
+  VO_CHECK(vo_pose_only_solve_ranges_dev(r->B, S.ranges, S.pts, S.obs, S.isg, S.cam5d, S.pose, S.outlier, D.ninl_solve, nullptr, S.st));
+  hipLaunchKernelGGL(k_reloc_local_count, dim3(r->B), dim3(256), 0, S.st, D, S.resblk);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
 
 }  // namespace vo

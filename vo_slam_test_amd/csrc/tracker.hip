@@ -14,6 +14,10 @@
 //   solvePoseOnlySE3, inlier count (:289-300)        k_track_scatter_gather + k_pose_only + k_track_count (which also
 //                                                    writes the frame's record of the result block)
 //
+// trackRefKeyFrame (:256-277) replaces the projection search by searchByBoW(reference key-frame, frame): stage_ref_keyframe (key-frames
+// from host arrays, the common-node walk on the host) or stage_ref_keyframe_store (key-frames read from a vo_kfstore by
+// number: k_featvec, k_ref_kf_gather, k_bow_walk, k_node_replay -- launches only).
+//
 // 27 kernel launches per batch (round 4: 33), no host synchronisation in between.  The extraction may run on a stream shared by several
 // trackers (vo_tracker_config.extract_stream): batch i + 1's extraction then overlaps batch i's searches and pose
 // solves (two events order them).  Round 2 kept this sequence in Python (vo_slam_test_amd/tracking.py) without the
@@ -90,6 +94,7 @@ struct PackArgs {
   const double *pose;
   const int *ninl, *nm_first, *nm, *orb_err, *guided_err;
   uint8_t *out;
+  const int *store_err;  // the store routes' sticky word, or NULL on a route that reads no store (the third flag stays)
 };
 __device__ __forceinline__ void pack_record(const PackArgs &K, int f, int ntracked, int status) {
   double *pd = reinterpret_cast<double *>(K.out + (size_t)f * 72);
@@ -100,6 +105,7 @@ __device__ __forceinline__ void pack_record(const PackArgs &K, int f, int ntrack
     int *fl = reinterpret_cast<int *>(K.out + (size_t)K.B * 72);
     fl[0] = K.orb_err ? *K.orb_err : 0;
     fl[1] = K.guided_err ? *K.guided_err : 0;
+    if (K.store_err) fl[2] = *K.store_err;
   }
 }
 // (on its own: the first frame of a sequence, whose counts are memsets)
@@ -179,6 +185,7 @@ struct InFrameArgs {
   float *qu, *qv, *qur;
   int *qlevel;
   float *qviewcos;
+  const int *frame_on;  // [frames] or NULL: a negative entry leaves the frame out (nothing of it is written)
 };
 // s_T: q (w, x, y, z), t, Ow of the frame's pose (in_frame_pose), set by one thread before a barrier
 __device__ __forceinline__ void in_frame_pose(const InFrameArgs &A, int f, double *s_T) {
@@ -232,6 +239,7 @@ __device__ __forceinline__ void in_frame_query(const InFrameArgs &A, int f, int 
 __global__ __launch_bounds__(256) void k_track_in_frame(InFrameArgs A) {
   __shared__ double s_T[10];
   const int f = blockIdx.y, q = blockIdx.x * 256 + threadIdx.x;
+  if (A.frame_on && A.frame_on[f] < 0) return;
   if (threadIdx.x == 0) in_frame_pose(A, f, s_T);
   __syncthreads();
   if (q < A.nq) in_frame_query(A, f, q, s_T);
@@ -283,6 +291,37 @@ __global__ __launch_bounds__(256) void k_track_first_status(int B, const int *n_
   pack_record(K, f, n_observed_first[f], st);
 }
 
+// trackRefKeyFrame from the key-frame store (vo_tracker_track_ref_keyframe_store): what vo_tracker_set_ref_keyframe uploads,
+// read out of the store instead.  Frame f's reference key-frame is record ref_kf[f]: its `points` section into p0 and its
+// `flags` section into pf0 and q0_flags (row stride n_last, zero beyond the key-frame's n), so that the tail of the
+// pipeline indexes them exactly as after the host call.  One lane per double of the points section -- 24 bytes per
+// feature, the section contiguous per key-frame: consecutive lanes read and write consecutive doubles -- and the first
+// n_last lanes of a frame also copy a flag byte each.  Thread 0 of a frame's first block writes the start pose: Tcw as
+// given and its se3 logarithm (frame_curr_->setPose(frame_last_->Tcw_), :259).  A number outside [0, size) is a key-frame
+// without features and raises the store routes' sticky word (only ever OR-ed).
+__global__ __launch_bounds__(256) void k_ref_kf_gather(vo::KfStoreView S, const int *ref_kf, const double *Tcw_in, int n_last,
+                                                       double *p0, uint8_t *pf0, uint8_t *q0_flags, double *Tcw, double *pose0,
+                                                       int *err) {
+  const int f = blockIdx.y, j = blockIdx.x * 256 + threadIdx.x;
+  const int k = ref_kf[f];
+  const bool have = k >= 0 && k < S.size;
+  const int n = have ? min(max(vo::kf_head(S, k)[0], 0), min(S.NK, n_last)) : 0;
+  if (j == 0) {
+    if (!have) atomicOr(err, (int)vo::kStoreErrBadId);
+    const double *T = Tcw_in + 12 * (size_t)f;
+    for (int i = 0; i < 12; i++) Tcw[12 * (size_t)f + i] = T[i];
+    double xi[6];
+    se3_log_from_R(T, T + 9, xi);
+    for (int i = 0; i < 6; i++) pose0[6 * (size_t)f + i] = xi[i];
+  }
+  const size_t o = (size_t)f * n_last;
+  if (j < 3 * n_last) p0[3 * o + j] = j < 3 * n ? vo::kf_sec<double>(S, k, S.o_points)[j] : 0.0;
+  if (j < n_last) {
+    const uint8_t fl = j < n ? vo::kf_sec<uint8_t>(S, k, S.o_flags)[j] : (uint8_t)0;
+    pf0[o + j] = fl, q0_flags[o + j] = fl;
+  }
+}
+
 constexpr int kStages = VO_TRACKER_STAGES;
 
 }  // namespace
@@ -327,11 +366,12 @@ struct vo_tracker {
     double *p0;
     uint8_t *q1_flags, *q1_desc, *pf1;  // the local map's [B][n_local]
     float *q1_u, *q1_v, *q1_aux, *q1_viewcos, *mind1, *maxd1;
-    int *q1_level, *link1;
+    int *q1_level, *link1, *ids1;  // ids1: map-point ids of the local points (vo_tracker_set_local_map_ids)
     double *p1, *nrm1;
     double *Tcw, *pose0, *pose, *pose_first;  // Tcw: [B][12], then the intrinsics as doubles
     uint8_t *resblk;                          // k_track_pack's block (72 bytes per frame + 2 flags)
     int *retry_nq;                            // [B] query counts of the retry pass
+    int *store_err;                           // the store routes' sticky word (vo_common.h: kStoreErr*)
     int *assigned, *assigned_first, *nm, *nm_first, *ninl, *ninl_first, *nobs_first, *ntracked, *status;
     double *fpoint, *pts, *obs, *isg;  // per-feature frame state [B][cap] and the pose problem gathered from it
     uint8_t *fhas, *fobs, *foutl, *outlier;
@@ -343,6 +383,8 @@ struct vo_tracker {
   OwnedPinnedBuf stage;
   bool have_result = false;  // a call has written the result block
   bool have_link = false;
+  bool have_local = false, have_ids = false;  // vo_tracker_set_local_map / _ids have been called (the ids belong to that local map)
+  bool last_reloc = false;                    // the last front ran a relocalisation route: track_local_map takes the hand-over
   // a search's matches that the next solve_pose writes into the frame's slots (k_track_scatter_gather)
   struct { const int32_t *assigned = nullptr; const double *qpoints = nullptr; const uint8_t *qflags = nullptr; int stride = 0; } pend;
   int first_min_matches = 20;
@@ -352,6 +394,12 @@ struct vo_tracker {
   // the relocalisation route (reloc.hip); NULL: not configured (vo_tracker_config.max_reloc_candidates == 0)
   vo::Reloc *reloc = nullptr;
   const vo::RelocStoreArgs *store_args = nullptr;  // set for the duration of a vo_tracker_relocalize_store / _db call
+  // the store routes' BoW walk buffers (relocalisation and trackRefKeyFrame share them), sized by the first such call
+  vo::BowWalkBufs walk;
+  // trackRefKeyFrame from the store: the arguments of the call being enqueued; whether the last front ran that route
+  struct RefStoreArgs { const vo_kfstore *store; const vo_vocab *vocab; const int32_t *ref_kf; const double *Tcw12; };
+  const RefStoreArgs *ref_store_args = nullptr;
+  bool ref_store = false;
   const char *store_call = "";                      // the entry point of the last store route (error texts)
   hipEvent_t rtev[8] = {nullptr};                   // vo_tracker_get_reloc_timing: created by the first timed store route
   bool rtimed = false;
@@ -392,6 +440,7 @@ void vo_tracker::layout(vo::Arena &a) {
   a.take(d.maxd1, B * nm * 4);
   a.take(d.pf1, B * nm);
   a.take(d.link1, B * nm * 4);
+  a.take(d.ids1, B * nm * 4);
   a.take(d.Tcw, B * 96 + 64);  // Tcw, then the intrinsics as doubles
   a.take(d.pose0, B * 48);
   a.take(d.pose, B * 48);
@@ -417,6 +466,7 @@ void vo_tracker::layout(vo::Arena &a) {
   a.take(d.status, B * 4 + 64);
   a.take(d.retry_nq, B * 4 + 64);
   a.take(d.foutl, B * cap + 64);
+  a.take(d.store_err, 64);
 }
 
 namespace {
@@ -489,7 +539,7 @@ int solve_pose(vo_tracker *t) {
 
 // What a call runs: the front (extraction + Frame::Frame), one of the two first stages -- trackWithMotion's projection
 // search (with its 2 x radius retry) or trackRefKeyFrame's vocabulary-node search --, and the local-map stage.
-enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u, kRunReloc = 16u };
+enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u, kRunReloc = 16u, kRunRefStore = 32u };
 
 // the images and the depth of one call, in device memory (the host-buffer calls pass their uploaded copies)
 struct FrameInput {
@@ -540,7 +590,7 @@ int stage_front(vo_tracker *t, const FrameInput &in, const void *host_depth) {
 PackArgs pack_args(vo_tracker *t) {
   t->have_result = true;
   return PackArgs{t->B, t->d.pose, t->d.ninl, t->d.nm_first, t->d.nm, vo::orb_error_flag(t->orb), vo::guided_error_flag(t->frames),
-                  t->d.resblk};
+                  t->d.resblk, t->ref_store ? t->d.store_err : nullptr};
 }
 int launch_pack(vo_tracker *t) {
   hipLaunchKernelGGL(k_track_pack, dim3((t->B + 255) / 256), dim3(256), 0, t->st, pack_args(t), t->d.ntracked, t->d.status);
@@ -612,13 +662,38 @@ int stage_ref_keyframe(vo_tracker *t, const vo_tracker_params &P) {
   return VO_OK;
 }
 
+// The same search with the reference key-frames read from the key-frame store by number (vo_tracker_track_ref_keyframe_store):
+// the frames' FeatureVectors (k_bow_transform, k_featvec), the key-frames' map points and the start pose out of the store
+// (k_ref_kf_gather), the common-node walk on the device (k_bow_walk, one pair per frame, a bad key-frame searched like any
+// other) and k_node_replay -- six launches, nothing but launches and two event operations around the store's stream.
+int stage_ref_keyframe_store(vo_tracker *t, const vo_tracker_params &P) {
+  const int B = t->B;
+  hipStream_t st = t->st;
+  StageTimer tm(t, 2, st);
+  const vo_tracker::RefStoreArgs &A = *t->ref_store_args;
+  const vo_tracker::Arrays &d = t->d;
+  VO_CHECK(vo::bow_featvec_resident(A.vocab, t->frames, B, 3, t->walk, st));
+  VO_CHECK(vo::kfstore_order_before(A.store, st));
+  const vo::KfStoreView S = vo::kfstore_view(A.store);
+  hipLaunchKernelGGL(k_ref_kf_gather, dim3((3 * t->n_last + 255) / 256, B), dim3(256), 0, st, S, A.ref_kf, A.Tcw12, t->n_last, d.p0,
+                     d.pf0, d.q0_flags, d.Tcw, d.pose0, d.store_err);
+  hipLaunchKernelGGL(k_track_prep, dim3(B), dim3(256), 0, st, t->cap, t->n_last, d.assigned, d.fhas, d.fobs, d.last_matched, d.pose0,
+                     d.pose);
+  VO_HIP_CHECK(hipGetLastError());
+  VO_CHECK(vo::bow_walk_replay(t->frames, B, 1, S, A.ref_kf, P.ref_ratio > 0.f ? P.ref_ratio : 0.7f, 1, t->walk, d.assigned,
+                               d.nm_first, st, nullptr, nullptr, true));
+  VO_CHECK(vo::kfstore_order_after(A.store, st));
+  t->pend.assigned = d.assigned, t->pend.qpoints = d.p0, t->pend.qflags = d.q0_flags, t->pend.stride = t->n_last;
+  return VO_OK;
+}
+
 InFrameArgs in_frame_args(vo_tracker *t) {
   const vo_tracker_config &c = t->cfg;
   const vo_tracker::Arrays &d = t->d;
   return InFrameArgs{t->nq_local, t->n_local, d.pose, d.p1, d.nrm1, d.mind1, d.maxd1, d.pf1, t->have_link ? d.link1 : (const int *)nullptr,
                      d.last_matched, t->n_last, c.intrinsics[0], c.intrinsics[1], c.intrinsics[2], c.intrinsics[3], c.intrinsics[4], 0.f,
                      (float)c.width, 0.f, (float)c.height, (float)log((double)t->sf[1]), t->n_levels, d.q1_flags, d.q1_u, d.q1_v,
-                     d.q1_aux, d.q1_level, d.q1_viewcos};
+                     d.q1_aux, d.q1_level, d.q1_viewcos, nullptr};
 }
 
 // solvePoseOnlySE3 + cullingOutliersBeforeLocalMap (:249-250 / :271-272)
@@ -674,17 +749,52 @@ int stage_local(vo_tracker *t, const vo_tracker_params &P) {
 
 // VisualOdometry::relocalization() (:313-395) on the frames the front has built: reloc.hip works on the tracker's
 // per-feature frame state and pose-solver buffers
-int stage_reloc(vo_tracker *t) {
+vo::RelocShared reloc_shared(vo_tracker *t) {
   const vo_tracker_config &c = t->cfg;
   const vo_tracker::Arrays &d = t->d;
   vo::RelocShared S{};
   S.frames = t->frames, S.B = t->B, S.cap = t->cap, S.n_levels = t->n_levels, S.width = c.width, S.height = c.height, S.sf = t->sf;
   for (int i = 0; i < 5; i++) S.cam5[i] = c.intrinsics[i];
   S.cam5d = d.Tcw + (size_t)t->B * 12;
-  S.pose = d.pose, S.fpoint = d.fpoint, S.fhas = d.fhas, S.foutl = d.foutl, S.pts = d.pts, S.obs = d.obs, S.isg = d.isg;
+  S.pose = d.pose, S.fpoint = d.fpoint, S.fhas = d.fhas, S.foutl = d.foutl, S.fobs = d.fobs, S.pts = d.pts, S.obs = d.obs, S.isg = d.isg;
   S.ranges = d.ranges, S.index = d.index, S.outlier = d.outlier, S.ninl = d.ninl, S.assigned = d.assigned, S.nm = d.nm;
   S.resblk = d.resblk, S.orb_err = vo::orb_error_flag(t->orb), S.guided_err = vo::guided_error_flag(t->frames);
   S.st = t->st;
+  return S;
+}
+
+// trackLocalMap behind a relocalisation (:61, :74, :82-83 -> :280-310): searchLocalMapPoints from the frame state the walk
+// left in fpoint / fhas / fobs / foutl, the local points the frame already holds skipped by id, the search with
+// occupied = the slot holds an observed point, the solve over all non-null slots, inliers_num_.  Frames whose
+// relocalisation failed are left out of every launch.
+int stage_local_reloc(vo_tracker *t, const vo_tracker_params &P) {
+  const int B = t->B;
+  hipStream_t st = t->st;
+  const vo_tracker::Arrays &d = t->d;
+  const vo::RelocShared S = reloc_shared(t);
+  const vo::RelocLocalArgs L{t->nq_local, t->n_local, d.pf1, d.q1_flags, t->have_ids ? d.ids1 : (const int *)nullptr, d.p1};
+  const int *frame_on = nullptr;
+  VO_CHECK(vo::reloc_local_prep(t->reloc, S, L, &frame_on));
+  if (t->nq_local > 0) {
+    InFrameArgs A = in_frame_args(t);
+    A.pflags = d.q1_flags, A.link = nullptr, A.frame_on = frame_on;  // (a thread reads its point's flags before it writes them)
+    hipLaunchKernelGGL(k_track_in_frame, dim3((t->nq_local + 255) / 256, B), dim3(256), 0, st, A);
+    VO_HIP_CHECK(hipGetLastError());
+    vo_guided_queries q{};
+    vo_guided_params gp{};
+    gp.n_levels = t->n_levels, gp.scale_factors = t->sf;
+    q.n_queries = t->nq_local, q.stride = t->n_local, q.n_per_frame = frame_on, q.flags = d.q1_flags, q.u = d.q1_u, q.v = d.q1_v;
+    q.aux = d.q1_aux, q.level = d.q1_level, q.viewcos = d.q1_viewcos, q.desc = d.q1_desc;
+    gp.mode = 1, gp.radius = P.th_radius, gp.ratio = P.ratio, gp.bf = 0.f, gp.direction = 0, gp.check_rot = 0;
+    VO_CHECK(vo_match_guided_dev(t->frames, 0, B, &q, &gp, d.fobs, d.assigned, nullptr, d.nm, 0, st));
+  } else {
+    VO_HIP_CHECK(hipMemsetAsync(d.nm, 0, (size_t)B * 4, st));
+  }
+  return vo::reloc_local_finish(t->reloc, S, L);
+}
+
+int stage_reloc(vo_tracker *t) {
+  const vo::RelocShared S = reloc_shared(t);
   t->have_result = true;
   if (!t->store_args) return vo::reloc_run(t->reloc, S);
   vo::RelocStoreArgs A = *t->store_args;
@@ -715,7 +825,11 @@ int run_pipeline(vo_tracker *t, const FrameInput &in, const vo_tracker_params *p
   } else {
     P.radius = 15.f, P.th_radius = 3.f, P.ratio = 0.8f, P.direction = 0, P.no_retry = 0, P.ref_ratio = 0.7f;
   }
-  if (run & kRunFront) VO_CHECK(stage_front(t, in, host_depth));
+  if (run & kRunFront) {
+    t->ref_store = (run & kRunRefStore) != 0;
+    t->last_reloc = (run & kRunReloc) != 0;
+    VO_CHECK(stage_front(t, in, host_depth));
+  }
   if (run & kRunReloc) return stage_reloc(t);
   const size_t capB = (size_t)B * t->cap;
   if ((run & kRunMotion) && t->nq_last == 0) {
@@ -738,8 +852,11 @@ int run_pipeline(vo_tracker *t, const FrameInput &in, const vo_tracker_params *p
   } else if (run & kRunRefKeyFrame) {
     t->first_min_matches = 15;  // :268
     VO_CHECK(stage_ref_keyframe(t, P));
+  } else if (run & kRunRefStore) {
+    t->first_min_matches = 15;  // :268
+    VO_CHECK(stage_ref_keyframe_store(t, P));
   }
-  if (run & (kRunMotion | kRunRefKeyFrame)) VO_CHECK(stage_solve_cull(t));
+  if (run & (kRunMotion | kRunRefKeyFrame | kRunRefStore)) VO_CHECK(stage_solve_cull(t));
   // (the result block is written by the last kernel of either route: k_track_count / k_track_first_status)
   if (run & kRunLocal) {
     VO_CHECK(stage_local(t, P));
@@ -815,6 +932,7 @@ int vo_tracker_create(vo_tracker **out, const vo_tracker_config *cfg) {
   if ((rc = t->kps.reserve((size_t)t->B * t->kcap * sizeof(vo_keypoint))) != VO_OK || (rc = t->desc.reserve((size_t)t->B * t->kcap * 32)) != VO_OK)
     return fail(rc);
   t->d.kps = t->kps.as<vo_keypoint>(), t->d.desc = t->desc.as<uint8_t>();
+  if (hipMemset(t->d.store_err, 0, 64) != hipSuccess) return fail(VO_ERR_HIP);
   if (cfg->max_reloc_candidates > 0 || cfg->max_reloc_features > 0) {
     if (cfg->max_reloc_candidates < 1 || cfg->max_reloc_candidates > 256 || cfg->max_reloc_features < 1) return fail(VO_ERR_INVALID);
     if ((rc = vo::reloc_create(&t->reloc, t->B, t->cap, cfg->max_reloc_candidates, cfg->max_reloc_features, t->sf, t->n_levels)) != VO_OK)
@@ -900,7 +1018,21 @@ int vo_tracker_set_local_map(vo_tracker *t, int n, const double *points, const d
   t->have_link = link != nullptr;
   if (link) VO_CHECK(put_rows(t, t->d.link1, link, n, t->n_local, 4));
   t->nq_local = n;
+  t->have_local = true, t->have_ids = false;  // (ids belong to the local map they were set for)
   VO_HIP_CHECK(hipStreamSynchronize(t->st));
+  return VO_OK;
+}
+
+int vo_tracker_set_local_map_ids(vo_tracker *t, int n, const int32_t *ids) {
+  if (!t) return VO_ERR_INVALID;
+  if (!t->have_local || n != t->nq_local || (n > 0 && !ids)) {
+    vo::set_error("vo_tracker_set_local_map_ids: %d ids for a local map of %d points (vo_tracker_set_local_map first)", n,
+                  t->have_local ? t->nq_local : -1);
+    return VO_ERR_INVALID;
+  }
+  VO_CHECK(put_rows(t, t->d.ids1, ids, n, t->n_local, 4));
+  VO_HIP_CHECK(hipStreamSynchronize(t->st));
+  t->have_ids = true;
   return VO_OK;
 }
 
@@ -954,6 +1086,17 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params) {
   if (!t->have_result) {
     vo::set_error("vo_tracker_track_local_map: no first stage has run (vo_tracker_track_first / _ref_keyframe_first)");
     return VO_ERR_INVALID;
+  }
+  if (t->last_reloc) {  // behind vo_tracker_relocalize*: the hand-over (checked before anything is enqueued)
+    if (!t->have_local) {
+      vo::set_error("vo_tracker_track_local_map: no local map has been set (vo_tracker_set_local_map)");
+      return VO_ERR_INVALID;
+    }
+    vo_tracker_params P;
+    if (params) P = *params;
+    else P.radius = 15.f, P.th_radius = 5.f, P.ratio = 0.8f, P.direction = 0, P.no_retry = 0, P.ref_ratio = 0.7f;  // :768
+    t->pend.assigned = nullptr;
+    return stage_local_reloc(t, P);
   }
   return run_pipeline(t, FrameInput{}, params, kRunLocal);
 }
@@ -1038,6 +1181,71 @@ int vo_tracker_set_ref_keyframe(vo_tracker *t, const vo_vocab *vocab, int n, con
   return VO_OK;
 }
 
+// The BoW walk buffers of the store routes, sized from the tracker's capacities: max_reloc_candidates key-frames per frame
+// (trackRefKeyFrame: one) of up to `nk` features, nk = the bound of the calling route on a store's max_features
+// (relocalisation: max_reloc_features, trackRefKeyFrame: max_last).  The buffers only ever grow, and only on the first call
+// of a route that needs more than the routes used so far: a tracker that never runs trackRefKeyFrame from the store keeps
+// the relocalisation footprint it had.
+static int walk_reserve(vo_tracker *t, int nk) {
+  if (t->walk.B != 0 && nk > t->walk.NK) VO_HIP_CHECK(hipStreamSynchronize(t->st));  // (growing frees the block an enqueued route may still read)
+  return vo::bow_walk_reserve(t->walk, t->B, t->cap, std::max(t->cfg.max_reloc_candidates, 1), std::max(nk, t->walk.NK), t->st);
+}
+
+// what the store form of trackRefKeyFrame checks before anything is enqueued; sizes the walk buffers on the first call
+static int ref_store_ready(vo_tracker *t, const char *call, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_ref_kf,
+                           const double *dev_Tcw12) {
+  if (!t) return VO_ERR_INVALID;
+  if (!store || !vocab || !dev_ref_kf || !dev_Tcw12) {
+    vo::set_error("%s: no store, no vocabulary, or no key-frame numbers / poses", call);
+    return VO_ERR_INVALID;
+  }
+  const vo::KfStoreView V = vo::kfstore_view(store);
+  if (V.NK > t->n_last) {
+    vo::set_error("%s: the store holds %d features per key-frame, the tracker %d (max_last)", call, V.NK, t->n_last);
+    return VO_ERR_CAPACITY;
+  }
+  return walk_reserve(t, t->n_last);
+}
+
+// only behind a call that was enqueued (as vo_tracker_set_ref_keyframe commits "only now"): like that call the route
+// replaces the last-frame state, and the host route's reference key-frame is gone
+static void ref_store_commit(vo_tracker *t, const char *call, const vo_kfstore *store) {
+  t->store_call = call;
+  t->ref_vocab = nullptr, t->ref_kf.clear();
+  // the rows hold max_features entries, flag 0 beyond a key-frame's own n (which only the device knows): a following
+  // vo_tracker_track without vo_tracker_set_last_frame would project those dead queries too
+  t->nq_last = vo::kfstore_view(store).NK;
+}
+
+int vo_tracker_track_ref_keyframe_store(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_ref_kf,
+                                        const double *dev_Tcw12, const uint8_t *images, const void *depth, int depth_kind,
+                                        const vo_tracker_params *params, int first_stage_only) {
+  if (!t || !images || depth_kind < 0 || depth_kind > 2 || (depth_kind && !depth)) return VO_ERR_INVALID;
+  VO_CHECK(ref_store_ready(t, "vo_tracker_track_ref_keyframe_store", store, vocab, dev_ref_kf, dev_Tcw12));
+  const vo_tracker::RefStoreArgs A{store, vocab, dev_ref_kf, dev_Tcw12};
+  t->ref_store_args = &A;
+  const int rc = track_host(t, images, depth, depth_kind, params, kRunFront | kRunRefStore | (first_stage_only ? 0u : kRunLocal));
+  t->ref_store_args = nullptr;
+  if (rc == VO_OK) ref_store_commit(t, "vo_tracker_track_ref_keyframe_store", store);
+  return rc;
+}
+
+int vo_tracker_track_ref_keyframe_store_dev(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_ref_kf,
+                                            const double *dev_Tcw12, const uint8_t *dev_images, int image_pitch,
+                                            size_t image_frame_stride, const void *dev_depth, int depth_kind,
+                                            size_t depth_frame_stride, int depth_pitch, const vo_tracker_params *params,
+                                            int first_stage_only) {
+  const FrameInput in{dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch};
+  if (!dev_input_ok(t, in)) return VO_ERR_INVALID;
+  VO_CHECK(ref_store_ready(t, "vo_tracker_track_ref_keyframe_store_dev", store, vocab, dev_ref_kf, dev_Tcw12));
+  const vo_tracker::RefStoreArgs A{store, vocab, dev_ref_kf, dev_Tcw12};
+  t->ref_store_args = &A;
+  const int rc = track_dev(t, in, params, kRunFront | kRunRefStore | (first_stage_only ? 0u : kRunLocal));
+  t->ref_store_args = nullptr;
+  if (rc == VO_OK) ref_store_commit(t, "vo_tracker_track_ref_keyframe_store_dev", store);
+  return rc;
+}
+
 static int reloc_ready(vo_tracker *t) {
   if (!t) return VO_ERR_INVALID;
   if (!t->reloc) {
@@ -1091,8 +1299,9 @@ static int store_route_ready(vo_tracker *t, const char *call, vo_kfdb *db, const
       return VO_ERR_CAPACITY;
     }
   }
+  VO_CHECK(walk_reserve(t, t->cfg.max_reloc_features));
   t->store_call = call;
-  return vo::reloc_store_prepare(t->reloc, db != nullptr, t->st);
+  return vo::reloc_store_prepare(t->reloc, &t->walk, t->d.store_err, db != nullptr, t->st);
 }
 
 static int store_route_host(vo_tracker *t, const vo::RelocStoreArgs &A, const uint8_t *images, const void *depth, int depth_kind,
@@ -1188,17 +1397,17 @@ int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_
       if (dst[k]) dst[k][f] = pi[k];
   }
   const int32_t *flags = reinterpret_cast<const int32_t *>(h + B * 72);
-  const int32_t store_err = vo::reloc_last_was_store(t->reloc) ? flags[2] : 0;  // (the third word is the store routes' only)
+  const int32_t store_err = (t->ref_store || vo::reloc_last_was_store(t->reloc)) ? flags[2] : 0;  // (the third word is the store routes' only)
   if (flags[0] != 0 || flags[1] != 0) {
     // a sticky error flag of a stage is up (dropped key-points, exhausted candidate pools): report and clear it
     VO_CHECK(vo_orb_sync(t->orb));
     VO_CHECK(vo_match_guided_status(t->frames, t->st));
   }
   if (store_err) {  // report and clear
-    VO_HIP_CHECK(hipMemsetAsync(const_cast<int *>(vo::reloc_store_error_flag(t->reloc)), 0, 4, t->st));
+    VO_HIP_CHECK(hipMemsetAsync(t->d.store_err, 0, 4, t->st));
     VO_HIP_CHECK(hipMemsetAsync(t->d.resblk + B * 72 + 8, 0, 4, t->st));
     if (store_err & 2) {
-      vo::set_error("%s: a candidate key-frame number lies outside the store (walked as a bad key-frame)", t->store_call);
+      vo::set_error("%s: a key-frame number lies outside the store (treated as a key-frame without features)", t->store_call);
       return VO_ERR_INVALID;
     }
     vo::set_error("%s: a frame has more candidates than the tracker walks (max_reloc_candidates = %d); the first %d were walked",

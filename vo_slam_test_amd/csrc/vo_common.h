@@ -242,6 +242,7 @@ struct RelocShared {
   double *pose;         // [B][6]
   double *fpoint;       // [B][cap][3]
   uint8_t *fhas, *foutl;
+  uint8_t *fobs;        // [B][cap] the slot's map point has observations
   double *pts, *obs, *isg;
   int *ranges, *index;
   uint8_t *outlier;
@@ -255,6 +256,20 @@ void reloc_destroy(Reloc *r);
 int reloc_set_candidates(Reloc *r, const vo_vocab *vocab, int max_cand, const int32_t *n_cand, const vo_reloc_candidate *cands,
                          hipStream_t st);
 int reloc_run(Reloc *r, const RelocShared &S);
+// trackLocalMap behind a relocalisation (vo_tracker_track_local_map after vo_tracker_relocalize*).  reloc_local_prep: the
+// local points whose id the frame already holds lose their flags (q1_flags = the flags Frame::isInFrame is then run with),
+// `assigned` is cleared, *frame_on [B] = the per-frame query count of the steps in between (-1: the frame's relocalisation
+// failed, it is left out).  The caller runs isInFrame and the search; reloc_local_finish writes the matches into the slots,
+// solves over all non-null slots and writes the counts and the frames' records of the result block.
+struct RelocLocalArgs {
+  int nq, stride;
+  const uint8_t *pf1;
+  uint8_t *q1_flags;
+  const int *ids1;  // or NULL: nothing is skipped
+  const double *p1;
+};
+int reloc_local_prep(Reloc *r, const RelocShared &S, const RelocLocalArgs &L, const int **frame_on);
+int reloc_local_finish(Reloc *r, const RelocShared &S, const RelocLocalArgs &L);
 // device array behind a VO_TRACKER_RELOC_* selector (nullptr: not one of them)
 const void *reloc_selector(const Reloc *r, int what, size_t *bytes);
 
@@ -288,7 +303,8 @@ int kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const int32_
 
 // ---- searchByBoW against key-frames of a store with the common-node walk on the device (match.hip): k_bow_transform and
 // k_featvec build every resident frame's FeatureVector; k_bow_walk writes every (frame, candidate) pair's query list and
-// argument block; k_node_replay runs as in bow_search_resident.  All buffers are sized once from (B, cap, per, NK).
+// argument block; k_node_replay runs as in bow_search_resident.  All buffers are sized once from (B, cap, per, NK).  A
+// tracker owns ONE set, shared by its store routes: relocalisation walks `per` candidates per frame, trackRefKeyFrame one.
 struct BowWalkBufs {
   int B = 0, cap = 0, per = 0, NK = 0;
   Arena mem;
@@ -300,10 +316,12 @@ struct BowWalkBufs {
 int bow_walk_reserve(BowWalkBufs &b, int B, int cap, int per, int NK, hipStream_t st);
 int bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int levelsup, BowWalkBufs &b, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);  // (events around k_featvec)
-// pair p = f * per + c searches key-frame dev_pair_kf[p] of the store (-1: no key-frame, the pair matches nothing)
+// pair p = f * per + c searches key-frame dev_pair_kf[p] of the store (a number outside [0, size): no key-frame, the pair
+// matches nothing); per <= the buffers' `per`.  search_bad: a key-frame flagged bad is searched like any other
+// (trackRefKeyFrame) instead of matching nothing (relocalisation).
 int bow_walk_replay(vo_frames *frames, int B, int per, const KfStoreView &S, const int *dev_pair_kf, float ratio, int check_rot,
                     BowWalkBufs &b, int32_t *dev_assigned, int32_t *dev_n_matches, hipStream_t st, hipEvent_t ev0 = nullptr,
-                    hipEvent_t ev1 = nullptr);  // (events around k_bow_walk)
+                    hipEvent_t ev1 = nullptr, bool search_bad = false);  // (events around k_bow_walk)
 // the FeatureVector of n features from their node ids (device arrays): n_nodes into *dev_n_nodes, node [n] ascending,
 // start [n + 1], feat [n] (the features of a node in index order); n <= 16384
 int featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int *dev_node, int *dev_start, int *dev_feat,
@@ -320,10 +338,12 @@ struct RelocStoreArgs {
   const float *dev_stale;
   hipEvent_t *tev;                   // 8 events (featvec, gather, local ids, walk: begin / end) or NULL
 };
-int reloc_store_prepare(Reloc *r, bool with_db, hipStream_t st);
+// `walk`, `err`: the tracker's BoW walk buffers (reserved by the caller) and its sticky word of the store routes (bit 0:
+// more candidates than the route holds, bit 1: a key-frame number outside the store), shared with trackRefKeyFrame's
+// store route (tracker.hip)
+int reloc_store_prepare(Reloc *r, BowWalkBufs *walk, int *err, bool with_db, hipStream_t st);
 int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A);
-// the sticky word of the store routes (bit 0: more candidates than the route holds, bit 1: a candidate outside the store)
-const int *reloc_store_error_flag(const Reloc *r);
+enum { kStoreErrTooMany = 1, kStoreErrBadId = 2 };
 bool reloc_last_was_store(const Reloc *r);
 
 // vo_set_option's process-wide values as last set, 0 before (vo_common.hip): VO_OPT_BA_GRAPH (ba.hip), VO_OPT_POSE_BLOCK
