@@ -785,9 +785,9 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params);
 /* vo_tracker_track_local_map after vo_tracker_relocalize, _store or _db (and their _dev forms): trackLocalMap as the
  * reference runs it behind a successful relocalization() (visualOdometry.cpp:61, :74, :82-83 -> :726-774, :287-310), on the
  * frame state the relocalisation left (VO_TRACKER_FEATURE_HAS_POINT / _POINTS / _OUTLIER, VO_TRACKER_RELOC_POINT_IDS).  The
- * local map is whatever vo_tracker_set_local_map holds: the caller reads the winners (VO_TRACKER_RELOC_*) and builds it
- * between the two calls; it passes th_radius = 5 (:768; params NULL: 5, 0.8).  vo_tracker_set_local_map_ids: the map-point
- * id of every local point, ids [batch][n] with n = the local map's n, in the id space VO_TRACKER_RELOC_POINT_IDS reports
+ * local map is whatever vo_tracker_set_local_map holds -- the caller reads the winners (VO_TRACKER_RELOC_*) and builds it
+ * between the two calls -- or what vo_tracker_build_local_map has built on the device; the caller passes th_radius = 5
+ * (:768; params NULL: 5, 0.8).  vo_tracker_set_local_map_ids: the map-point id of every local point, ids [batch][n] with n = the local map's n, in the id space VO_TRACKER_RELOC_POINT_IDS reports
  * (the store's global ids after _store / _db, the dense ids after vo_tracker_relocalize; negative: no id).  A local point
  * whose id is held by a non-null, non-outlier slot of its frame is skipped (`mp->visualIdxOfFrame_ == frame id`, :753);
  * the ids belong to the local map they were set for (vo_tracker_set_local_map forgets them), and WITHOUT ids nothing is
@@ -895,6 +895,33 @@ int vo_kfstore_insert_dev(vo_kfstore *s, int n, int bad, const float *dev_angle,
 int vo_kfstore_set_bad(vo_kfstore *s, int keyframe, int bad);
 int vo_kfstore_update_points(vo_kfstore *s, int keyframe, const uint8_t *flags, const double *points, const int32_t *ids,
                              const uint8_t *point_desc, const float *min_distance, const float *max_distance);
+/* What vo_tracker_build_local_map (below) reads of a key-frame beyond its features.  All three are additive: the records,
+ * entry points and results above do not change, and every buffer is sized at creation from (max_keyframes, max_features).
+ * set_graph: the covisibility / spanning-tree links VisualOdometry::updateLocalKeyFrames walks (visualOdometry.cpp:649-689).
+ * neighbors = getBestCovisibleKFs(10) in its order (n_neighbors <= VO_KFSTORE_MAX_NEIGHBORS); children = getChildren() in
+ * ASCENDING KEY-FRAME NUMBER -- the reference's set<KeyFrame*> iterates in pointer order, which no restatement can
+ * reproduce: the rule DESIGN.md section 4e states for pointer-keyed containers (a list that is not strictly ascending is
+ * VO_ERR_INVALID); at most VO_KFSTORE_MAX_CHILDREN children per key-frame, VO_ERR_CAPACITY beyond (nothing is truncated);
+ * parent = getParent() as a key-frame number or -1.  Every id must lie in [0, size), else VO_ERR_INVALID, and nothing
+ * changes on an error.  Until set, a key-frame has no neighbours, no children and no parent.  One copy, synchronises once.
+ * set_graph_batch: the same for the key-frames first .. first + count - 1 in one call: n_neighbors [count], neighbors
+ * [count][VO_KFSTORE_MAX_NEIGHBORS], n_children [count], children [count][VO_KFSTORE_MAX_CHILDREN] (entries beyond the
+ * counts are ignored), parent [count]; everything is validated before anything is copied.
+ * set_normals: MapPoint::normalVector_ of the key-frame's map points, normals [n][3] (n as inserted), a per-feature column
+ * of its own which Frame::isInFrame reads (frame.cpp:176).  THE COLUMN IS ZERO UNTIL SET: a zero normal gives a view
+ * cosine of 0 and fails the `cos > 0.5` gate, so a local point built from such a feature is never searched.
+ * The observation index (no entry point): map-point id -> the key-frames that hold it, in ascending key-frame number;
+ * key-frame k holds id p when one of its features has ids == p and flags bit 0 set.  It stands in for
+ * MapPoint::getObservedKFs() and is rebuilt on the device (sorted keys), lazily, by the first
+ * vo_tracker_build_local_map after an insert, insert_dev or update_points: launches on the store's stream only, no host
+ * synchronisation, no device-to-host copy. */
+#define VO_KFSTORE_MAX_NEIGHBORS 10
+#define VO_KFSTORE_MAX_CHILDREN 64
+int vo_kfstore_set_graph(vo_kfstore *s, int keyframe, int n_neighbors, const int32_t *neighbors, int n_children,
+                         const int32_t *children, int parent);
+int vo_kfstore_set_graph_batch(vo_kfstore *s, int first, int count, const int32_t *n_neighbors, const int32_t *neighbors,
+                               const int32_t *n_children, const int32_t *children, const int32_t *parent);
+int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals /*[n][3]*/);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors
@@ -953,6 +980,40 @@ int vo_tracker_track_ref_keyframe_store_dev(vo_tracker *t, const vo_kfstore *sto
                                             int image_pitch, size_t image_frame_stride, const void *dev_depth, int depth_kind,
                                             size_t depth_frame_stride, int depth_pitch, const vo_tracker_params *params,
                                             int first_stage_only);
+/* VisualOdometry::updateLocalKeyFrames + updateLocalMapPoints (visualOdometry.cpp:595-724) for every frame of the batch,
+ * on the device, from the key-frame store: the step between a store route and vo_tracker_track_local_map.  Valid after
+ * vo_tracker_relocalize_store / _db (and their _dev forms) and after vo_tracker_track_ref_keyframe_store[_dev] with
+ * first_stage_only = 1; after any other route: VO_ERR_INVALID, nothing enqueued.  The slot ids of frame f are what
+ * VO_TRACKER_RELOC_POINT_IDS holds (after a relocalisation), or store.ids[ref_kf[f]][assigned_last[i]] of every slot i
+ * that still holds a point after the culling (reference-key-frame route; there `store` must be the store the route read,
+ * after a relocalisation any store in the same id space serves).  Four steps, all enqueued on the tracker's stream, ordered
+ * against the store's stream by events like the store routes, no host synchronisation, no allocation after the first
+ * call (a later call with a store of more max_keyframes grows the vote buffer):
+ *  1 votes (:598-614): every non-null slot gives one vote to every key-frame that holds its id (the observation index); an
+ *    id in two slots votes twice.  A slot whose id no key-frame holds is `mp->isBad()`: it is nulled (:612) --
+ *    VO_TRACKER_FEATURE_HAS_POINT cleared, its VO_TRACKER_RELOC_POINT_IDS entry -1.
+ *  2 voters (:625-639) in ascending key-frame number (the ordering rule of vo_kfstore_set_graph), key-frames flagged bad
+ *    skipped; the best key-frame is the first with the strictly largest count.
+ *  3 expansion (:641-690) over the ORIGINAL voters in order, stopping once the list holds more than 80: per voter the
+ *    first non-bad unmarked neighbour, the first non-bad unmarked child, the parent if unmarked and not bad.
+ *  4 points (:700-724): the list's key-frames in list order, each one's features in index order with bit 0 set, first
+ *    occurrence of an id wins; written straight into the local-map arrays (position, normal, min / max distance, the
+ *    store's point_desc, flags = the feature's bits 0 and 1, the ids of vo_tracker_set_local_map_ids).  The local map's n
+ *    becomes max_local; entries beyond a frame's count get flags 0 and id -1.  link: -1 after a relocalisation (the id
+ *    skip acts there); on the reference-key-frame route the lowest feature index of the frame's reference key-frame that
+ *    holds the same id with bit 0 set, or -1 -- vo_tracker_track_local_map then runs unchanged on either route.
+ * Deviations, all stated: (a) a frame without voters gets an EMPTY local map and best key-frame -1, where the reference
+ * returns early (:616) and keeps the previous frame's list, which the independent frames of a batch do not have; so does a
+ * frame with VO_TRACK_RELOC_FAILED, of which nothing else is touched.  (b) The expansion walks the original voters only:
+ * the reference caches the end iterator before its pushes (:641) and stays defined only while reserve(3 * voters) holds.
+ * (c) The list holds VO_TRACKER_LOCAL_MAX_KEYFRAMES = 84 entries: 80 voters + 3 is the most an expansion reaches, and a
+ * frame with 81 .. 84 voters keeps them all (no expansion, :643); a frame with MORE voters keeps the first 84 in key-frame
+ * order, VO_TRACKER_LOCAL_N_KEYFRAMES reports its true count and vo_tracker_results the sticky VO_ERR_CAPACITY (the best
+ * key-frame is still taken over all voters).  (d) A frame with more distinct points than max_local keeps the first
+ * max_local in order, VO_TRACKER_LOCAL_N_POINTS reports the true count: sticky VO_ERR_CAPACITY as well; every other
+ * frame's outputs are valid.  The addVisible / addFound counters are not kept. */
+#define VO_TRACKER_LOCAL_MAX_KEYFRAMES 84
+int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store);
 /* With vo_tracker_set_timing on, a store route records HIP events around its four new stages: 0 k_featvec, 1 the gather
  * from the store, 2 the id compaction, 3 k_bow_walk.  Synchronises and returns the milliseconds of the LAST such call
  * (VO_ERR_INVALID when none has run with timing on).  tools/reloc_db_bench.py. */
@@ -990,7 +1051,19 @@ enum {
                                         PnP correspondence, 1 = correspondence, RANSAC outlier, 2 = RANSAC inlier */
   /* after vo_tracker_relocalize_store / _db */
   VO_TRACKER_RELOC_CANDIDATES = 21,  /* int32 [batch][max_reloc_candidates]: the key-frame numbers walked, -1 beyond them */
-  VO_TRACKER_RELOC_N_CANDIDATES = 22 /* int32 [batch]: the frame's true candidate count (may exceed max_reloc_candidates) */
+  VO_TRACKER_RELOC_N_CANDIDATES = 22, /* int32 [batch]: the frame's true candidate count (may exceed max_reloc_candidates) */
+  /* after vo_tracker_build_local_map */
+  VO_TRACKER_LOCAL_KEYFRAMES = 23,   /* int32 [batch][VO_TRACKER_LOCAL_MAX_KEYFRAMES]: localKeyframes_ in list order, -1 beyond */
+  VO_TRACKER_LOCAL_N_KEYFRAMES = 24, /* int32 [batch]: the list's length (the true voter count where it exceeds 84) */
+  VO_TRACKER_LOCAL_N_POINTS = 25,    /* int32 [batch]: distinct local points of the frame (may exceed max_local) */
+  VO_TRACKER_LOCAL_REF_KF = 26,      /* int32 [batch]: keyframe_best (:692-696), -1 without voters */
+  /* the local map as it stands ([batch][max_local]; set by vo_tracker_set_local_map / _ids or built) */
+  VO_TRACKER_LOCAL_POINT_IDS = 27,   /* int32: map-point id per local point, -1 beyond a built frame's count */
+  VO_TRACKER_LOCAL_POINTS = 28, VO_TRACKER_LOCAL_NORMALS = 29, /* double [..][3] */
+  VO_TRACKER_LOCAL_MIN_DISTANCE = 30, VO_TRACKER_LOCAL_MAX_DISTANCE = 31, /* float */
+  VO_TRACKER_LOCAL_DESC = 32,        /* uint8 [..][32] */
+  VO_TRACKER_LOCAL_MAP_FLAGS = 33,   /* uint8: the flags as set / built (VO_TRACKER_LOCAL_FLAGS: after isInFrame) */
+  VO_TRACKER_LOCAL_LINK = 34         /* int32 */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 int vo_tracker_sync(vo_tracker *t);

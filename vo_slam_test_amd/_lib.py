@@ -54,6 +54,7 @@ SYMBOLS = [
     "vo_kfstore_set_bad", "vo_kfstore_update_points", "vo_tracker_relocalize_store", "vo_tracker_relocalize_store_dev",
     "vo_tracker_relocalize_db", "vo_tracker_relocalize_db_dev", "vo_tracker_get_reloc_timing",
     "vo_tracker_track_ref_keyframe_store", "vo_tracker_track_ref_keyframe_store_dev", "vo_tracker_set_local_map_ids",
+    "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -461,7 +462,9 @@ class Tracker:
     (ASSIGNED_LAST, ASSIGNED_LOCAL, POSE_FIRST, INLIERS_FIRST, OBSERVED_INLIERS_FIRST, FEATURE_HAS_POINT, FEATURE_POINTS,
      LOCAL_FLAGS, LOCAL_U, LOCAL_V, LOCAL_UR, LOCAL_LEVEL, LOCAL_VIEWCOS, KEYPOINT_COUNTS, FEATURE_OUTLIER,
      RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK,
-     RELOC_CANDIDATES, RELOC_N_CANDIDATES) = range(23)
+     RELOC_CANDIDATES, RELOC_N_CANDIDATES, LOCAL_KEYFRAMES, LOCAL_N_KEYFRAMES, LOCAL_N_POINTS, LOCAL_REF_KF, LOCAL_POINT_IDS,
+     LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK) = range(35)
+    LOCAL_MAX_KEYFRAMES = 84
     RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
     FEW_MATCHES, FEW_INLIERS, RELOC_FAILED = 1, 2, 4
@@ -712,6 +715,13 @@ class Tracker:
             check(lib().vo_tracker_relocalize_db(*head, _p(img), _p(dp), kind, None), "vo_tracker_relocalize_db")
         self._reloc_keep = (db, store, vocab, stale_score)
 
+    def build_local_map(self, store):
+        """vo_tracker_build_local_map: updateLocalKeyFrames + updateLocalMapPoints on the device from `store`, after
+        relocalize_store / relocalize_db or track_ref_keyframe_store(first_stage_only=True); track_local_map follows without
+        set_local_map.  Asynchronous; get(LOCAL_KEYFRAMES / LOCAL_N_KEYFRAMES / LOCAL_N_POINTS / LOCAL_REF_KF / LOCAL_*) after."""
+        check(lib().vo_tracker_build_local_map(self._h, store._h), "vo_tracker_build_local_map")
+        self._local_store_keep = store  # the enqueued kernels read it
+
     def get_reloc_timing(self):
         """milliseconds of the four new stages of the last store route run with set_timing(True)"""
         ms = (C.c_double * len(self.RELOC_STAGES))()
@@ -741,7 +751,13 @@ class Tracker:
             self.RELOC_POINT_IDS: ((B, cap), np.int32), self.RELOC_BOW_MATCHES: ((B, mrc), np.int32),
             self.RELOC_PNP_INLIERS: ((B, mrc), np.int32), self.RELOC_OUTCOME: ((B, mrc), np.int32),
             self.RELOC_PNP_MASK: ((B, mrc, cap), np.uint8), self.RELOC_CANDIDATES: ((B, mrc), np.int32),
-            self.RELOC_N_CANDIDATES: ((B,), np.int32)}[what]
+            self.RELOC_N_CANDIDATES: ((B,), np.int32),
+            self.LOCAL_KEYFRAMES: ((B, self.LOCAL_MAX_KEYFRAMES), np.int32), self.LOCAL_N_KEYFRAMES: ((B,), np.int32),
+            self.LOCAL_N_POINTS: ((B,), np.int32), self.LOCAL_REF_KF: ((B,), np.int32),
+            self.LOCAL_POINT_IDS: ((B, max(nl, 1)), np.int32), self.LOCAL_POINTS: ((B, max(nl, 1), 3), np.float64),
+            self.LOCAL_NORMALS: ((B, max(nl, 1), 3), np.float64), self.LOCAL_MIN_DISTANCE: ((B, max(nl, 1)), np.float32),
+            self.LOCAL_MAX_DISTANCE: ((B, max(nl, 1)), np.float32), self.LOCAL_DESC: ((B, max(nl, 1), 32), np.uint8),
+            self.LOCAL_MAP_FLAGS: ((B, max(nl, 1)), np.uint8), self.LOCAL_LINK: ((B, max(nl, 1)), np.int32)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out
@@ -1570,6 +1586,36 @@ class KeyFrameStore:
         check(lib().vo_kfstore_update_points(self._h, int(keyframe), _p(a(flags, np.uint8)), _p(a(points, np.float64)), _p(a(ids, np.int32)),
                                              _p(a(point_desc, np.uint8)), _p(a(min_dist, np.float32)), _p(a(max_dist, np.float32))),
               "vo_kfstore_update_points")
+
+    MAX_NEIGHBORS, MAX_CHILDREN = 10, 64
+
+    def set_graph(self, keyframe, neighbors, children, parent=-1):
+        """the links build_local_map walks: neighbors = getBestCovisibleKFs(10) in its order, children in ascending
+        key-frame number (at most MAX_CHILDREN), parent a key-frame number or -1"""
+        nb, ch = np.ascontiguousarray(neighbors, np.int32), np.ascontiguousarray(children, np.int32)
+        check(lib().vo_kfstore_set_graph(self._h, int(keyframe), len(nb), _p(nb), len(ch), _p(ch), int(parent)), "vo_kfstore_set_graph")
+
+    def set_graph_batch(self, first, neighbors, children, parents):
+        """set_graph for the key-frames first, first + 1, ... in one call (lists of lists, a list of parents)"""
+        count = len(parents)
+        for name, lists, cap in (("neighbours", neighbors, self.MAX_NEIGHBORS), ("children", children, self.MAX_CHILDREN)):
+            if any(len(x) > cap for x in lists):
+                raise VoError(f"vo_kfstore_set_graph_batch failed with status -4: more than {cap} {name} for a key-frame")
+        n_nb = np.array([len(x) for x in neighbors], np.int32)
+        n_ch = np.array([len(x) for x in children], np.int32)
+        nb = np.full((count, self.MAX_NEIGHBORS), -1, np.int32)
+        ch = np.full((count, self.MAX_CHILDREN), -1, np.int32)
+        for k in range(count):
+            nb[k, :n_nb[k]] = neighbors[k]
+            ch[k, :n_ch[k]] = children[k]
+        par = np.ascontiguousarray(parents, np.int32)   # (named: the array must outlive the call)
+        check(lib().vo_kfstore_set_graph_batch(self._h, int(first), count, _p(n_nb), _p(nb), _p(n_ch), _p(ch), _p(par)),
+              "vo_kfstore_set_graph_batch")
+
+    def set_normals(self, keyframe, normals):
+        """MapPoint::normalVector_ per feature [n, 3] (n as inserted); zero until set, and a zero normal fails isInFrame"""
+        nrm = np.ascontiguousarray(normals, np.float64)
+        check(lib().vo_kfstore_set_normals(self._h, int(keyframe), _p(nrm)), "vo_kfstore_set_normals")
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -16,6 +16,66 @@ __global__ void k_kfstore_bad(int *head, int bad) {
   if (threadIdx.x == 0) head[1] = bad;
 }
 
+// ---- the observation index: one 64-bit key per flagged feature of the store, id << 32 | entry,
+// sorted by a device-wide bitonic network (fixed: the result is a function of the keys alone, and the keys are distinct).
+constexpr int kObsChunk = 2048;  // keys a workgroup of 256 sorts in LDS
+
+__global__ __launch_bounds__(256) void k_obs_fill(vo::KfStoreView V, unsigned long long *keys, int n_keys) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= n_keys) return;
+  const int k = e / V.NK, i = e - k * V.NK;
+  unsigned long long key = ~0ull;
+  if (k < V.size && i < min(max(vo::kf_head(V, k)[0], 0), V.NK) && (vo::kf_sec<uint8_t>(V, k, V.o_flags)[i] & 1)) {
+    const int id = vo::kf_sec<int>(V, k, V.o_ids)[i];
+    if (id >= 0) key = ((unsigned long long)(unsigned)id << 32) | (unsigned)e;
+  }
+  keys[e] = key;
+}
+
+// the steps j = min(k / 2, kObsChunk / 2) .. 1 of the stages k = k_lo .. k_hi on one chunk of kObsChunk keys, in LDS; the
+// direction of a compare-exchange comes from the key's GLOBAL position
+__global__ __launch_bounds__(256) void k_obs_sort_local(unsigned long long *keys, int k_lo, int k_hi) {
+  __shared__ unsigned long long sk[kObsChunk];
+  const int base = blockIdx.x * kObsChunk, tid = threadIdx.x;
+  for (int i = tid; i < kObsChunk; i += 256) sk[i] = keys[base + i];
+  for (int k = k_lo; k <= k_hi && k > 0; k <<= 1)
+    for (int j = min(k >> 1, kObsChunk >> 1); j > 0; j >>= 1) {
+      __syncthreads();
+      for (int t = tid; t < kObsChunk / 2; t += 256) {
+        const int i = 2 * t - (t & (j - 1)), l = i + j;
+        const unsigned long long a = sk[i], b = sk[l];
+        if ((a > b) == (((base + i) & k) == 0)) sk[i] = b, sk[l] = a;
+      }
+    }
+  __syncthreads();
+  for (int i = tid; i < kObsChunk; i += 256) keys[base + i] = sk[i];
+}
+
+// one step (k, j) with j >= kObsChunk: partners lie in different chunks
+__global__ __launch_bounds__(256) void k_obs_sort_global(unsigned long long *keys, int n_keys, int k, int j) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_keys / 2) return;
+  const int i = 2 * t - (t & (j - 1)), l = i + j;
+  const unsigned long long a = keys[i], b = keys[l];
+  if ((a > b) == ((i & k) == 0)) keys[i] = b, keys[l] = a;
+}
+
+// run[entry] = position of the first key that carries the entry's id (binary search below the key's own position)
+__global__ __launch_bounds__(256) void k_obs_runs(const unsigned long long *keys, int n_keys, int *run) {
+  const int s = blockIdx.x * 256 + threadIdx.x;
+  if (s >= n_keys) return;
+  const unsigned long long key = keys[s];
+  if (key == ~0ull) return;
+  const unsigned long long first = key & 0xffffffff00000000ull;
+  int lo = 0, hi = s;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (keys[mid] < first) lo = mid + 1;
+    else hi = mid;
+  }
+  run[(unsigned)(key & 0xffffffffu)] = lo;
+}
+
 size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 }  // namespace
@@ -28,6 +88,11 @@ struct vo_kfstore {
   vo::OwnedDevBuf rec;
   vo::OwnedPinnedBuf stage;
   std::vector<int> n;  // features per key-frame (host copy: update_points' lengths)
+  // what vo_tracker_build_local_map reads beyond the records (vo_common.h: KfObsView)
+  vo::OwnedDevBuf graph, normals, okeys, orun;
+  int okeys_cap = 0;      // keys the index holds: the power of two above max_kf * NK, at least one chunk
+  bool obs_dirty = true;  // an insert or update_points has happened since the index was built
+  int obs_n = 0;          // keys the built index spans (a power of two covering size * NK)
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -53,7 +118,65 @@ int kfstore_order_after(const vo_kfstore *s, hipStream_t st) {
   return VO_OK;
 }
 
+int kfstore_obs_view(vo_kfstore *s, KfObsView *out) {
+  if (!s || !out) return VO_ERR_INVALID;
+  if (s->obs_dirty) {
+    int n = kObsChunk;
+    while ((long long)n < (long long)s->size * s->NK) n <<= 1;  // (<= okeys_cap: size <= max_kf)
+    unsigned long long *keys = s->okeys.as<unsigned long long>();
+    hipStream_t st = s->st;
+    KfStoreView V = kfstore_view(s);
+    hipLaunchKernelGGL(k_obs_fill, dim3(n / 256), dim3(256), 0, st, V, keys, n);
+    hipLaunchKernelGGL(k_obs_sort_local, dim3(n / kObsChunk), dim3(256), 0, st, keys, 2, kObsChunk);
+    for (int k = 2 * kObsChunk; k <= n && k > 0; k <<= 1) {
+      for (int j = k >> 1; j >= kObsChunk; j >>= 1)
+        hipLaunchKernelGGL(k_obs_sort_global, dim3(n / 512), dim3(256), 0, st, keys, n, k, j);
+      hipLaunchKernelGGL(k_obs_sort_local, dim3(n / kObsChunk), dim3(256), 0, st, keys, k, k);
+    }
+    hipLaunchKernelGGL(k_obs_runs, dim3(n / 256), dim3(256), 0, st, (const unsigned long long *)keys, n, s->orun.as<int>());
+    VO_HIP_CHECK(hipGetLastError());
+    s->obs_n = n, s->obs_dirty = false;
+  }
+  *out = KfObsView{s->graph.as<int>(), s->normals.as<double>(), s->okeys.as<unsigned long long>(), s->orun.as<int>(), s->obs_n};
+  return VO_OK;
+}
+
 }  // namespace vo
+
+namespace {
+
+// one key-frame's graph row (vo_common.h: kKfGraphInts) from the caller's lists, validated against [0, size)
+int graph_row(const vo_kfstore *s, const char *call, int keyframe, int n_nb, const int32_t *nb, int n_ch, const int32_t *ch, int parent,
+              int32_t *row) {
+  if (n_nb < 0 || n_ch < 0 || (n_nb > 0 && !nb) || (n_ch > 0 && !ch) || parent < -1 || parent >= s->size) {
+    vo::set_error("%s: key-frame %d: a negative count, a missing list, or parent %d outside [-1, %d)", call, keyframe, parent, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (n_nb > vo::kKfGraphNb || n_ch > vo::kKfGraphCh) {
+    vo::set_error("%s: key-frame %d: %d neighbours / %d children, the store holds %d / %d per key-frame", call, keyframe, n_nb, n_ch,
+                  vo::kKfGraphNb, vo::kKfGraphCh);
+    return VO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < vo::kKfGraphInts; i++) row[i] = -1;
+  row[0] = n_nb, row[1] = n_ch, row[2] = parent, row[3] = 0;
+  for (int i = 0; i < n_nb; i++) {
+    if (nb[i] < 0 || nb[i] >= s->size) {
+      vo::set_error("%s: key-frame %d: neighbour %d outside [0, %d)", call, keyframe, nb[i], s->size);
+      return VO_ERR_INVALID;
+    }
+    row[4 + i] = nb[i];
+  }
+  for (int i = 0; i < n_ch; i++) {
+    if (ch[i] < 0 || ch[i] >= s->size || (i > 0 && ch[i] <= ch[i - 1])) {
+      vo::set_error("%s: key-frame %d: child %d outside [0, %d) or not in ascending order", call, keyframe, ch[i], s->size);
+      return VO_ERR_INVALID;
+    }
+    row[16 + i] = ch[i];
+  }
+  return VO_OK;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -96,6 +219,27 @@ int vo_kfstore_create(vo_kfstore **out, int max_keyframes, int max_features) {
     return fail(VO_ERR_HIP);
   }
   s->n.reserve((size_t)max_keyframes);
+  // the graph (no neighbours, no children, no parent until set), the normals (zero until set) and the observation index
+  {
+    const size_t ents = (size_t)max_keyframes * NK;
+    if (ents > ((size_t)1 << 30)) {
+      vo::set_error("vo_kfstore_create: %zu feature entries, the observation index addresses 2^30", ents);
+      return fail(VO_ERR_CAPACITY);
+    }
+    int cap = kObsChunk;
+    while ((size_t)cap < ents) cap <<= 1;
+    s->okeys_cap = cap;
+    std::vector<int32_t> rows((size_t)max_keyframes * vo::kKfGraphInts, -1);
+    for (int k = 0; k < max_keyframes; k++) rows[(size_t)k * vo::kKfGraphInts] = rows[(size_t)k * vo::kKfGraphInts + 1] = 0;
+    if (s->graph.reserve(rows.size() * 4) != VO_OK || s->normals.reserve(ents * 24) != VO_OK || s->okeys.reserve((size_t)cap * 8) != VO_OK ||
+        s->orun.reserve((size_t)cap * 4) != VO_OK)
+      return fail(VO_ERR_HIP);
+    if (hipMemcpy(s->graph.p, rows.data(), rows.size() * 4, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(s->normals.p, 0, ents * 24) != hipSuccess || hipMemset(s->orun.p, 0, (size_t)cap * 4) != hipSuccess) {
+      vo::set_error("vo_kfstore_create: initialising the graph and the normals failed");
+      return fail(VO_ERR_HIP);
+    }
+  }
   *out = s;
   return VO_OK;
 }
@@ -179,6 +323,7 @@ int vo_kfstore_insert(vo_kfstore *s, const vo_reloc_candidate *kf, int32_t *inde
   if (index) *index = s->size;
   s->n.push_back(K.n);
   s->size++;
+  s->obs_dirty = true;
   return VO_OK;
 }
 
@@ -226,6 +371,7 @@ int vo_kfstore_insert_dev(vo_kfstore *s, int n, int bad, const float *dev_angle,
   if (index) *index = s->size;
   s->n.push_back(n);
   s->size++;
+  s->obs_dirty = true;
   return VO_OK;
 }
 
@@ -266,8 +412,44 @@ int vo_kfstore_update_points(vo_kfstore *s, int keyframe, const uint8_t *flags, 
   VO_CHECK(up(V.o_pdesc, n * 32));
   VO_CHECK(up(V.o_mind, n * 4));
   VO_CHECK(up(V.o_maxd, n * 4));
+  s->obs_dirty = true;
   VO_HIP_CHECK(hipStreamSynchronize(s->st));
   return VO_OK;
+}
+
+int vo_kfstore_set_graph(vo_kfstore *s, int keyframe, int n_neighbors, const int32_t *neighbors, int n_children,
+                         const int32_t *children, int parent) {
+  if (!s || keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  int32_t row[vo::kKfGraphInts];
+  VO_CHECK(graph_row(s, "vo_kfstore_set_graph", keyframe, n_neighbors, neighbors, n_children, children, parent, row));
+  const char *W = "vo_kfstore_set_graph";
+  VO_CHECK(vo::copy_h2d(s->graph.as<int>() + (size_t)keyframe * vo::kKfGraphInts, row, sizeof(row), s->st, W));
+  return vo::stream_sync(s->st, W);  // (row is a local: the copy must have read it)
+}
+
+int vo_kfstore_set_graph_batch(vo_kfstore *s, int first, int count, const int32_t *n_neighbors, const int32_t *neighbors,
+                               const int32_t *n_children, const int32_t *children, const int32_t *parent) {
+  if (!s || first < 0 || count < 0 || first + (long long)count > s->size ||
+      (count > 0 && (!n_neighbors || !neighbors || !n_children || !children || !parent)))
+    return VO_ERR_INVALID;
+  if (count == 0) return VO_OK;
+  std::vector<int32_t> rows((size_t)count * vo::kKfGraphInts);
+  for (int k = 0; k < count; k++)
+    VO_CHECK(graph_row(s, "vo_kfstore_set_graph_batch", first + k, n_neighbors[k], neighbors + (size_t)k * vo::kKfGraphNb, n_children[k],
+                       children + (size_t)k * vo::kKfGraphCh, parent[k], rows.data() + (size_t)k * vo::kKfGraphInts));
+  const char *W = "vo_kfstore_set_graph_batch";
+  VO_CHECK(vo::copy_h2d(s->graph.as<int>() + (size_t)first * vo::kKfGraphInts, rows.data(), rows.size() * 4, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals) {
+  if (!s || keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!normals) return VO_ERR_INVALID;
+  const char *W = "vo_kfstore_set_normals";
+  VO_CHECK(vo::copy_h2d(s->normals.as<double>() + (size_t)keyframe * s->NK * 3, normals, n * 24, s->st, W));
+  return vo::stream_sync(s->st, W);
 }
 
 }  // extern "C"

@@ -1097,6 +1097,12 @@ int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A) {
 
 bool reloc_last_was_store(const Reloc *r) { return r && r->last_store; }
 
+int reloc_frame_ids(Reloc *r, int **fid, const int **winner) {
+  if (!r || !r->last_store || !fid || !winner) return VO_ERR_INVALID;
+  *fid = r->s.fid_g, *winner = r->winner;
+  return VO_OK;
+}
+
 // ---- trackLocalMap behind a relocalisation --------------------------------------------------------------------------
 namespace {
 LocalDev local_dev(Reloc *r, const RelocLocalArgs &L) {

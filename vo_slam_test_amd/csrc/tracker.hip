@@ -372,6 +372,7 @@ struct vo_tracker {
     uint8_t *resblk;                          // k_track_pack's block (72 bytes per frame + 2 flags)
     int *retry_nq;                            // [B] query counts of the retry pass
     int *store_err;                           // the store routes' sticky word (vo_common.h: kStoreErr*)
+    int *ref_kf;                              // [B] the key-frame numbers of the last trackRefKeyFrame from the store
     int *assigned, *assigned_first, *nm, *nm_first, *ninl, *ninl_first, *nobs_first, *ntracked, *status;
     double *fpoint, *pts, *obs, *isg;  // per-feature frame state [B][cap] and the pose problem gathered from it
     uint8_t *fhas, *fobs, *foutl, *outlier;
@@ -385,6 +386,12 @@ struct vo_tracker {
   bool have_link = false;
   bool have_local = false, have_ids = false;  // vo_tracker_set_local_map / _ids have been called (the ids belong to that local map)
   bool last_reloc = false;                    // the last front ran a relocalisation route: track_local_map takes the hand-over
+  // vo_tracker_build_local_map: which slot ids the last front left (0: none; 1: a relocalisation from the store; 2:
+  // trackRefKeyFrame from the store, first stage only); its buffers, laid out by the first call for the store's max_keyframes
+  int ids_route = 0;
+  vo::Arena lm_mem;
+  int lm_max_kf = 0;
+  struct { int *votes, *lkf, *n_kf, *best, *n_pts; } lm{};
   // a search's matches that the next solve_pose writes into the frame's slots (k_track_scatter_gather)
   struct { const int32_t *assigned = nullptr; const double *qpoints = nullptr; const uint8_t *qflags = nullptr; int stride = 0; } pend;
   int first_min_matches = 20;
@@ -467,6 +474,7 @@ void vo_tracker::layout(vo::Arena &a) {
   a.take(d.retry_nq, B * 4 + 64);
   a.take(d.foutl, B * cap + 64);
   a.take(d.store_err, 64);
+  a.take(d.ref_kf, B * 4 + 64);
 }
 
 namespace {
@@ -680,6 +688,8 @@ int stage_ref_keyframe_store(vo_tracker *t, const vo_tracker_params &P) {
   hipLaunchKernelGGL(k_track_prep, dim3(B), dim3(256), 0, st, t->cap, t->n_last, d.assigned, d.fhas, d.fobs, d.last_matched, d.pose0,
                      d.pose);
   VO_HIP_CHECK(hipGetLastError());
+  // (the caller's numbers are free once the stream has passed this call: vo_tracker_build_local_map reads the copy)
+  VO_HIP_CHECK(hipMemcpyAsync(d.ref_kf, A.ref_kf, (size_t)B * 4, hipMemcpyDeviceToDevice, st));
   VO_CHECK(vo::bow_walk_replay(t->frames, B, 1, S, A.ref_kf, P.ref_ratio > 0.f ? P.ref_ratio : 0.7f, 1, t->walk, d.assigned,
                                d.nm_first, st, nullptr, nullptr, true));
   VO_CHECK(vo::kfstore_order_after(A.store, st));
@@ -828,6 +838,7 @@ int run_pipeline(vo_tracker *t, const FrameInput &in, const vo_tracker_params *p
   if (run & kRunFront) {
     t->ref_store = (run & kRunRefStore) != 0;
     t->last_reloc = (run & kRunReloc) != 0;
+    t->ids_route = ((run & kRunReloc) && t->store_args) ? 1 : ((run & kRunRefStore) && !(run & kRunLocal)) ? 2 : 0;
     VO_CHECK(stage_front(t, in, host_depth));
   }
   if (run & kRunReloc) return stage_reloc(t);
@@ -929,6 +940,9 @@ int vo_tracker_create(vo_tracker **out, const vo_tracker_config *cfg) {
                                  (float)cfg->height)) != VO_OK)
     return fail(rc);
   if ((rc = t->mem.build([&](vo::Arena &a) { t->layout(a); }, "vo_tracker_create")) != VO_OK) return fail(rc);
+  // rows that no route writes for a frame it leaves out (a failed relocalisation) read as zero in every tracker, whatever
+  // the allocator handed back
+  if (hipMemset(t->mem.block, 0, t->mem.bytes ? t->mem.bytes : 4096) != hipSuccess) return fail(VO_ERR_HIP);
   if ((rc = t->kps.reserve((size_t)t->B * t->kcap * sizeof(vo_keypoint))) != VO_OK || (rc = t->desc.reserve((size_t)t->B * t->kcap * 32)) != VO_OK)
     return fail(rc);
   t->d.kps = t->kps.as<vo_keypoint>(), t->d.desc = t->desc.as<uint8_t>();
@@ -1356,6 +1370,65 @@ int vo_tracker_relocalize_db_dev(vo_tracker *t, vo_kfdb *db, const vo_kfstore *s
   return store_route_dev(t, A, {dev_images, image_pitch, image_frame_stride, dev_depth, depth_kind, depth_frame_stride, depth_pitch}, params);
 }
 
+int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store) {
+  if (!t || !store) return VO_ERR_INVALID;
+  // everything is checked before anything is enqueued
+  if (!t->have_result || t->ids_route == 0) {
+    vo::set_error("vo_tracker_build_local_map: the last route left no map-point ids (valid after vo_tracker_relocalize_store / _db and "
+                  "vo_tracker_track_ref_keyframe_store with first_stage_only = 1)");
+    return VO_ERR_INVALID;
+  }
+  if (t->cfg.max_local < 1) {
+    vo::set_error("vo_tracker_build_local_map: the tracker holds no local points (max_local = 0)");
+    return VO_ERR_INVALID;
+  }
+  const vo::KfStoreView V = vo::kfstore_view(store);
+  if (t->ids_route == 2 && V.NK > t->n_last) {
+    vo::set_error("vo_tracker_build_local_map: the store holds %d features per key-frame, the tracker %d (max_last)", V.NK, t->n_last);
+    return VO_ERR_CAPACITY;
+  }
+  int *fid = nullptr;
+  const int *winner = nullptr;
+  if (t->ids_route == 1) VO_CHECK(vo::reloc_frame_ids(t->reloc, &fid, &winner));
+  hipStream_t st = t->st;
+  if (V.max_kf > t->lm_max_kf) {  // the first call, or a store of more key-frames than any before
+    if (t->lm_max_kf) VO_HIP_CHECK(hipStreamSynchronize(st));  // (growing frees the block an enqueued call may still use)
+    const size_t B = t->B;
+    t->lm = {};
+    t->lm_max_kf = 0;
+    VO_CHECK(t->lm_mem.build(
+        [&](vo::Arena &a) {
+          a.take(t->lm.votes, B * (size_t)V.max_kf * 4);
+          a.take(t->lm.lkf, B * VO_TRACKER_LOCAL_MAX_KEYFRAMES * 4);
+          a.take(t->lm.n_kf, B * 4 + 64);
+          a.take(t->lm.best, B * 4 + 64);
+          a.take(t->lm.n_pts, B * 4 + 64);
+        },
+        "vo_tracker_build_local_map"));
+    t->lm_max_kf = V.max_kf;
+  }
+  vo::LocalMapArgs A{};
+  VO_CHECK(vo::kfstore_obs_view(store, &A.O));  // (rebuilds the observation index on the store's stream when it is stale)
+  VO_CHECK(vo::kfstore_order_before(store, st));
+  const vo_tracker::Arrays &d = t->d;
+  A.S = vo::kfstore_view(store);
+  A.B = t->B, A.cap = t->cap, A.max_local = t->cfg.max_local, A.stride = t->n_local;
+  A.fn = vo::frame_store_view(t->frames).n;
+  A.winner = winner, A.sid = fid;
+  if (t->ids_route == 2) A.ref_kf = d.ref_kf, A.assigned = d.assigned_first;
+  A.fhas = d.fhas, A.fobs = d.fobs;
+  A.votes = t->lm.votes, A.lkf = t->lm.lkf, A.n_kf = t->lm.n_kf, A.best = t->lm.best, A.n_pts = t->lm.n_pts;
+  A.err = d.store_err;
+  A.p1 = d.p1, A.nrm1 = d.nrm1, A.mind1 = d.mind1, A.maxd1 = d.maxd1, A.pf1 = d.pf1, A.desc1 = d.q1_desc, A.link1 = d.link1, A.ids1 = d.ids1;
+  VO_CHECK(vo::local_map_build(A, st));
+  // the sticky word into the result block (its third flag), as the store routes leave it
+  VO_HIP_CHECK(hipMemcpyAsync(d.resblk + (size_t)t->B * 72 + 8, d.store_err, 4, hipMemcpyDeviceToDevice, st));
+  VO_CHECK(vo::kfstore_order_after(store, st));
+  t->nq_local = t->cfg.max_local;
+  t->have_local = true, t->have_ids = true, t->have_link = t->ids_route == 2;
+  return VO_OK;
+}
+
 int vo_tracker_get_reloc_timing(vo_tracker *t, double *ms) {
   if (!t || !ms) return VO_ERR_INVALID;
   if (!t->rtimed) {
@@ -1410,6 +1483,12 @@ int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_
       vo::set_error("%s: a key-frame number lies outside the store (treated as a key-frame without features)", t->store_call);
       return VO_ERR_INVALID;
     }
+    if (store_err & (vo::kStoreErrLocalPoints | vo::kStoreErrLocalKfs)) {
+      vo::set_error("vo_tracker_build_local_map: a frame has more distinct local points than max_local = %d, or more voting key-frames "
+                    "than %d; the first of them in order were kept (VO_TRACKER_LOCAL_N_POINTS / _N_KEYFRAMES hold the true counts)",
+                    t->cfg.max_local, VO_TRACKER_LOCAL_MAX_KEYFRAMES);
+      return VO_ERR_CAPACITY;
+    }
     vo::set_error("%s: a frame has more candidates than the tracker walks (max_reloc_candidates = %d); the first %d were walked",
                   t->store_call, t->cfg.max_reloc_candidates, t->cfg.max_reloc_candidates);
     return VO_ERR_CAPACITY;
@@ -1454,7 +1533,23 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     case VO_TRACKER_LOCAL_VIEWCOS: b = t->d.q1_viewcos, bytes = B * (size_t)t->n_local * 4; break;
     case VO_TRACKER_KEYPOINT_COUNTS: b = t->d.cnt, bytes = B * 4; break;
     case VO_TRACKER_FEATURE_OUTLIER: b = t->d.foutl, bytes = B * cap; break;
+    case VO_TRACKER_LOCAL_KEYFRAMES: b = t->lm.lkf, bytes = B * VO_TRACKER_LOCAL_MAX_KEYFRAMES * 4; break;
+    case VO_TRACKER_LOCAL_N_KEYFRAMES: b = t->lm.n_kf, bytes = B * 4; break;
+    case VO_TRACKER_LOCAL_N_POINTS: b = t->lm.n_pts, bytes = B * 4; break;
+    case VO_TRACKER_LOCAL_REF_KF: b = t->lm.best, bytes = B * 4; break;
+    case VO_TRACKER_LOCAL_POINT_IDS: b = t->d.ids1, bytes = B * (size_t)t->n_local * 4; break;
+    case VO_TRACKER_LOCAL_POINTS: b = t->d.p1, bytes = B * (size_t)t->n_local * 24; break;
+    case VO_TRACKER_LOCAL_NORMALS: b = t->d.nrm1, bytes = B * (size_t)t->n_local * 24; break;
+    case VO_TRACKER_LOCAL_MIN_DISTANCE: b = t->d.mind1, bytes = B * (size_t)t->n_local * 4; break;
+    case VO_TRACKER_LOCAL_MAX_DISTANCE: b = t->d.maxd1, bytes = B * (size_t)t->n_local * 4; break;
+    case VO_TRACKER_LOCAL_DESC: b = t->d.q1_desc, bytes = B * (size_t)t->n_local * 32; break;
+    case VO_TRACKER_LOCAL_MAP_FLAGS: b = t->d.pf1, bytes = B * (size_t)t->n_local; break;
+    case VO_TRACKER_LOCAL_LINK: b = t->d.link1, bytes = B * (size_t)t->n_local * 4; break;
     default: return VO_ERR_INVALID;
+  }
+  if (!b) {
+    vo::set_error("vo_tracker_get(%d): vo_tracker_build_local_map has not run", what);
+    return VO_ERR_INVALID;
   }
   if (dst_bytes < bytes) {
     vo::set_error("vo_tracker_get(%d): destination holds %zu bytes, %zu needed", what, dst_bytes, bytes);

@@ -295,6 +295,22 @@ KfStoreView kfstore_view(const vo_kfstore *s);
 int kfstore_order_before(const vo_kfstore *s, hipStream_t st);
 int kfstore_order_after(const vo_kfstore *s, hipStream_t st);
 
+// What vo_tracker_build_local_map reads beyond the records (kfstore.hip).  graph: kKfGraphInts ints
+// per key-frame [n_neighbors, n_children, parent, 0 | neighbors 10, 2 spare | children 64]; normals [max_kf][NK][3]; the
+// observation index: keys [n_keys] ascending, key = map-point id << 32 | entry, entry = key-frame * NK + feature, for the
+// features with flags bit 0 set (~0ull: no entry; n_keys a power of two >= 2048); run[entry] = position of the first key
+// of the entry's id.  kfstore_obs_view rebuilds the index on the store's stream when an insert or update_points has
+// happened since the last use (launches only), and returns the views.
+constexpr int kKfGraphNb = VO_KFSTORE_MAX_NEIGHBORS, kKfGraphCh = VO_KFSTORE_MAX_CHILDREN, kKfGraphInts = 16 + kKfGraphCh;
+struct KfObsView {
+  const int *graph;
+  const double *normals;
+  const unsigned long long *keys;
+  const int *run;
+  int n_keys;
+};
+int kfstore_obs_view(vo_kfstore *s, KfObsView *out);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
@@ -343,8 +359,32 @@ struct RelocStoreArgs {
 // store route (tracker.hip)
 int reloc_store_prepare(Reloc *r, BowWalkBufs *walk, int *err, bool with_db, hipStream_t st);
 int reloc_run_store(Reloc *r, const RelocShared &S, const RelocStoreArgs &A);
-enum { kStoreErrTooMany = 1, kStoreErrBadId = 2 };
+// (bits 2, 3: vo_tracker_build_local_map -- more distinct local points than max_local, more voters than the list holds)
+enum { kStoreErrTooMany = 1, kStoreErrBadId = 2, kStoreErrLocalPoints = 4, kStoreErrLocalKfs = 8 };
 bool reloc_last_was_store(const Reloc *r);
+// the frames' slot ids in the store's id space [B][cap] and the winners [B] a store route left (VO_ERR_INVALID otherwise)
+int reloc_frame_ids(Reloc *r, int **fid, const int **winner);
+
+// vo_tracker_build_local_map's kernels (local_map.hip): votes, voters, expansion (k_lm_keyframes, a workgroup per frame),
+// the local points (k_lm_points, a workgroup per frame).  Enqueued on st; the caller orders st against the store's stream.
+struct LocalMapArgs {
+  KfStoreView S;
+  KfObsView O;
+  int B, cap, max_local, stride;  // frames, feature slots per frame, local points per frame, row stride of the local-map arrays
+  const int *fn;                  // [B] features per frame
+  const int *winner;              // [B] < 0: the frame's relocalisation failed (NULL: every frame takes part)
+  int *sid;                       // [B][cap] slot ids (relocalisation), or NULL: read through ref_kf / assigned
+  const int *ref_kf, *assigned;   // [B], [B][cap] the reference-key-frame route's key-frame numbers and first-search matches
+  uint8_t *fhas, *fobs;           // [B][cap]
+  int *votes;                     // [B][S.max_kf] scratch: the counts, then list position + 1 per key-frame
+  int *lkf, *n_kf, *best, *n_pts; // [B][VO_TRACKER_LOCAL_MAX_KEYFRAMES], [B], [B], [B]
+  int *err;                       // the store routes' sticky word
+  double *p1, *nrm1;
+  float *mind1, *maxd1;
+  uint8_t *pf1, *desc1;
+  int *link1, *ids1;
+};
+int local_map_build(const LocalMapArgs &A, hipStream_t st);
 
 // vo_set_option's process-wide values as last set, 0 before (vo_common.hip): VO_OPT_BA_GRAPH (ba.hip), VO_OPT_POSE_BLOCK
 // (pose_only.hip), VO_OPT_BA_PAIRS_KERNEL (ba.hip), VO_OPT_HAMMING_KERNEL (match.hip: 0 = matrix-core form, 1 = VALU form)

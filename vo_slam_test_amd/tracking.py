@@ -35,3 +35,14 @@ def load_maps(trk: "vo.Tracker", maps, n_last=None, n_local=None):
     trk.set_local_map(local["points"], local["normals"], local["min_dist"], local["max_dist"], local["valid"], local["desc"],
                       link=local["link"])
     return last, local
+
+
+def load_keyframe_graph(store: "vo.KeyFrameStore", keyframes, first=0):
+    """hand the map side that Tracker.build_local_map reads to a key-frame store: keyframes = one dict per key-frame already
+    inserted (numbers first, first + 1, ...) with neighbors (getBestCovisibleKFs(10) in its order), children (any order: sorted
+    here into the ascending key-frame number the store takes), parent (-1: none) and optionally normals [n, 3]"""
+    store.set_graph_batch(first, [list(k.get("neighbors", ())) for k in keyframes], [sorted(k.get("children", ())) for k in keyframes],
+                          [int(k.get("parent", -1)) for k in keyframes])
+    for i, k in enumerate(keyframes):
+        if k.get("normals") is not None:
+            store.set_normals(first + i, np.asarray(k["normals"], np.float64))
