@@ -922,6 +922,60 @@ int vo_kfstore_set_graph(vo_kfstore *s, int keyframe, int n_neighbors, const int
 int vo_kfstore_set_graph_batch(vo_kfstore *s, int first, int count, const int32_t *n_neighbors, const int32_t *neighbors,
                                const int32_t *n_children, const int32_t *children, const int32_t *parent);
 int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals /*[n][3]*/);
+/* The covisibility graph and the spanning tree maintained on the device: KeyFrame::updateConnections
+ * with addConnection and updateBestCovisibles (keyframe.cpp:69-198), from the observation index, so that insert ->
+ * update connections -> vo_tracker_build_local_map -> vo_tracker_track_local_map runs without the host computing anything.
+ * enable_connections: valid on an empty store only (size == 0, else VO_ERR_INVALID); allocates the connection state, a dense
+ * int32 weight row and an ordered list per key-frame plus five words: 8 * max_keyframes^2 + 20 * max_keyframes + 16 bytes
+ * (2 010 016 at 500 key-frames).  max_keyframes above VO_KFSTORE_CONNECTIONS_MAX_KEYFRAMES is VO_ERR_CAPACITY (the count
+ * kernel keeps one counter per key-frame in 16 KB of LDS, the order kernel sorts a row in 32 KB; the state would be
+ * 128 MB there).  A store without this call allocates and behaves exactly as before.  With it the graph has ONE writer:
+ * vo_kfstore_set_graph / _batch return VO_ERR_INVALID.  Synchronises once.
+ * update_connections[_dev]: update(k) for every k of the list IN LIST ORDER, repeats allowed; the result is that of the
+ * reference called sequentially.  update(k), with "j holds p" as the observation index defines it (the key-frames' bad
+ * flag plays no part: updateConnections never tests it):
+ *  1 C[j], j != k: the features of k with bit 0 set whose id j holds (:80-93).  An id in two features of k counts twice, j
+ *    counts once per feature however many of its features hold the id: C is NOT symmetric.  All zero: nothing changes (:95).
+ *  2 nmax / kfmax: the first strictly largest count in ASCENDING KEY-FRAME NUMBER (:105-111; the rule of
+ *    vo_kfstore_set_graph for pointer-keyed containers).
+ *  3 T = { j : C[j] >= 15 }, or { kfmax } when that is empty (:112-124).
+ *  4 addConnection(j <- k, C[j]) for every j of T (:157-171): where the weight j keeps for k is absent or different it is
+ *    set and j's ordered list becomes ALL of j's weights, sorted (updateBestCovisibles, :176-198); an equal weight changes
+ *    nothing.
+ *  5 k's weights become C, every entry >= 1 (:140); k's ordered list is T only, sorted (:127-142).
+ *  6 sorted: weight descending, equal weights in DESCENDING key-frame number (sort of (weight, KeyFrame*) pairs ascending,
+ *    then push_front).
+ *  7 on k's first update that finds a connection, k != 0: parent = the front of k's ordered list, k joins the parent's
+ *    children (:145-150).  Key-frame 0 never gets a parent.
+ * So a key-frame's ordered list is thresholded right after its own update and becomes its whole weight map, entries below
+ * 15 included, as soon as a neighbour's update changes one of its weights -- both visible through getBestCovisibleKFs(10).
+ * Besides the state the calls rewrite the graph row (vo_kfstore_set_graph's) of every key-frame whose ordered list, parent
+ * or children changed: the first VO_KFSTORE_MAX_NEIGHBORS of the ordered list, the parent, the children ascending;
+ * vo_tracker_build_local_map reads it unchanged.  The work runs on the store's stream -- the observation index rebuilt
+ * first when an insert or update_points has happened since its last use, then three launches (count, apply, order) -- and
+ * tracker calls order themselves behind it like behind any other store call.
+ * update_connections: host list; every number is validated against [0, size) before anything is enqueued (VO_ERR_INVALID,
+ * nothing changes); one copy, synchronises once (the list is free on return).
+ * update_connections_dev: device list [n], which must stay untouched until the stream has passed the call.  Enqueues only: no
+ * host synchronisation, no device-to-host copy, no allocation except by the first call with a larger n than any before.
+ * Conditions only the device sees go to a sticky word on the store: a listed number outside [0, size) is skipped
+ * (VO_KFSTORE_CONNECTIONS_INVALID); a parent with more than VO_KFSTORE_MAX_CHILDREN children keeps its 64 lowest-numbered
+ * ones in its graph row (VO_KFSTORE_CONNECTIONS_CAPACITY; the child's parent is still set).
+ * connections_status: synchronises, returns the word and clears it.
+ * get_connections: synchronises; any pointer may be NULL.  n_connected and weights [size] = connectedKFWts_ (0: not
+ * connected); n_ordered, ordered [size], ordered_weights [size] = orderedConnectKFs_ / orderedWTs_ (entries beyond
+ * n_ordered: -1 / 0); parent = getParent() or -1; n_children, children [VO_KFSTORE_MAX_CHILDREN] = the graph row's
+ * (entries beyond n_children: -1).
+ * Not covered: eraseKeyFrame / eraseConnection, cullingKeyFrames, loop edges. */
+#define VO_KFSTORE_CONNECTIONS_MAX_KEYFRAMES 4096
+#define VO_KFSTORE_CONNECTIONS_INVALID 1
+#define VO_KFSTORE_CONNECTIONS_CAPACITY 2
+int vo_kfstore_enable_connections(vo_kfstore *s);
+int vo_kfstore_update_connections(vo_kfstore *s, int n, const int32_t *keyframes);
+int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes);
+int vo_kfstore_connections_status(vo_kfstore *s, int32_t *word);
+int vo_kfstore_get_connections(vo_kfstore *s, int keyframe, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
+                               int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

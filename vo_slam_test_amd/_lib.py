@@ -55,6 +55,8 @@ SYMBOLS = [
     "vo_tracker_relocalize_db", "vo_tracker_relocalize_db_dev", "vo_tracker_get_reloc_timing",
     "vo_tracker_track_ref_keyframe_store", "vo_tracker_track_ref_keyframe_store_dev", "vo_tracker_set_local_map_ids",
     "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
+    "vo_kfstore_enable_connections", "vo_kfstore_update_connections", "vo_kfstore_update_connections_dev",
+    "vo_kfstore_connections_status", "vo_kfstore_get_connections",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1616,6 +1618,41 @@ class KeyFrameStore:
         """MapPoint::normalVector_ per feature [n, 3] (n as inserted); zero until set, and a zero normal fails isInFrame"""
         nrm = np.ascontiguousarray(normals, np.float64)
         check(lib().vo_kfstore_set_normals(self._h, int(keyframe), _p(nrm)), "vo_kfstore_set_normals")
+
+    CONNECTIONS_INVALID, CONNECTIONS_CAPACITY = 1, 2
+
+    def enable_connections(self):
+        """the covisibility graph and spanning tree maintained on the device from now on; valid on
+        an empty store only, and set_graph / set_graph_batch are invalid afterwards"""
+        check(lib().vo_kfstore_enable_connections(self._h), "vo_kfstore_enable_connections")
+
+    def update_connections(self, keyframes):
+        """KeyFrame::updateConnections for the listed key-frames in list order (repeats allowed).  A list / numpy array is
+        validated and synchronises once; a device tensor (int32) is enqueued only and must stay untouched until the
+        store's stream has passed the call"""
+        if hasattr(keyframes, "data_ptr"):
+            check(lib().vo_kfstore_update_connections_dev(self._h, int(keyframes.numel()), _p(keyframes)), "vo_kfstore_update_connections_dev")
+            return
+        kf = np.ascontiguousarray(keyframes, np.int32).reshape(-1)
+        check(lib().vo_kfstore_update_connections(self._h, len(kf), _p(kf)), "vo_kfstore_update_connections")
+
+    def connections_status(self):
+        """the sticky word of update_connections (CONNECTIONS_INVALID | CONNECTIONS_CAPACITY), cleared by the read"""
+        w = C.c_int32(0)
+        check(lib().vo_kfstore_connections_status(self._h, C.byref(w)), "vo_kfstore_connections_status")
+        return int(w.value)
+
+    def connections(self, keyframe):
+        """-> dict(n_connected, weights [size] (0: not connected), ordered, ordered_weights (orderedConnectKFs_ /
+        orderedWTs_), parent, children (ascending, at most MAX_CHILDREN)) as plain lists and ints"""
+        size = len(self)
+        w, o, ow = (np.zeros(max(size, 1), np.int32) for _ in range(3))
+        ch = np.zeros(self.MAX_CHILDREN, np.int32)
+        nc, no, par, nch = (C.c_int32(0) for _ in range(4))
+        check(lib().vo_kfstore_get_connections(self._h, int(keyframe), C.byref(nc), _p(w), C.byref(no), _p(o), _p(ow), C.byref(par),
+                                               C.byref(nch), _p(ch)), "vo_kfstore_get_connections")
+        return dict(n_connected=int(nc.value), weights=[int(x) for x in w[:size]], ordered=[int(x) for x in o[:no.value]],
+                    ordered_weights=[int(x) for x in ow[:no.value]], parent=int(par.value), children=[int(x) for x in ch[:nch.value]])
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -37,6 +37,7 @@ SOURCES = [
     ("vocab_train.hip", ["-ffp-contract=off"]),
     ("kfdb.hip", ["-ffp-contract=off"]),
     ("kfstore.hip", ["-ffp-contract=off"]),
+    ("connections.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -93,6 +93,7 @@ struct vo_kfstore {
   int okeys_cap = 0;      // keys the index holds: the power of two above max_kf * NK, at least one chunk
   bool obs_dirty = true;  // an insert or update_points has happened since the index was built
   int obs_n = 0;          // keys the built index spans (a power of two covering size * NK)
+  vo::KfConnections *conn = nullptr;  // vo_kfstore_enable_connections: the graph is then maintained on the device (section 4h)
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -176,6 +177,17 @@ int graph_row(const vo_kfstore *s, const char *call, int keyframe, int n_nb, con
   return VO_OK;
 }
 
+int graph_has_writer(const char *call) {
+  vo::set_error("%s: the store maintains its graph itself (vo_kfstore_enable_connections)", call);
+  return VO_ERR_INVALID;
+}
+
+int need_connections(const vo_kfstore *s, const char *call) {
+  if (s && s->conn) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_connections has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
 }  // namespace
 
 extern "C" {
@@ -248,6 +260,7 @@ void vo_kfstore_destroy(vo_kfstore *s) {
   if (!s) return;
   if (s->ev_in) (void)hipEventDestroy(s->ev_in);
   if (s->ev_out) (void)hipEventDestroy(s->ev_out);
+  if (s->conn) vo::connections_destroy(s->conn);
   delete s;
 }
 
@@ -420,6 +433,7 @@ int vo_kfstore_update_points(vo_kfstore *s, int keyframe, const uint8_t *flags, 
 int vo_kfstore_set_graph(vo_kfstore *s, int keyframe, int n_neighbors, const int32_t *neighbors, int n_children,
                          const int32_t *children, int parent) {
   if (!s || keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  if (s->conn) return graph_has_writer("vo_kfstore_set_graph");
   int32_t row[vo::kKfGraphInts];
   VO_CHECK(graph_row(s, "vo_kfstore_set_graph", keyframe, n_neighbors, neighbors, n_children, children, parent, row));
   const char *W = "vo_kfstore_set_graph";
@@ -432,6 +446,7 @@ int vo_kfstore_set_graph_batch(vo_kfstore *s, int first, int count, const int32_
   if (!s || first < 0 || count < 0 || first + (long long)count > s->size ||
       (count > 0 && (!n_neighbors || !neighbors || !n_children || !children || !parent)))
     return VO_ERR_INVALID;
+  if (s->conn) return graph_has_writer("vo_kfstore_set_graph_batch");
   if (count == 0) return VO_OK;
   std::vector<int32_t> rows((size_t)count * vo::kKfGraphInts);
   for (int k = 0; k < count; k++)
@@ -450,6 +465,60 @@ int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals) {
   const char *W = "vo_kfstore_set_normals";
   VO_CHECK(vo::copy_h2d(s->normals.as<double>() + (size_t)keyframe * s->NK * 3, normals, n * 24, s->st, W));
   return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_enable_connections(vo_kfstore *s) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("vo_kfstore_enable_connections: the store holds %d key-frames, the call is valid on an empty store only", s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->conn) return VO_OK;
+  return vo::connections_create(&s->conn, s->max_kf, s->graph.as<int>(), s->st);
+}
+
+int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {
+  VO_CHECK(need_connections(s, "vo_kfstore_update_connections_dev"));
+  if (n < 0 || (n > 0 && !dev_keyframes)) return VO_ERR_INVALID;
+  if (n == 0 || s->size == 0) return VO_OK;
+  VO_CHECK(vo::connections_reserve(s->conn, n, nullptr));  // (before the index: nothing is enqueued when it fails)
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  return vo::connections_update(s->conn, vo::kfstore_view(s), O, n, dev_keyframes, s->st);
+}
+
+int vo_kfstore_update_connections(vo_kfstore *s, int n, const int32_t *keyframes) {
+  const char *W = "vo_kfstore_update_connections";
+  VO_CHECK(need_connections(s, W));
+  if (n < 0 || (n > 0 && !keyframes)) return VO_ERR_INVALID;
+  for (int i = 0; i < n; i++)
+    if (keyframes[i] < 0 || keyframes[i] >= s->size) {
+      vo::set_error("%s: entry %d: key-frame %d outside [0, %d)", W, i, keyframes[i], s->size);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  int *dev_list = nullptr;
+  VO_CHECK(vo::connections_reserve(s->conn, n, &dev_list));
+  VO_CHECK(vo::copy_h2d(dev_list, keyframes, (size_t)n * 4, s->st, W));
+  VO_CHECK(vo_kfstore_update_connections_dev(s, n, dev_list));
+  return vo::stream_sync(s->st, W);  // (the caller's list is free on return)
+}
+
+int vo_kfstore_connections_status(vo_kfstore *s, int32_t *word) {
+  VO_CHECK(need_connections(s, "vo_kfstore_connections_status"));
+  if (!word) return VO_ERR_INVALID;
+  int w = 0;
+  VO_CHECK(vo::connections_status(s->conn, s->st, &w));
+  *word = w;
+  return VO_OK;
+}
+
+int vo_kfstore_get_connections(vo_kfstore *s, int keyframe, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
+                               int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children) {
+  VO_CHECK(need_connections(s, "vo_kfstore_get_connections"));
+  if (keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  return vo::connections_get(s->conn, s->size, keyframe, s->st, n_connected, weights, n_ordered, ordered, ordered_weights, parent,
+                             n_children, children);
 }
 
 }  // extern "C"

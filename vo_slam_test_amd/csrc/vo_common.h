@@ -311,6 +311,21 @@ struct KfObsView {
 };
 int kfstore_obs_view(vo_kfstore *s, KfObsView *out);
 
+// The covisibility graph and spanning tree of a store, maintained on the device (connections.hip):
+// KeyFrame::updateConnections (keyframe.cpp:69-152) for a device list of key-frame numbers, in list order.  The state is
+// allocated once by connections_create (connections_bytes(max_kf) bytes; `graph`: the store's graph rows, which the calls
+// rewrite); connections_reserve sizes the scratch of a list of n entries (grow-only) and returns the device list of the
+// host form; connections_update enqueues three launches on st and nothing else.
+struct KfConnections;
+size_t connections_bytes(int max_kf);
+int connections_create(KfConnections **out, int max_kf, int *graph, hipStream_t st);
+void connections_destroy(KfConnections *c);
+int connections_reserve(KfConnections *c, int n, int **dev_list);
+int connections_update(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n, const int *dev_list, hipStream_t st);
+int connections_status(KfConnections *c, hipStream_t st, int *word);  // synchronises; bit 0: invalid number, bit 1: children
+int connections_get(KfConnections *c, int size, int k, hipStream_t st, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
+                    int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
