@@ -865,7 +865,7 @@ int vo_tracker_relocalize_dev(vo_tracker *t, const uint8_t *dev_images, int imag
 
 /* The key-frame feature store: everything the relocalisation route reads of a key-frame, resident
  * on the device, so that the route takes its candidates as key-frame numbers.  A key-frame is known by its insertion
- * number 0, 1, 2 ... -- the numbering of vo_kfdb -- and is never erased.  Every device buffer is sized at creation from
+ * number 0, 1, 2 ... -- the numbering of vo_kfdb -- and keeps it (vo_kfstore_erase_keyframe marks, it does not reclaim).  Every device buffer is sized at creation from
  * (max_keyframes, max_features); one more key-frame, or a key-frame with more features (or more FeatureVector entries)
  * than that, is VO_ERR_CAPACITY and nothing is truncated.  Per key-frame: n, bad; per feature: angle, desc, flags (bit 0:
  * the map point exists and is not bad; bit 1: observe_cnt_ > 0, the meaning vo_tracker_set_ref_keyframe gives it -- the
@@ -966,7 +966,8 @@ int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals /*
  * connected); n_ordered, ordered [size], ordered_weights [size] = orderedConnectKFs_ / orderedWTs_ (entries beyond
  * n_ordered: -1 / 0); parent = getParent() or -1; n_children, children [VO_KFSTORE_MAX_CHILDREN] = the graph row's
  * (entries beyond n_children: -1).
- * Not covered: eraseKeyFrame / eraseConnection, cullingKeyFrames, loop edges. */
+ * A store with culling (below) skips a listed key-frame that has been erased like a number outside the store.
+ * Not covered: loop edges. */
 #define VO_KFSTORE_CONNECTIONS_MAX_KEYFRAMES 4096
 #define VO_KFSTORE_CONNECTIONS_INVALID 1
 #define VO_KFSTORE_CONNECTIONS_CAPACITY 2
@@ -976,6 +977,84 @@ int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_k
 int vo_kfstore_connections_status(vo_kfstore *s, int32_t *word);
 int vo_kfstore_get_connections(vo_kfstore *s, int keyframe, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
                                int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children);
+/* Redundant key-frames culled on the device: LocalMapping::cullingKeyFrames (localMapping.cpp:434-494)
+ * with KeyFrame::eraseKeyFrame, eraseConnection (keyframe.cpp:400-526) and MapPoint::eraseObservedKF / eraseMapPoint
+ * (mappoint.cpp:333-381), on the observation index and the connection state, so that a store with device-side connections
+ * can lose a key-frame without the host computing or uploading anything.  A store that does not call enable_culling
+ * allocates and behaves exactly as before; every entry point of this block except get_flags returns VO_ERR_INVALID on it.
+ * enable_culling: valid only on an EMPTY store on which vo_kfstore_enable_connections has succeeded, else VO_ERR_INVALID.
+ * Allocates three per-feature columns [max_keyframes][max_features] -- octave (int32, default 0), depth and u_right (float,
+ * default -1: what Frame::findDepth gives a feature without depth, frame.cpp:113-131) -- and seven words per key-frame
+ * (erased, locked, pending, and the four-word record of the last cull call): 12 * max_keyframes * max_features +
+ * 28 * max_keyframes + 16 bytes (6 014 016 at 500 key-frames of 1000 features).  A key-frame whose columns were never set has
+ * mp_cnt == 0 and is never culled.  Synchronises once.
+ * set_keypoints: host arrays [n], n as inserted; one copy, synchronises once.  set_keypoints_dev: device arrays [n],
+ * enqueues only (for insert_dev callers); the arrays must stay untouched until the stream has passed the call.  Both
+ * validate the key-frame number against [0, size).
+ * set_erase_lock: notEraseLoopDetecting_ (keyframe.cpp:408-412, 541-560) of a key-frame, on or off; enqueues only.  Taking the
+ * lock off erases nothing: the caller reads `pending` (cull_state) and calls erase_keyframe, which is
+ * setEraseLoopDetectingKF's second half.  Loop edges themselves are the caller's.
+ * Definitions (choices of this restatement):
+ *  - key-frame j HOLDS id p when one of its features has ids == p and flags bit 0 set and j is not erased;
+ *  - j's OBSERVATION of p is its lowest-numbered such feature (observedKFs_ has one entry per key-frame, addObservation
+ *    keeps the first: mappoint.cpp:52-58);
+ *  - obs(p) = the sum over the holders of 2 where u_right >= 0 at the observation, else 1 (mappoint.cpp:60-63);
+ *  - bad(j) = the record's bad flag (vo_kfstore_set_bad and the erase write it).
+ * cull_keyframes(current, th_depth), the result being that of the reference called once:
+ *  1 the candidates are current's ordered list as the call finds it (:439 copies it), walked in its order; a candidate
+ *    with bad(k) or k == 0 is skipped (:445).
+ *  2 every feature i of k with bit 0 set: skipped when depth[i] < 0 || depth[i] > th_depth (float comparison, :455); else
+ *    mp_cnt++, and when obs(id) > 3, the holders j != k with !bad(j) whose observation has octave <= octave[i] + 1 are
+ *    counted: three or more give re_obs++ (:460-483).  An id in two features of k counts once per feature, each with its
+ *    own octave.
+ *  3 k is erased when re_obs > 0.9 * mp_cnt (:487; in double as written -- for every count a store can hold the product
+ *    decides like 10 * re_obs > 9 * mp_cnt, so a tie keeps k and mp_cnt == 0 never erases).  An erase changes what every later
+ *    candidate of the call sees.
+ * erase(k), also the explicit call erase_keyframe:
+ *  - k == 0 or k already erased: nothing happens.  locked[k]: pending[k] = 1 and nothing else (the cull reports decision 2).
+ *  - for every j with W[k][j] != 0: where W[j][k] != 0 it becomes 0 and j's ordered list becomes its whole map
+ *    (eraseConnection + updateBestCovisibles).  QUIRK Q-E1: the walk runs over k's map, not over who points at k, so a j with
+ *    W[j][k] != 0 but W[k][j] == 0 keeps its connection to the erased k (keyframe.cpp:415-416).
+ *  - for every observation of k: k leaves the holders; when the remaining obs(p) <= 2 the point dies (eraseMapPoint): bit 0 is
+ *    cleared in every feature that carries p of every key-frame not erased before, and of k itself.  Weights do not change
+ *    with a point's death.
+ *  - W[k][*] = 0 and k's ordered list is empty.
+ *  - spanning tree (:429-485): the candidate set starts as {parent[k]} (empty when k has no parent: the reference dereferences
+ *    null there).  A round takes, over the non-bad children c of k in ascending number and the members x of c's ordered list
+ *    that are in the set, the strictly largest W[c][x] -- ties: the first c, then the first x in list order, i.e. the higher
+ *    number --, sets parent[c] = x and moves c from the children into the set; rounds repeat until one finds nothing.  The
+ *    remaining children, bad ones included, get parent[k].  k leaves its parent's children; parent[k] itself is KEPT (the
+ *    caller's Tcp_; the store holds no poses).
+ *  - erased[k] = 1 and the record's bad flag is set.  The slot is not reclaimed.
+ * Afterwards the observation index skips erased key-frames (so do vo_tracker_build_local_map's votes), a parent's children
+ * are the non-erased key-frames whose parent it is, an erased key-frame's graph row is empty with its parent kept, and
+ * update_connections skips a listed erased key-frame (VO_KFSTORE_CONNECTIONS_INVALID).  More than VO_KFSTORE_MAX_CHILDREN
+ * children after a re-parenting: VO_KFSTORE_CONNECTIONS_CAPACITY as before.  Map::eraseKeyFrame (map.cpp:37-58) edits a copy
+ * of each inverted-index list: vo_kfdb needs nothing.
+ * cull_keyframes / erase_keyframe validate the number against [0, size) and ENQUEUE ONLY on the store's stream: the index
+ * rebuilt first when stale, then count, apply and the ordering pass (erase_keyframe: apply and order).  No host
+ * synchronisation, no device-to-host copy, no allocation.  Every such call marks the index stale (the host cannot know
+ * whether anything was erased).  That `current` has been erased only the device knows: the call then walks no candidate
+ * and raises VO_KFSTORE_CONNECTIONS_INVALID.
+ * cull_result: synchronises; the record of the last cull call: n_candidates and, per candidate in list order, the key-frame,
+ * mp_cnt, re_obs (0 / 0 for a skipped one) and decision (arrays [size], any may be NULL).  cull_state: synchronises; any
+ * pointer may be NULL.  get_flags: synchronises; the flags bytes [n] and the bad flag of a key-frame as the store holds them
+ * (valid on every store). */
+#define VO_KFSTORE_CULL_KEPT 0
+#define VO_KFSTORE_CULL_ERASED 1
+#define VO_KFSTORE_CULL_PENDING 2
+#define VO_KFSTORE_CULL_SKIPPED 3
+int vo_kfstore_enable_culling(vo_kfstore *s);
+int vo_kfstore_set_keypoints(vo_kfstore *s, int keyframe, const int32_t *octave, const float *depth, const float *u_right);
+int vo_kfstore_set_keypoints_dev(vo_kfstore *s, int keyframe, const int32_t *dev_octave, const float *dev_depth,
+                                 const float *dev_u_right);
+int vo_kfstore_set_erase_lock(vo_kfstore *s, int keyframe, int on);
+int vo_kfstore_cull_keyframes(vo_kfstore *s, int current, float th_depth);
+int vo_kfstore_erase_keyframe(vo_kfstore *s, int keyframe);
+int vo_kfstore_cull_result(vo_kfstore *s, int32_t *n_candidates, int32_t *keyframes, int32_t *mp_cnt, int32_t *re_obs,
+                           int32_t *decision);
+int vo_kfstore_cull_state(vo_kfstore *s, int keyframe, int32_t *erased, int32_t *locked, int32_t *pending);
+int vo_kfstore_get_flags(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *bad);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

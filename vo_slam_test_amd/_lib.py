@@ -57,6 +57,8 @@ SYMBOLS = [
     "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
     "vo_kfstore_enable_connections", "vo_kfstore_update_connections", "vo_kfstore_update_connections_dev",
     "vo_kfstore_connections_status", "vo_kfstore_get_connections",
+    "vo_kfstore_enable_culling", "vo_kfstore_set_keypoints", "vo_kfstore_set_keypoints_dev", "vo_kfstore_set_erase_lock",
+    "vo_kfstore_cull_keyframes", "vo_kfstore_erase_keyframe", "vo_kfstore_cull_result", "vo_kfstore_cull_state", "vo_kfstore_get_flags",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1653,6 +1655,55 @@ class KeyFrameStore:
                                                C.byref(nch), _p(ch)), "vo_kfstore_get_connections")
         return dict(n_connected=int(nc.value), weights=[int(x) for x in w[:size]], ordered=[int(x) for x in o[:no.value]],
                     ordered_weights=[int(x) for x in ow[:no.value]], parent=int(par.value), children=[int(x) for x in ch[:nch.value]])
+
+    CULL_KEPT, CULL_ERASED, CULL_PENDING, CULL_SKIPPED = 0, 1, 2, 3
+
+    def enable_culling(self):
+        """cullingKeyFrames / eraseKeyFrame on the device from now on; valid on an empty store after
+        enable_connections only"""
+        check(lib().vo_kfstore_enable_culling(self._h), "vo_kfstore_enable_culling")
+
+    def set_keypoints(self, keyframe, octave, depth, u_right):
+        """octave (int32), depth and u_right (float32; < 0: none) per feature [n], n as inserted.  numpy arrays are copied and
+        synchronise once; device tensors (all three) are enqueued only"""
+        if hasattr(octave, "data_ptr"):
+            check(lib().vo_kfstore_set_keypoints_dev(self._h, int(keyframe), _p(octave), _p(depth), _p(u_right)), "vo_kfstore_set_keypoints_dev")
+            return
+        o, d, u = np.ascontiguousarray(octave, np.int32), np.ascontiguousarray(depth, np.float32), np.ascontiguousarray(u_right, np.float32)
+        check(lib().vo_kfstore_set_keypoints(self._h, int(keyframe), _p(o), _p(d), _p(u)), "vo_kfstore_set_keypoints")
+
+    def set_erase_lock(self, keyframe, on=True):
+        """notEraseLoopDetecting_: a locked key-frame is marked pending instead of being erased"""
+        check(lib().vo_kfstore_set_erase_lock(self._h, int(keyframe), int(bool(on))), "vo_kfstore_set_erase_lock")
+
+    def cull_keyframes(self, current, th_depth):
+        """LocalMapping::cullingKeyFrames for the current key-frame; enqueued only"""
+        check(lib().vo_kfstore_cull_keyframes(self._h, int(current), C.c_float(th_depth)), "vo_kfstore_cull_keyframes")
+
+    def erase_keyframe(self, keyframe):
+        """KeyFrame::eraseKeyFrame; enqueued only"""
+        check(lib().vo_kfstore_erase_keyframe(self._h, int(keyframe)), "vo_kfstore_erase_keyframe")
+
+    def cull_result(self):
+        """the last cull call -> [(key-frame, mp_cnt, re_obs, decision)] per candidate in list order"""
+        size = max(len(self), 1)
+        kf, mp, re, de = (np.zeros(size, np.int32) for _ in range(4))
+        n = C.c_int32(0)
+        check(lib().vo_kfstore_cull_result(self._h, C.byref(n), _p(kf), _p(mp), _p(re), _p(de)), "vo_kfstore_cull_result")
+        return [(int(kf[t]), int(mp[t]), int(re[t]), int(de[t])) for t in range(n.value)]
+
+    def cull_state(self, keyframe):
+        """-> dict(erased, locked, pending) of a key-frame"""
+        e, l, p = (C.c_int32(0) for _ in range(3))
+        check(lib().vo_kfstore_cull_state(self._h, int(keyframe), C.byref(e), C.byref(l), C.byref(p)), "vo_kfstore_cull_state")
+        return dict(erased=int(e.value), locked=int(l.value), pending=int(p.value))
+
+    def flags(self, keyframe, n=None):
+        """-> (flags bytes as a list, bad) of a key-frame as the store holds them"""
+        f = np.zeros(self.max_features, np.uint8)
+        bad = C.c_int32(0)
+        check(lib().vo_kfstore_get_flags(self._h, int(keyframe), _p(f), C.byref(bad)), "vo_kfstore_get_flags")
+        return [int(x) for x in (f if n is None else f[:n])], int(bad.value)
 
 
 def rgb_to_gray(img, first_is_red=True):

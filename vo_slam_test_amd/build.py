@@ -38,6 +38,7 @@ SOURCES = [
     ("kfdb.hip", ["-ffp-contract=off"]),
     ("kfstore.hip", ["-ffp-contract=off"]),
     ("connections.hip", ["-ffp-contract=off"]),
+    ("cull.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

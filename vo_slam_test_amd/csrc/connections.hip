@@ -14,6 +14,7 @@
 #include "vo_common.h"
 
 #include "block_sort.h"
+#include "obs_walk.h"
 
 #include <algorithm>
 #include <new>
@@ -29,6 +30,7 @@ struct KfConnections {
   int *n_ordered = nullptr, *mode = nullptr, *first = nullptr, *parent = nullptr, *touched = nullptr;  // [max_kf]
   int *status = nullptr;                                                                         // the sticky word
   int *graph = nullptr;                                                                          // the store's graph rows
+  const int *erased = nullptr;  // [max_kf] of a store with culling, else NULL: nothing is erased
   // views into `scratch`
   int *rows = nullptr, *list = nullptr;
   int4 *meta = nullptr;
@@ -74,13 +76,14 @@ __device__ __forceinline__ void block_reduce(int &n, unsigned long long &a, unsi
 }
 
 // meta[t] = (key-frame or -1: skipped, entries >= 15, kfmax or -1: no connection, front of the sorted list)
-__global__ __launch_bounds__(256) void k_conn_count(KfStoreView S, KfObsView O, const int *list, int *rows, int4 *meta, int *status) {
+__global__ __launch_bounds__(256) void k_conn_count(KfStoreView S, KfObsView O, const int *list, const int *erased, int *rows, int4 *meta,
+                                                    int *status) {
   __shared__ int hist[kMaxKf];
   __shared__ int s_n[256];
   __shared__ unsigned long long s_a[256], s_b[256];
   const int t = blockIdx.x, tid = threadIdx.x, size = S.size, NK = S.NK;
   const int k = list[t];
-  if (k < 0 || k >= size) {  // (uniform over the workgroup)
+  if (k < 0 || k >= size || (erased && erased[k])) {  // (uniform over the workgroup; an erased key-frame is never updated)
     if (tid == 0) atomicOr(status, (int)kConnInvalid), meta[t] = make_int4(-1, 0, -1, -1);
     return;
   }
@@ -93,13 +96,10 @@ __global__ __launch_bounds__(256) void k_conn_count(KfStoreView S, KfObsView O, 
     if (!(flags[i] & 1)) continue;
     const int id = ids[i];
     if (id < 0) continue;
-    int prev = -1;
-    for (int s = max(O.run[(size_t)k * NK + i], 0); s < O.n_keys && (int)(O.keys[s] >> 32) == id; s++) {
-      const int kk = (int)((unsigned)(O.keys[s] & 0xffffffffu) / (unsigned)NK);
-      if (kk == prev || kk >= size) continue;  // (two features of one key-frame: one observation)
-      prev = kk;
+    obs_run_holders(O, NK, size, O.run[(size_t)k * NK + i], id, [](int, unsigned) { return true; }, [&](int kk, int) {
       if (kk != k) atomicAdd(&hist[kk], 1);  // `if (itf->first->id_ == id_) continue;` (:89)
-    }
+      return true;
+    });
   }
   __syncthreads();
   int *row = rows + (size_t)t * S.max_kf;
@@ -169,8 +169,9 @@ __global__ __launch_bounds__(1024) void k_conn_apply(int size, int max_kf, int n
   }
 }
 
-__global__ __launch_bounds__(256) void k_conn_order(int size, int max_kf, const int *W, const int *mode, const int *parent, int *touched,
-                                                    int *ordered, int *n_ordered, int *graph, int *status) {
+__global__ __launch_bounds__(256) void k_conn_order(int size, int max_kf, const int *W, const int *mode, const int *parent,
+                                                    const int *erased, int *touched, int *ordered, int *n_ordered, int *graph,
+                                                    int *status) {
   __shared__ unsigned long long keys[kMaxKf];
   __shared__ int s_n[256];
   __shared__ unsigned long long s_a[256], s_b[256];
@@ -201,11 +202,12 @@ __global__ __launch_bounds__(256) void k_conn_order(int size, int max_kf, const 
   for (int i = tid; i < m; i += 256) out[i] = (int)(~keys[i] & 0xffffffffu);
   int *g = graph + (size_t)a * kKfGraphInts;
   for (int i = tid; i < kKfGraphNb + 2; i += 256) g[4 + i] = i < min(m, kKfGraphNb) ? (int)(~keys[i] & 0xffffffffu) : -1;
-  // children: the key-frames whose parent this one is, ascending, the lowest kKfGraphCh of them
+  // children: the key-frames whose parent this one is, ascending, the lowest kKfGraphCh of them; an erased key-frame keeps
+  // its parent but has left the children (eraseChild, keyframe.cpp:485)
   int base = 0;
   for (int j0 = 0; j0 < size; j0 += 256) {
     const int j = j0 + tid, lane = tid & 63, wv = tid >> 6;
-    const bool c = j < size && parent[j] == a;
+    const bool c = j < size && parent[j] == a && !(erased && erased[j]);
     const unsigned long long bal = __ballot(c);
     __syncthreads();
     if (lane == 0) s_w[wv] = __popcll(bal);
@@ -289,14 +291,24 @@ int connections_reserve(KfConnections *c, int n, int **dev_list) {
 int connections_update(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n, const int *dev_list, hipStream_t st) {
   if (n <= 0 || S.size <= 0) return VO_OK;
   VO_CHECK(connections_reserve(c, n, nullptr));
-  hipLaunchKernelGGL(k_conn_count, dim3(n), dim3(256), 0, st, S, O, dev_list, c->rows, c->meta, c->status);
+  hipLaunchKernelGGL(k_conn_count, dim3(n), dim3(256), 0, st, S, O, dev_list, c->erased, c->rows, c->meta, c->status);
   hipLaunchKernelGGL(k_conn_apply, dim3(1), dim3(1024), 0, st, S.size, c->max_kf, n, (const int *)c->rows, (const int4 *)c->meta, c->W,
                      c->mode, c->first, c->parent, c->touched);
-  hipLaunchKernelGGL(k_conn_order, dim3(S.size), dim3(256), 0, st, S.size, c->max_kf, (const int *)c->W, (const int *)c->mode,
-                     (const int *)c->parent, c->touched, c->ordered, c->n_ordered, c->graph, c->status);
+  return connections_order(c, S.size, st);
+}
+
+int connections_order(KfConnections *c, int size, hipStream_t st) {
+  hipLaunchKernelGGL(k_conn_order, dim3(size), dim3(256), 0, st, size, c->max_kf, (const int *)c->W, (const int *)c->mode,
+                     (const int *)c->parent, c->erased, c->touched, c->ordered, c->n_ordered, c->graph, c->status);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
+
+KfConnView connections_view(const KfConnections *c) {
+  return KfConnView{c->max_kf, c->W, c->ordered, c->n_ordered, c->mode, c->parent, c->touched, c->status};
+}
+
+void connections_set_erased(KfConnections *c, const int *erased) { c->erased = erased; }
 
 int connections_status(KfConnections *c, hipStream_t st, int *word) {
   const char *W = "vo_kfstore_connections_status";

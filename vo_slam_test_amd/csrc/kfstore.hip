@@ -20,12 +20,14 @@ __global__ void k_kfstore_bad(int *head, int bad) {
 // sorted by a device-wide bitonic network (fixed: the result is a function of the keys alone, and the keys are distinct).
 constexpr int kObsChunk = 2048;  // keys a workgroup of 256 sorts in LDS
 
-__global__ __launch_bounds__(256) void k_obs_fill(vo::KfStoreView V, unsigned long long *keys, int n_keys) {
+// (erased: the column of a store with culling, else NULL -- an erased key-frame holds nothing)
+__global__ __launch_bounds__(256) void k_obs_fill(vo::KfStoreView V, const int *erased, unsigned long long *keys, int n_keys) {
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= n_keys) return;
   const int k = e / V.NK, i = e - k * V.NK;
   unsigned long long key = ~0ull;
-  if (k < V.size && i < min(max(vo::kf_head(V, k)[0], 0), V.NK) && (vo::kf_sec<uint8_t>(V, k, V.o_flags)[i] & 1)) {
+  if (k < V.size && !(erased && erased[k]) && i < min(max(vo::kf_head(V, k)[0], 0), V.NK) &&
+      (vo::kf_sec<uint8_t>(V, k, V.o_flags)[i] & 1)) {
     const int id = vo::kf_sec<int>(V, k, V.o_ids)[i];
     if (id >= 0) key = ((unsigned long long)(unsigned)id << 32) | (unsigned)e;
   }
@@ -94,6 +96,9 @@ struct vo_kfstore {
   bool obs_dirty = true;  // an insert or update_points has happened since the index was built
   int obs_n = 0;          // keys the built index spans (a power of two covering size * NK)
   vo::KfConnections *conn = nullptr;  // vo_kfstore_enable_connections: the graph is then maintained on the device (section 4h)
+  vo::OwnedDevBuf cull;               // vo_kfstore_enable_culling: the columns and words of section 4i
+  vo::KfCullView X{};
+  bool culling = false;
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -127,7 +132,7 @@ int kfstore_obs_view(vo_kfstore *s, KfObsView *out) {
     unsigned long long *keys = s->okeys.as<unsigned long long>();
     hipStream_t st = s->st;
     KfStoreView V = kfstore_view(s);
-    hipLaunchKernelGGL(k_obs_fill, dim3(n / 256), dim3(256), 0, st, V, keys, n);
+    hipLaunchKernelGGL(k_obs_fill, dim3(n / 256), dim3(256), 0, st, V, (const int *)(s->culling ? s->X.erased : nullptr), keys, n);
     hipLaunchKernelGGL(k_obs_sort_local, dim3(n / kObsChunk), dim3(256), 0, st, keys, 2, kObsChunk);
     for (int k = 2 * kObsChunk; k <= n && k > 0; k <<= 1) {
       for (int j = k >> 1; j >= kObsChunk; j >>= 1)
@@ -185,6 +190,18 @@ int graph_has_writer(const char *call) {
 int need_connections(const vo_kfstore *s, const char *call) {
   if (s && s->conn) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_connections has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_culling(const vo_kfstore *s, const char *call) {
+  if (s && s->culling) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_culling has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_keyframe(const vo_kfstore *s, const char *call, int keyframe) {
+  if (keyframe >= 0 && keyframe < s->size) return VO_OK;
+  vo::set_error("%s: key-frame %d outside [0, %d)", call, keyframe, s->size);
   return VO_ERR_INVALID;
 }
 
@@ -475,6 +492,131 @@ int vo_kfstore_enable_connections(vo_kfstore *s) {
   }
   if (s->conn) return VO_OK;
   return vo::connections_create(&s->conn, s->max_kf, s->graph.as<int>(), s->st);
+}
+
+int vo_kfstore_enable_culling(vo_kfstore *s) {
+  const char *W = "vo_kfstore_enable_culling";
+  VO_CHECK(need_connections(s, W));
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->culling) return VO_OK;
+  VO_CHECK(s->cull.reserve(vo::cull_bytes(s->max_kf, s->NK)));
+  s->X = vo::cull_layout(s->cull.p, s->max_kf, s->NK);
+  VO_CHECK(vo::cull_init(s->X, s->max_kf, s->st));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  vo::connections_set_erased(s->conn, s->X.erased);
+  s->culling = true;
+  return VO_OK;
+}
+
+int vo_kfstore_set_keypoints(vo_kfstore *s, int keyframe, const int32_t *octave, const float *depth, const float *u_right) {
+  const char *W = "vo_kfstore_set_keypoints";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
+  if (n == 0) return VO_OK;
+  if (!octave || !depth || !u_right) return VO_ERR_INVALID;
+  // the three columns of a key-frame lie side by side: staged whole (the defaults beyond n), one copy
+  uint8_t *h = s->stage.data();  // (a record is longer than 12 bytes a feature)
+  int32_t *ho = reinterpret_cast<int32_t *>(h);
+  float *hd = reinterpret_cast<float *>(h) + NK, *hu = hd + NK;
+  for (size_t i = 0; i < NK; i++) ho[i] = i < n ? octave[i] : 0, hd[i] = i < n ? depth[i] : -1.f, hu[i] = i < n ? u_right[i] : -1.f;
+  VO_CHECK(vo::copy_h2d(vo::cull_octave(s->X, keyframe), h, NK * 12, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_keypoints_dev(vo_kfstore *s, int keyframe, const int32_t *dev_octave, const float *dev_depth, const float *dev_u_right) {
+  const char *W = "vo_kfstore_set_keypoints_dev";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_octave || !dev_depth || !dev_u_right) return VO_ERR_INVALID;
+  VO_HIP_CHECK(hipMemcpyAsync(vo::cull_octave(s->X, keyframe), dev_octave, n * 4, hipMemcpyDeviceToDevice, s->st));
+  VO_HIP_CHECK(hipMemcpyAsync(vo::cull_depth(s->X, keyframe), dev_depth, n * 4, hipMemcpyDeviceToDevice, s->st));
+  VO_HIP_CHECK(hipMemcpyAsync(vo::cull_uright(s->X, keyframe), dev_u_right, n * 4, hipMemcpyDeviceToDevice, s->st));
+  return VO_OK;
+}
+
+int vo_kfstore_set_erase_lock(vo_kfstore *s, int keyframe, int on) {
+  const char *W = "vo_kfstore_set_erase_lock";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  return vo::cull_set_lock(s->X, keyframe, on, s->st);
+}
+
+int vo_kfstore_cull_keyframes(vo_kfstore *s, int current, float th_depth) {
+  const char *W = "vo_kfstore_cull_keyframes";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has not been erased only the device knows: the kernels then walk no candidate and raise the sticky
+  //  VO_KFSTORE_CONNECTIONS_INVALID)
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::cull_enqueue(vo::kfstore_view(s), O, vo::connections_view(s->conn), s->X, current, th_depth, s->st));
+  s->obs_dirty = true;  // (whether anything was erased only the device knows)
+  return vo::connections_order(s->conn, s->size, s->st);
+}
+
+int vo_kfstore_erase_keyframe(vo_kfstore *s, int keyframe) {
+  const char *W = "vo_kfstore_erase_keyframe";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::erase_enqueue(vo::kfstore_view(s), O, vo::connections_view(s->conn), s->X, keyframe, s->st));
+  s->obs_dirty = true;
+  return vo::connections_order(s->conn, s->size, s->st);
+}
+
+int vo_kfstore_cull_result(vo_kfstore *s, int32_t *n_candidates, int32_t *keyframes, int32_t *mp_cnt, int32_t *re_obs, int32_t *decision) {
+  const char *W = "vo_kfstore_cull_result";
+  VO_CHECK(need_culling(s, W));
+  if (!n_candidates) return VO_ERR_INVALID;
+  std::vector<int32_t> rec((size_t)s->size * 4 + 4);
+  int32_t n = 0;
+  VO_CHECK(vo::copy_d2h(&n, s->X.n_rec, 4, s->st, W));
+  if (s->size > 0) VO_CHECK(vo::copy_d2h(rec.data(), s->X.rec, (size_t)s->size * 16, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  n = std::min(std::max(n, 0), s->size);
+  *n_candidates = n;
+  for (int t = 0; t < n; t++) {
+    if (keyframes) keyframes[t] = rec[(size_t)t * 4];
+    if (mp_cnt) mp_cnt[t] = rec[(size_t)t * 4 + 1];
+    if (re_obs) re_obs[t] = rec[(size_t)t * 4 + 2];
+    if (decision) decision[t] = rec[(size_t)t * 4 + 3];
+  }
+  return VO_OK;
+}
+
+int vo_kfstore_cull_state(vo_kfstore *s, int keyframe, int32_t *erased, int32_t *locked, int32_t *pending) {
+  const char *W = "vo_kfstore_cull_state";
+  VO_CHECK(need_culling(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  int32_t w[3] = {0, 0, 0};
+  VO_CHECK(vo::copy_d2h(w, s->X.erased + keyframe, 4, s->st, W));
+  VO_CHECK(vo::copy_d2h(w + 1, s->X.locked + keyframe, 4, s->st, W));
+  VO_CHECK(vo::copy_d2h(w + 2, s->X.pending + keyframe, 4, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  if (erased) *erased = w[0];
+  if (locked) *locked = w[1];
+  if (pending) *pending = w[2];
+  return VO_OK;
+}
+
+int vo_kfstore_get_flags(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *bad) {
+  const char *W = "vo_kfstore_get_flags";
+  if (!s) return VO_ERR_INVALID;
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  int32_t head[2] = {0, 0};
+  VO_CHECK(vo::copy_d2h(head, s->record(keyframe), 8, s->st, W));
+  if (flags && n > 0) VO_CHECK(vo::copy_d2h(flags, s->record(keyframe) + s->V.o_flags, n, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  if (bad) *bad = head[1];
+  return VO_OK;
 }
 
 int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {

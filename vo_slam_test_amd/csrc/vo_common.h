@@ -325,6 +325,42 @@ int connections_update(KfConnections *c, const KfStoreView &S, const KfObsView &
 int connections_status(KfConnections *c, hipStream_t st, int *word);  // synchronises; bit 0: invalid number, bit 1: children
 int connections_get(KfConnections *c, int size, int k, hipStream_t st, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
                     int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children);
+// for the culling kernels (cull.hip): the state's arrays; the `erased` column every later update and ordering pass
+// honours (NULL until vo_kfstore_enable_culling); k_conn_order over the touched key-frames on its own (one launch)
+struct KfConnView {
+  int max_kf;
+  int *W, *ordered, *n_ordered, *mode, *parent, *touched, *status;
+};
+KfConnView connections_view(const KfConnections *c);
+void connections_set_erased(KfConnections *c, const int *erased);
+int connections_order(KfConnections *c, int size, hipStream_t st);
+
+// Key-frame culling on the device (cull.hip): LocalMapping::cullingKeyFrames with
+// KeyFrame::eraseKeyFrame, eraseConnection and MapPoint::eraseObservedKF.  cols: [max_kf][3][NK] -- octave (int32), depth,
+// u_right (float) of a key-frame side by side, so that the host form of set_keypoints is one copy; erased, locked, pending
+// [max_kf]; rec [max_kf] (key-frame, mp_cnt, re_obs, decision) of the last cull call and n_rec its candidate count.
+// cull_bytes is what cull_layout hands out of one block; cull_init writes the defaults; cull_enqueue is k_cull_count +
+// k_cull_apply, erase_enqueue the erase alone, both without the ordering pass.  Launches only.
+struct KfCullView {
+  int NK;
+  int *cols;
+  int *erased, *locked, *pending, *n_rec;
+  int4 *rec;
+};
+__host__ __device__ __forceinline__ int *cull_octave(const KfCullView &X, int k) { return X.cols + (size_t)k * 3 * X.NK; }
+__host__ __device__ __forceinline__ float *cull_depth(const KfCullView &X, int k) {
+  return reinterpret_cast<float *>(X.cols + ((size_t)k * 3 + 1) * X.NK);
+}
+__host__ __device__ __forceinline__ float *cull_uright(const KfCullView &X, int k) {
+  return reinterpret_cast<float *>(X.cols + ((size_t)k * 3 + 2) * X.NK);
+}
+size_t cull_bytes(int max_kf, int NK);
+KfCullView cull_layout(void *block, int max_kf, int NK);
+int cull_init(const KfCullView &X, int max_kf, hipStream_t st);
+int cull_set_lock(const KfCullView &X, int k, int on, hipStream_t st);
+int cull_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, int current, float th_depth,
+                 hipStream_t st);
+int erase_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, int keyframe, hipStream_t st);
 
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
