@@ -1196,7 +1196,10 @@ enum {
   VO_TRACKER_LOCAL_MIN_DISTANCE = 30, VO_TRACKER_LOCAL_MAX_DISTANCE = 31, /* float */
   VO_TRACKER_LOCAL_DESC = 32,        /* uint8 [..][32] */
   VO_TRACKER_LOCAL_MAP_FLAGS = 33,   /* uint8: the flags as set / built (VO_TRACKER_LOCAL_FLAGS: after isInFrame) */
-  VO_TRACKER_LOCAL_LINK = 34         /* int32 */
+  VO_TRACKER_LOCAL_LINK = 34,        /* int32 */
+  VO_TRACKER_POSE_START = 35         /* double [batch][6]: the se3 the route's first solve started from: log of the Tcw given
+                                        (vo_tracker_set_last_frame, vo_tracker_set_ref_keyframe, and computed on the device
+                                        by vo_tracker_track_ref_keyframe_store) */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 int vo_tracker_sync(vo_tracker *t);

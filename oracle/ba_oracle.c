@@ -46,15 +46,6 @@ static void quat_rotate(const double q[4], const double v[3], double o[3]) {
   o[1] = v[1] + q[0] * uv[1] + (q[3] * uv[0] - q[1] * uv[2]);
   o[2] = v[2] + q[0] * uv[2] + (q[1] * uv[1] - q[2] * uv[0]);
 }
-static void quat_to_R(const double q[4], double R[9] /*row-major*/) {
-  const double tx = 2 * q[1], ty = 2 * q[2], tz = 2 * q[3];
-  const double twx = tx * q[0], twy = ty * q[0], twz = tz * q[0];
-  const double txx = tx * q[1], txy = ty * q[1], txz = tz * q[1];
-  const double tyy = ty * q[2], tyz = tz * q[2], tzz = tz * q[3];
-  R[0] = 1 - (tyy + tzz), R[1] = txy - twz, R[2] = txz + twy;
-  R[3] = txy + twz, R[4] = 1 - (txx + tzz), R[5] = tyz - twx;
-  R[6] = txz - twy, R[7] = tyz + twx, R[8] = 1 - (txx + tyy);
-}
 static void so3_exp_theta(const double om[3], double q[4], double *theta) {
   *theta = sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
   double half = 0.5 * (*theta), imag, real = cos(half);
@@ -98,10 +89,12 @@ void orc_se3_exp(const double xi[6], double q[4], double t[3]) {
   hat(om, Om);
   mat3_mul(Om, Om, Om2);
   if (theta < SMALL_EPS) {
-    quat_to_R(q, V);
+    /* V to second order; Sophus takes V = R here, off by theta |upsilon| / 2 */
+    for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0 ? 1.0 : 0.0) + 0.5 * Om[i] + (1. / 6.) * Om2[i];
   } else {
-    double t2 = theta * theta;
-    double a = (1 - cos(theta)) / t2, b = (theta - sin(theta)) / (t2 * theta);
+    double t2 = theta * theta, sh = sin(0.5 * theta);
+    /* 1 - cos(theta) as 2 sin^2(theta / 2): the difference loses every digit below 1e-8 */
+    double a = (2 * sh * sh) / t2, b = (theta - sin(theta)) / (t2 * theta);
     for (int i = 0; i < 9; i++) V[i] = (i % 4 == 0 ? 1.0 : 0.0) + a * Om[i] + b * Om2[i];
   }
   for (int i = 0; i < 3; i++) t[i] = V[i * 3] * ups[0] + V[i * 3 + 1] * ups[1] + V[i * 3 + 2] * ups[2];
@@ -114,7 +107,9 @@ void orc_se3_log(const double q[4], const double t[3], double xi[6]) {
   double Om[9], Om2[9], Vinv[9];
   hat(om, Om);
   mat3_mul(Om, Om, Om2);
-  double c = (theta < SMALL_EPS) ? (1. / 12.) : (1 - theta / (2 * tan(theta / 2))) / (theta * theta);
+  /* theta is negative for w < 0 (the same rotation, omega below pi) and c is even in it: select on |theta|.  Sophus
+     compares the signed theta and takes 1 / 12 for every w < 0 */
+  double c = (fabs(theta) < SMALL_EPS) ? (1. / 12.) : (1 - theta / (2 * tan(theta / 2))) / (theta * theta);
   for (int i = 0; i < 9; i++) Vinv[i] = (i % 4 == 0 ? 1.0 : 0.0) - 0.5 * Om[i] + c * Om2[i];
   for (int i = 0; i < 3; i++) xi[i] = Vinv[i * 3] * t[0] + Vinv[i * 3 + 1] * t[1] + Vinv[i * 3 + 2] * t[2];
   xi[3] = om[0], xi[4] = om[1], xi[5] = om[2];

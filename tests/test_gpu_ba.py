@@ -31,6 +31,13 @@ def test_se3_helpers(vo, orc):
         assert np.abs(vo.se3_log(R, t) - xi).max() < 1e-12
     R, t = vo.se3_exp(np.array([0.1, 0.2, 0.3, 1e-13, 0, 0]))
     assert np.abs(t - [0.1, 0.2, 0.3]).max() < 1e-12
+    # the grid of tests/test_se3_ref.py against the mpmath reference, with the library as it is loaded next to the device
+    import se3_ref as ref
+    for c in ref.cases():
+        R, t = vo.se3_exp(c["xi_d"])
+        Rr, tr = ref.exp(c["xi_d"])
+        assert max(ref.err(R, Rr), ref.err(t, tr)) < 1e-14, (c["th"], c["axis"], c["tn"])
+        assert ref.log_error(vo.se3_log(c["R"], c["t"]), c) < 1e-12, (c["th"], c["axis"], c["tn"])
 
 
 @pytest.mark.parametrize("seed", [0, 1, 2, 3])

@@ -43,14 +43,16 @@ def ctx(vo, orc):
     c.voc.close()
 
 
-def _relocalized(vo, c, max_local):
-    """a tracker behind vo_tracker_relocalize_store on the fixture -> (tracker, the store it read, slot ids [B][cap], status)"""
+def _relocalized(vo, c, max_local, G=None):
+    """a tracker behind vo_tracker_relocalize_store on the fixture (G: in that gauge of tests/gauge.py -- the slot ids must be
+    the same) -> (tracker, the store it read, slot ids [B][cap], status)"""
     import torch
+    import gauge
     trk = vo.Tracker(len(FRAMES), c.fx["cam5"], None, W, H, max_last=8, max_local=max_local, inv_depth_scale=float(c.fx["inv"]),
                      max_reloc_candidates=reloc_inputs.MAX_CAND, max_reloc_features=c.fx["nk"])
     store = vo.KeyFrameStore(len(c.kfs) + 4, c.fx["nk"])
     for k in c.kfs:
-        store.insert(k)
+        store.insert(k if G is None else dict(k, points=gauge.points(G, k["points"])))
     stride = max(len(ls) for ls in c.lists)
     cand = np.full((len(c.lists), stride), -1, np.int32)
     for f, ls in enumerate(c.lists):
@@ -62,7 +64,10 @@ def _relocalized(vo, c, max_local):
     assert list(status & 4) == [0, 0, 0, 4] and all((slots[f] >= 0).sum() >= 50 for f in range(3))
     if c.slots is None:
         c.slots = slots
-    assert np.array_equal(slots, c.slots)   # the same injection every time
+    ok = np.ones(len(FRAMES), bool) if G is None else (status & 4) == 0
+    # the same injection every time; in another gauge for the frames that relocalise -- what the failed frame keeps is the
+    # leak of candidates whose PnP found a few inliers, and RANSAC's masks hang on the float32 rounding of the points
+    assert np.array_equal(slots[ok], c.slots[ok])
     return trk, store, slots, status
 
 
@@ -426,3 +431,74 @@ def test_after_track_ref_keyframe_store_first_stage(vo, orc, rk_ctx):
     assert np.array_equal(oracle["assigned_local"], snaps[1]["ASSIGNED_LOCAL"][0, :len(k)])
     for key in snaps[0]:
         assert np.array_equal(snaps[0][key], snaps[1][key]), key
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The builder after a rigid change of the world frame (tests/gauge.py).  Its outputs are integers and copied values, so
+# the model comparison stays exact; the relocalisation that injects the slot ids runs in the new gauge too.
+RELOC_GAUGE_POSE_TOL = 1.54e-5
+
+
+def reloc_models(orc, fx, sub, lists, kfs, G):
+    """the CPU model of the relocalisation of every frame of the batch on the store's key-frames in gauge G"""
+    import gauge
+    import reloc_ref
+    out = []
+    for f, fr in enumerate(sub["frames"]):
+        cands = [dict(kfs[g], points=gauge.points(G, kfs[g]["points"])) for g in lists[f]]
+        out.append(reloc_ref.relocalize(orc, fr[0], fr[1], fr[2], fr[3], fr[4], sub["fnodes"][f], cands, fx["cam5"], fx["sf"]))
+    return out
+
+
+@pytest.mark.parametrize("name", ["skew_2.6_w_negative", "skew_2.4_w_positive", "y_pi_minus_0.02"])
+def test_builder_in_a_rotated_world_frame(vo, orc, ctx, name):
+    """the batch of test_builder_on_a_batch_of_four with every point at G P and every normal at R_G n.
+    1. Device against the model in the new gauge, exactly (_compare); the relocalised poses against reloc_ref within 1e-9.
+    2. Against the identity gauge: the slot ids after the relocalisation, the key-frame lists, counts, reference key-frames,
+    point ids, links and flags identical; the copied points and normals mapped back through G equal the identity gauge's to
+    the rounding of the two rigid maps (4e-15 at |P| < 20 m); the relocalised poses mapped back within
+    RELOC_GAUGE_POSE_TOL = 1.54e-5, ten times the worst deviation of the corrected model between the gauges on these frames,
+    1.54e-6, measured on the CPU (PnP reads float32 points, see tests/test_gpu_reloc_local_map.py).
+    The frame whose candidates all fail is compared with the model in its own gauge only: the slots it keeps are the leak
+    of PnP inlier masks, which the float32 rounding of the moved points changes in the model as well (y gauge)."""
+    import gauge
+    from vo_slam_test_amd import synth
+    c = ctx
+    G = gauge.GAUGES[name]
+    results = []
+    for g in (None, G):
+        rng = np.random.default_rng(2)
+        trk, keep, slots, status = _relocalized(vo, c, 1500, g)   # (asserts the slot ids of the identity gauge)
+        poses = trk.results()["pose"].copy()
+        pool = np.concatenate([_pool(slots[f:f + 1], rng, 120) for f in range(3)])
+        kfs = _synthetic(rng, 40, 5, 50, pool, p_bad=0.15, empty=(3, 17))
+        if g is not None:
+            kfs = [dict(k, points=gauge.points(g, k["points"]), normals=gauge.directions(g, k["normals"])) for k in kfs]
+        store = _device_store(vo, kfs, 50, max_keyframes=45)
+        trk.build_local_map(store)
+        after, want = _compare(trk, kfs, slots, status & 4, 1500)
+        got = {key: trk.get(getattr(trk, key)) for key in ARRAYS + ("LOCAL_KEYFRAMES", "LOCAL_N_KEYFRAMES", "LOCAL_N_POINTS", "LOCAL_REF_KF")}
+        results.append((after, want, got, poses, status.copy()))
+        trk.close(), store.close(), keep.close()
+    (a0, w0, g0, p0, s0), (a1, w1, g1, p1, s1) = results
+    models = reloc_models(orc, c.fx, c.sub, c.lists, c.kfs, G)
+    ok = (s0 & 4) == 0
+    assert np.array_equal(a0[ok], a1[ok]) and np.array_equal(s0, s1)
+    for f in range(len(FRAMES)):
+        for key in ("keyframes", "n_keyframes", "n_points", "best", "points", "capacity") + (("slots",) if ok[f] else ()):
+            assert w0[f][key] == w1[f][key], (f, key)
+    for key in ("LOCAL_KEYFRAMES", "LOCAL_N_KEYFRAMES", "LOCAL_N_POINTS", "LOCAL_REF_KF", "LOCAL_POINT_IDS", "LOCAL_LINK", "LOCAL_MAP_FLAGS",
+                "LOCAL_MIN_DISTANCE", "LOCAL_MAX_DISTANCE", "LOCAL_DESC"):
+        assert np.array_equal(g0[key], g1[key]), key
+    for f in range(len(FRAMES)):
+        n = len(w1[f]["points"])
+        back = (g1["LOCAL_POINTS"][f, :n] - G[1]) @ G[0]
+        assert n > 0 or s1[f] & 4   # (the failed frame has no local map)
+        assert n == 0 or np.abs(back - g0["LOCAL_POINTS"][f, :n]).max() < 4e-15 * 20 and np.abs(g1["LOCAL_NORMALS"][f, :n] @ G[0] - g0["LOCAL_NORMALS"][f, :n]).max() < 4e-15 * 20
+        # (the failed frame too: its pose is what the last solve of a rejected candidate left, test_control_plane_parity)
+        assert gauge.pose_distance(synth.se3_exp(p1[f]), synth.se3_exp(models[f]["pose"])) < 1e-9, f
+        if s1[f] & 4:
+            continue
+        d = gauge.pose_distance(gauge.pose6_back(G, p1[f]), synth.se3_exp(p0[f]))
+        print(f"{name} frame {f}: relocalised pose, rotated gauge mapped back - identity gauge {d:.3g}")
+        assert d < RELOC_GAUGE_POSE_TOL, (f, d)

@@ -73,19 +73,17 @@ class _Ctx:
     pass
 
 
-@pytest.fixture(scope="module")
-def ctx(vo, orc):
-    import torch
+def route_inputs(orc, transform, c=None):
+    """everything of the fixture that needs no device: frames, maps, key-frames (transform: descriptors -> node ids, the
+    vocabulary's or the oracle's -- the same numbers, tests/test_gpu_match.py)"""
     from vo_slam_test_amd.tracking import stack_maps
-    c = _Ctx()
+    c = c or _Ctx()
     c.imgs = synth.make_frames(B, start=80)
     c.raw = np.stack([synth.make_depth(80 + i) for i in range(B)])
     c.inv = np.float32(1.0) / np.float32(synth.DEPTH_SCALE)
     c.cam5 = synth.CAM.astype(np.float32)
     c.sf = np.array(list(orc.orb_params().scale)[:8], np.float32)
     c.ofr = _oracle_frames(orc, c.imgs, c.raw, c.inv, c.cam5)
-    vd = synth.make_vocabulary(3, k=8, L=4)
-    c.voc = vo.Vocabulary(vd["L"], vd["child_start"], vd["children"], vd["node_desc"], vd["node_weight"], vd["word_id"])
     c.maps = [synth.make_tracking_map(fr[2], fr[3], fr[0]["octave"], fr[0]["angle"], fr[1], fr[5], seed=30 + f) for f, fr in enumerate(c.ofr)]
     rng = np.random.default_rng(5)
     c.kfs = []
@@ -95,7 +93,7 @@ def ctx(vo, orc):
         desc = last["desc"][perm].copy()
         if f == 1:
             desc = rng.integers(0, 256, desc.shape, dtype=np.uint8)   # an unrelated key-frame
-        _, _, node = c.voc.transform(desc, 3)
+        node = transform(desc)
         c.kfs.append(dict(points=last["points"][perm], flags=last["flags"][perm], angle=last["angle"][perm], desc=desc, nodes=node))
     # two more key-frames that belong to neither frame: other points, random descriptors
     c.others = []
@@ -103,12 +101,22 @@ def ctx(vo, orc):
         src = c.kfs[s]
         n = len(src["flags"]) - 7 * (s + 1)
         desc = rng.integers(0, 256, (n, 32), dtype=np.uint8)
-        _, _, node = c.voc.transform(desc, 3)
+        node = transform(desc)
         c.others.append(dict(points=src["points"][:n] + 0.25, flags=src["flags"][:n], angle=src["angle"][:n], desc=desc, nodes=node))
     c.nk = max(len(k["flags"]) for k in c.kfs)
     c.n_local = max(len(m[3]["flags"]) for m in c.maps)
     c.local = stack_maps(c.maps, 3, ("points", "normals", "min_dist", "max_dist", "valid", "desc", "link"), c.n_local)
     c.Tcw = np.stack([m[0] for m in c.maps]).astype(np.float64)
+    return c
+
+
+@pytest.fixture(scope="module")
+def ctx(vo, orc):
+    import torch
+    c = _Ctx()
+    vd = synth.make_vocabulary(3, k=8, L=4)
+    c.voc = vo.Vocabulary(vd["L"], vd["child_start"], vd["children"], vd["node_desc"], vd["node_weight"], vd["word_id"])
+    route_inputs(orc, lambda desc: c.voc.transform(desc, 3)[2], c)
     c.d_Tcw = torch.from_numpy(c.Tcw).cuda()
     c.d_ref = torch.tensor(REF_KF, dtype=torch.int32, device="cuda")
     c.depth = c.raw.view(np.uint16)
@@ -314,3 +322,117 @@ def test_two_calls_back_to_back_without_a_host_round_trip(vo, ctx):
         assert torch.cuda.mem_get_info()[0] == free_before
         small.close()
     trk.close(), st.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The route after a rigid change of the world frame, one gauge per frame (tests/gauge.py): the store's key-frame points and
+# the local map go to G P / R_G n, the Tcw handed over to Tcw G^-1.  k_ref_kf_gather takes the start pose of the first
+# solve from that matrix on the device (se3_log_from_R); vo_tracker_get(VO_TRACKER_POSE_START) reads it.
+GAUGE_POSE_TOL = 9.8e-15
+# sign of w out of the matrix -> quaternion step for the two frames' Tcw: eleven w < 0 (seven of them on grid poses), three w > 0
+GAUGE_W = {"skew_2.6_w_negative": (-1, -1), "skew_2.4_w_positive": (1, 1), "y_pi_minus_0.02": (-1, -1), "grid_tr_switch": (-1, 1),
+           "grid_3.0_and_pi": (-1, -1), "grid_2.2_and_2.6": (-1, -1), "grid_pi_1e-3_and_3.0": (-1, -1)}
+
+
+def _grid_pose(angle, axis, tn=0.3):
+    """(R, t) of the pose grid of tests/se3_ref.py"""
+    import se3_ref as ref
+    c = [c for c in ref.cases() if c["th"] == angle and c["axis"] == axis and c["tn"] == tn]
+    return c[0]["R"], c[0]["t"]
+
+
+def gauge_cases(c):
+    """name -> the two frames' gauges: the three of tests/gauge.py, and four pairs that put the Tcw handed over onto poses of
+    the se3_ref grid -- either side of the tr = 0 switch of the matrix -> quaternion step about -x (w < 0 beyond it), 3.0 rad
+    about an axis led by -z and 1e-7 short of pi about -y, 2.2 rad about -z and 2.6 about the axis led by -z, 1e-3 short of
+    pi about -x and 3.0 about -y (all w < 0)"""
+    import gauge
+    import se3_ref as ref
+    old = [(T[:9].reshape(3, 3), T[9:]) for T in c.Tcw]
+    th = 2 * ref.PI / 3
+    out = {name: [G, G] for name, G in gauge.GAUGES.items() if name != "identity"}
+    out["grid_tr_switch"] = [gauge.from_Tcw(_grid_pose(th + 1e-9, 3), old[0]), gauge.from_Tcw(_grid_pose(th - 1e-9, 3), old[1])]
+    out["grid_3.0_and_pi"] = [gauge.from_Tcw(_grid_pose(3.0, 8), old[0]), gauge.from_Tcw(_grid_pose(ref.PI - 1e-7, 4), old[1])]
+    out["grid_2.2_and_2.6"] = [gauge.from_Tcw(_grid_pose(2.2, 5), old[0]), gauge.from_Tcw(_grid_pose(2.6, 8), old[1])]
+    out["grid_pi_1e-3_and_3.0"] = [gauge.from_Tcw(_grid_pose(ref.PI - 1e-3, 3), old[0]), gauge.from_Tcw(_grid_pose(3.0, 4), old[1])]
+    return out
+
+
+def gauged_inputs(c, Gs):
+    """(key-frames, local map, Tcw [B, 12], pose6 [B, 6] through synth.se3_log) in the frames' new gauges"""
+    import gauge
+    kfs = [dict(k, points=gauge.points(Gs[f], k["points"])) for f, k in enumerate(c.kfs)]
+    local = dict(c.local)
+    local["points"] = np.stack([gauge.points(Gs[f], c.local["points"][f]) for f in range(B)])
+    local["normals"] = np.stack([gauge.directions(Gs[f], c.local["normals"][f]) for f in range(B)])
+    Tcw = np.stack([gauge.Tcw12(Gs[f], c.Tcw[f]) for f in range(B)])
+    pose6 = np.stack([synth.se3_log(T[:9].reshape(3, 3), T[9:]) for T in Tcw])
+    return kfs, local, Tcw, pose6
+
+
+def gauged_oracle(orc, c, fnodes, kfs, local, pose6):
+    from track_ref import track_frame_ref_keyframe
+    out = []
+    for f in range(B):
+        k, d, ux, uy, ur, _ = c.ofr[f]
+        kf = {kk: (_pad(v, c.nk) if kk != "nodes" else _pad_nodes(v, c.nk)) for kk, v in kfs[f].items()}
+        lo = {kk: local[kk][f] for kk in local}
+        out.append(track_frame_ref_keyframe(orc, k, d, ux, uy, ur, pose6[f], kf, fnodes[f], lo, c.cam5, c.sf, W, H))
+    return out
+
+
+ORACLE_SAME = ("assigned_first", "n_first", "inliers_1", "observed_inliers_1", "assigned_local", "n_local", "inliers_2", "n_tracked",
+               "local_flags", "local_level", "feature_outlier")
+
+
+@pytest.mark.parametrize("name", ["skew_2.6_w_negative", "skew_2.4_w_positive", "y_pi_minus_0.02", "grid_tr_switch", "grid_3.0_and_pi",
+                                  "grid_2.2_and_2.6", "grid_pi_1e-3_and_3.0"])
+def test_store_route_in_a_rotated_world_frame(vo, orc, ctx, name):
+    """1. The start pose out of k_ref_kf_gather against the mpmath logarithm of the Tcw handed over (1e-12, the log bound of
+    tests/test_se3_ref.py); over the seven cases eleven Tcw have w < 0 out of the matrix -> quaternion step, seven of them
+    drawn from the se3_ref grid, and three w > 0, on both sides of tr = 0.  Device against the oracle in the new gauge as
+    test_store_route_against_the_oracle: assignments and counts equal, poses within 1e-9 (as (R, t)).
+    2. Against the identity gauge (the fixture's reference): every assignment, flag and count identical; poses mapped back
+    through G within GAUGE_POSE_TOL, ten times the worst deviation of the corrected oracle between the gauges over these
+    cases, 9.8e-16, measured on the CPU."""
+    import torch
+    import gauge
+    import se3_ref as ref
+    c = ctx
+    Gs = gauge_cases(c)[name]
+    kfs, local, Tcw, pose6 = gauged_inputs(c, Gs)
+    assert tuple(gauge.quat_w_sign(T[:9]) for T in Tcw) == GAUGE_W[name]
+    fnodes = [c.voc.transform(c.ofr[f][1], 3)[2] for f in range(B)]
+    want = gauged_oracle(orc, c, fnodes, kfs, local, pose6)
+    want0 = gauged_oracle(orc, c, fnodes, c.kfs, c.local, np.stack([m[1] for m in c.maps]))
+    st = vo.KeyFrameStore(6, c.nk)
+    for k in (c.others[0], kfs[1], c.others[1], kfs[0]):
+        st.insert(_store_kf(k))
+    trk = vo.Tracker(B, c.cam5, None, W, H, max_last=c.nk, max_local=c.n_local, inv_depth_scale=float(c.inv))
+    trk.set_local_map(local["points"], local["normals"], local["min_dist"], local["max_dist"], local["valid"], local["desc"], link=local["link"])
+    trk.track_ref_keyframe_store(st, c.voc, c.d_ref, torch.from_numpy(Tcw).cuda(), c.imgs, c.depth)
+    got = _collect(trk)
+    start = trk.get(trk.POSE_START)
+    trk.close(), st.close()
+    for f in range(B):
+        n = len(c.ofr[f][0])
+        wf, w0 = want[f], want0[f]
+        e = ref.err(start[f], ref.log(Tcw[f][:9].reshape(3, 3), Tcw[f][9:]))
+        print(f"{name} frame {f}: w {gauge.quat_w_sign(Tcw[f][:9]):+.0f}, tr {np.trace(Tcw[f][:9].reshape(3, 3)):+.3g}, start pose - mpmath {e:.3g}")
+        assert e < 1e-12, (f, e)
+        # 1. device against oracle, this gauge
+        assert np.array_equal(got["ASSIGNED_LAST"][f, :n], wf["assigned_first"]) and got["n_matches_last"][f] == wf["n_first"]
+        assert gauge.pose_distance(synth.se3_exp(got["POSE_FIRST"][f]), synth.se3_exp(wf["pose_1"])) < 1e-9
+        assert np.array_equal(got["ASSIGNED_LOCAL"][f, :n], wf["assigned_local"]) and got["n_matches_local"][f] == wf["n_local"]
+        assert got["n_inliers"][f] == wf["inliers_2"] and got["n_tracked"][f] == wf["n_tracked"]
+        assert gauge.pose_distance(synth.se3_exp(got["pose"][f]), synth.se3_exp(wf["pose_2"])) < 1e-9
+        # 2. against the identity gauge: the oracle's and the device's (ctx.want)
+        for key in ORACLE_SAME:
+            assert np.array_equal(wf[key], w0[key]), key
+        for key in ("ASSIGNED_LAST", "ASSIGNED_LOCAL", "INLIERS_FIRST", "OBSERVED_INLIERS_FIRST", "FEATURE_HAS_POINT", "FEATURE_OUTLIER",
+                    "n_tracked", "n_inliers", "n_matches_last", "n_matches_local", "status"):
+            assert np.array_equal(got[key][f], c.want[key][f]), key
+        for key in ("POSE_FIRST", "pose"):
+            d = gauge.pose_distance(gauge.pose6_back(Gs[f], got[key][f]), synth.se3_exp(c.want[key][f]))
+            print(f"{name} frame {f} {key}: rotated gauge mapped back - identity gauge {d:.3g}")
+            assert d < GAUGE_POSE_TOL, (key, f, d)

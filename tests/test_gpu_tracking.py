@@ -368,3 +368,100 @@ def test_track_ref_keyframe_route(vo, orc):
         assert res["n_tracked"][f] == want["n_tracked"]
     assert res["n_matches_last"][0] > 200 and res["n_matches_last"][1] < 15
     trk.close(), voc.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The same route after a rigid change of the world frame (tests/gauge.py): points G P, Tcw G^-1, normals R_G n.  The images
+# are untouched, so every pixel-level result keeps its exact-arithmetic value while the poses move to the far side of
+# SO(3) -- beyond 120 degrees with w < 0 and with w > 0 out of the matrix -> quaternion step, and next to pi.
+GAUGE_POSE_TOL = 9.3e-15
+
+
+class _GaugeCtx:
+    pass
+
+
+def gauge_inputs(orc):
+    """frames 60..62 undistorted (the inputs of test_tracked_frames_match_the_oracle) and their maps"""
+    c = _GaugeCtx()
+    c.B, c.W, c.H = 3, 640, 480
+    c.imgs = synth.make_frames(c.B, start=60)
+    c.raw = np.stack([synth.make_depth(60 + i) for i in range(c.B)])
+    c.inv = np.float32(1.0) / np.float32(synth.DEPTH_SCALE)
+    c.cam5 = synth.CAM.astype(np.float32)
+    c.sf = np.array(list(orc.orb_params().scale)[:8], np.float32)
+    c.frames = _oracle_frames(orc, c.imgs, c.raw, c.inv, c.cam5, None, c.W, c.H)
+    c.maps = [synth.make_tracking_map(fr[2], fr[3], fr[0]["octave"], fr[0]["angle"], fr[1], fr[5], seed=f) for f, fr in enumerate(c.frames)]
+    return c
+
+
+def gauge_oracle(orc, c, maps):
+    return [track_frame(orc, fr[0], fr[1], fr[2], fr[3], fr[4], m[0], m[1], m[2], m[3], c.cam5, c.sf, c.W, c.H) for fr, m in zip(c.frames, maps)]
+
+
+def _gauge_device(vo, c, maps):
+    from vo_slam_test_amd.tracking import load_maps
+    n_last = max(len(m[2]["flags"]) for m in maps)
+    n_local = max(len(m[3]["flags"]) for m in maps)
+    trk = vo.Tracker(c.B, c.cam5, None, c.W, c.H, max_last=n_last, max_local=n_local, inv_depth_scale=float(c.inv))
+    load_maps(trk, maps)
+    trk.track(c.imgs, c.raw.view(np.uint16))
+    out = dict(trk.results())
+    for key in ("ASSIGNED_LAST", "ASSIGNED_LOCAL", "POSE_FIRST", "POSE_START", "INLIERS_FIRST", "OBSERVED_INLIERS_FIRST", "LOCAL_FLAGS",
+                "LOCAL_U", "LOCAL_V", "LOCAL_UR", "LOCAL_LEVEL", "LOCAL_VIEWCOS"):
+        out[key] = trk.get(getattr(trk, key))
+    trk.close()
+    return out
+
+
+@pytest.fixture(scope="module")
+def gauge_ctx(vo, orc):
+    c = gauge_inputs(orc)
+    c.want0 = gauge_oracle(orc, c, c.maps)   # the identity gauge: computed once, never changed
+    c.got0 = _gauge_device(vo, c, c.maps)
+    return c
+
+
+@pytest.mark.parametrize("name", ["skew_2.6_w_negative", "skew_2.4_w_positive", "y_pi_minus_0.02"])
+def test_tracked_frames_in_a_rotated_world_frame(vo, orc, gauge_ctx, name):
+    """1. Device against oracle in the new gauge exactly as test_tracked_frames_match_the_oracle: assignments and
+    isInFrame's outputs bit-exact, poses within 1e-9 (as (R, t)), counts identical; the start pose that the route took from
+    the Tcw handed over against the mpmath logarithm (1e-12).
+    2. Against the identity gauge: assignments, flags, levels and every count identical, poses mapped back through G
+    within GAUGE_POSE_TOL = 9.3e-15 -- ten times the worst deviation of the corrected oracle between the gauges on these
+    frames, measured on the CPU."""
+    import gauge
+    import se3_ref as ref
+    c = gauge_ctx
+    G = gauge.GAUGES[name]
+    maps = [gauge.tracking_map(G, m) for m in c.maps]
+    w = [gauge.quat_w_sign(m[0][:9]) for m in maps]
+    assert all(np.trace(m[0][:9].reshape(3, 3)) <= 0 or "pi" in name for m in maps)   # beyond 120 degrees
+    assert all(s < 0 for s in w) if "negative" in name or "pi" in name else all(s > 0 for s in w)
+    want = gauge_oracle(orc, c, maps)
+    got = _gauge_device(vo, c, maps)
+    for f in range(c.B):
+        n, m = len(c.frames[f][0]), len(maps[f][3]["valid"])
+        wf, w0 = want[f], c.want0[f]
+        # 1. device against oracle, this gauge
+        assert ref.err(got["POSE_START"][f], ref.log(maps[f][0][:9].reshape(3, 3), maps[f][0][9:])) < 1e-12
+        assert np.array_equal(got["ASSIGNED_LAST"][f, :n], wf["assigned_last"]) and got["n_matches_last"][f] == wf["n_last"]
+        assert got["INLIERS_FIRST"][f] == wf["inliers_1"] and got["OBSERVED_INLIERS_FIRST"][f] == wf["observed_inliers_1"]
+        assert gauge.pose_distance(synth.se3_exp(got["POSE_FIRST"][f]), synth.se3_exp(wf["pose_1"])) < 1e-9
+        assert np.array_equal(got["LOCAL_FLAGS"][f, :m], wf["local_flags"]) and np.array_equal(got["LOCAL_LEVEL"][f, :m], wf["local_level"])
+        for key, k2 in (("LOCAL_U", "local_u"), ("LOCAL_V", "local_v"), ("LOCAL_UR", "local_ur"), ("LOCAL_VIEWCOS", "local_viewcos")):
+            assert np.array_equal(got[key][f, :m].view(np.uint32), wf[k2].view(np.uint32)), key
+        assert np.array_equal(got["ASSIGNED_LOCAL"][f, :n], wf["assigned_local"]) and got["n_matches_local"][f] == wf["n_local"]
+        assert got["n_inliers"][f] == wf["inliers_2"] and got["n_tracked"][f] == wf["n_tracked"] and got["status"][f] == 0
+        assert gauge.pose_distance(synth.se3_exp(got["pose"][f]), synth.se3_exp(wf["pose_2"])) < 1e-9
+        # 2. this gauge against the identity gauge: oracle and device
+        for key in ("assigned_last", "assigned_local", "local_flags", "local_level", "n_last", "n_local", "inliers_1", "inliers_2",
+                    "observed_inliers_1", "n_tracked"):
+            assert np.array_equal(wf[key], w0[key]), key
+        for key in ("ASSIGNED_LAST", "ASSIGNED_LOCAL", "LOCAL_FLAGS", "LOCAL_LEVEL", "INLIERS_FIRST", "OBSERVED_INLIERS_FIRST", "n_inliers",
+                    "n_tracked", "n_matches_last", "n_matches_local", "status"):
+            assert np.array_equal(got[key][f], c.got0[key][f]), key
+        for key in ("POSE_FIRST", "pose"):
+            d = gauge.pose_distance(gauge.pose6_back(G, got[key][f]), synth.se3_exp(c.got0[key][f]))
+            print(f"{name} frame {f} {key}: rotated gauge mapped back - identity gauge {d:.3g}")
+            assert d < GAUGE_POSE_TOL, (key, f, d)

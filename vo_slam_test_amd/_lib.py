@@ -467,7 +467,8 @@ class Tracker:
      LOCAL_FLAGS, LOCAL_U, LOCAL_V, LOCAL_UR, LOCAL_LEVEL, LOCAL_VIEWCOS, KEYPOINT_COUNTS, FEATURE_OUTLIER,
      RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK,
      RELOC_CANDIDATES, RELOC_N_CANDIDATES, LOCAL_KEYFRAMES, LOCAL_N_KEYFRAMES, LOCAL_N_POINTS, LOCAL_REF_KF, LOCAL_POINT_IDS,
-     LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK) = range(35)
+     LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK,
+     POSE_START) = range(36)
     LOCAL_MAX_KEYFRAMES = 84
     RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
@@ -761,7 +762,8 @@ class Tracker:
             self.LOCAL_POINT_IDS: ((B, max(nl, 1)), np.int32), self.LOCAL_POINTS: ((B, max(nl, 1), 3), np.float64),
             self.LOCAL_NORMALS: ((B, max(nl, 1), 3), np.float64), self.LOCAL_MIN_DISTANCE: ((B, max(nl, 1)), np.float32),
             self.LOCAL_MAX_DISTANCE: ((B, max(nl, 1)), np.float32), self.LOCAL_DESC: ((B, max(nl, 1), 32), np.uint8),
-            self.LOCAL_MAP_FLAGS: ((B, max(nl, 1)), np.uint8), self.LOCAL_LINK: ((B, max(nl, 1)), np.int32)}[what]
+            self.LOCAL_MAP_FLAGS: ((B, max(nl, 1)), np.uint8), self.LOCAL_LINK: ((B, max(nl, 1)), np.int32),
+            self.POSE_START: ((B, 6), np.float64)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out

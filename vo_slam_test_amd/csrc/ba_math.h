@@ -108,7 +108,11 @@ VO_HD Se3 se3_exp(const double xi[6]) {
   const double wxu[3] = {wy * u[2] - wz * u[1], wz * u[0] - wx * u[2], wx * u[1] - wy * u[0]};
   const double wwxu[3] = {wy * wxu[2] - wz * wxu[1], wz * wxu[0] - wx * wxu[2], wx * wxu[1] - wy * wxu[0]};
   if (theta < kSmallEps) {
-    quat_rotate(T.q, u, T.t);  // V = R in the small-angle branch
+    // V to second order.  Sophus takes V = R here, which is off by theta |u| / 2 (1e-10 for a 2 m translation) just
+    // below the switch: a deliberate deviation
+    T.t[0] = u[0] + 0.5 * wxu[0] + (1. / 6.) * wwxu[0];
+    T.t[1] = u[1] + 0.5 * wxu[1] + (1. / 6.) * wwxu[1];
+    T.t[2] = u[2] + 0.5 * wxu[2] + (1. / 6.) * wwxu[2];
   } else {
     const double t2 = theta * theta;
     double a, b;  // 1-cos = 2 sin^2(t/2)
@@ -125,7 +129,10 @@ VO_HD Se3 se3_exp(const double xi[6]) {
   return T;
 }
 
-// Sophus SE3::log
+// Sophus SE3::log, for either sign of the quaternion: with w < 0 the half angle atan(n / w) and with it theta = f n are
+// negative (omega = f q_xyz is the rotation vector of the same rotation, below pi), and the coefficient c is even in
+// theta -- so the small-angle selection looks at |theta|.  Sophus compares the signed theta and takes 1 / 12 for every
+// w < 0: a deliberate deviation
 VO_HD void se3_log(const Se3 &T, double xi[6]) {
   const double n = sqrt(T.q[1] * T.q[1] + T.q[2] * T.q[2] + T.q[3] * T.q[3]);
   const double w = T.q[0];
@@ -137,7 +144,7 @@ VO_HD void se3_log(const Se3 &T, double xi[6]) {
   const double theta = f * n;
   const double wx = f * T.q[1], wy = f * T.q[2], wz = f * T.q[3];
   // theta/2 = atan(n/w)  =>  tan(theta/2) = n/w: no second transcendental
-  const double c = (theta < kSmallEps) ? (1. / 12.) : (1 - theta * w / (2 * n)) / (theta * theta);
+  const double c = (fabs(theta) < kSmallEps) ? (1. / 12.) : (1 - theta * w / (2 * n)) / (theta * theta);
   const double *t = T.t;
   const double wxt[3] = {wy * t[2] - wz * t[1], wz * t[0] - wx * t[2], wx * t[1] - wy * t[0]};
   const double wwxt[3] = {wy * wxt[2] - wz * wxt[1], wz * wxt[0] - wx * wxt[2], wx * wxt[1] - wy * wxt[0]};
@@ -191,7 +198,7 @@ VO_HD void se3_log_fast(const Se3 &T, double xi[6]) {
   const double f = 2 * atan(n * inv_fast(w)) * rn;
   const double theta = f * n;
   const double wx = f * T.q[1], wy = f * T.q[2], wz = f * T.q[3];
-  const double c = (theta < kSmallEps) ? (1. / 12.) : (1 - 0.5 * f * w) * inv_fast(theta * theta);
+  const double c = (fabs(theta) < kSmallEps) ? (1. / 12.) : (1 - 0.5 * f * w) * inv_fast(theta * theta);
   const double *t = T.t;
   const double wxt[3] = {wy * t[2] - wz * t[1], wz * t[0] - wx * t[2], wx * t[1] - wy * t[0]};
   const double wwxt[3] = {wy * wxt[2] - wz * wxt[1], wz * wxt[0] - wx * wxt[2], wx * wxt[1] - wy * wxt[0]};

@@ -1545,6 +1545,7 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     case VO_TRACKER_LOCAL_DESC: b = t->d.q1_desc, bytes = B * (size_t)t->n_local * 32; break;
     case VO_TRACKER_LOCAL_MAP_FLAGS: b = t->d.pf1, bytes = B * (size_t)t->n_local; break;
     case VO_TRACKER_LOCAL_LINK: b = t->d.link1, bytes = B * (size_t)t->n_local * 4; break;
+    case VO_TRACKER_POSE_START: b = t->d.pose0, bytes = B * 48; break;
     default: return VO_ERR_INVALID;
   }
   if (!b) {

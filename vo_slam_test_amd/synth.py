@@ -87,7 +87,8 @@ def se3_exp(xi):
         V = np.eye(3) + 0.5 * Om
     else:
         R = np.eye(3) + np.sin(th) / th * Om + (1 - np.cos(th)) / th**2 * Om @ Om
-        V = np.eye(3) + (1 - np.cos(th)) / th**2 * Om + (th - np.sin(th)) / th**3 * Om @ Om
+        # 1 - cos(th) as 2 sin^2(th / 2): the difference has no digits left below 1e-8
+        V = np.eye(3) + 2 * np.sin(th / 2)**2 / th**2 * Om + (th - np.sin(th)) / th**3 * Om @ Om
     return R, V @ ups
 
 
@@ -115,8 +116,10 @@ def _octaves(rng, n):
     return rng.choice(8, size=n, p=QUOTAS / QUOTAS.sum())
 
 
-def make_pose_problem(i: int = 0, n: int = 1000, outlier_frac: float = 0.10, mono_frac: float = 0.10):
-    """Config 2: 1 frame x n observations; true pose identity, perturbed initial guess."""
+def make_pose_problem(i: int = 0, n: int = 1000, outlier_frac: float = 0.10, mono_frac: float = 0.10, true_pose=None):
+    """Config 2: 1 frame x n observations; true pose identity, perturbed initial guess.  With true_pose = (R, t) the
+    same observations are those of a camera at that pose: the world points become T^-1 times the camera points and the
+    initial guess log(exp(perturbation) T)."""
     rng = _rng(42 + i)
     z = rng.uniform(0.5, 6.0, n)
     u = rng.uniform(20, 620, n)
@@ -134,6 +137,11 @@ def make_pose_problem(i: int = 0, n: int = 1000, outlier_frac: float = 0.10, mon
     obs = obs.astype(np.float32).astype(np.float64)
     xi0 = np.concatenate([rng.uniform(-0.05, 0.05, 3), rng.uniform(-0.05, 0.05, 3)])
     inv_sigma = 1.0 / (np.float32(1.2) ** octv.astype(np.float32)).astype(np.float64)
+    if true_pose is not None:
+        Rt, tt = np.asarray(true_pose[0], np.float64), np.asarray(true_pose[1], np.float64)
+        P = (P - tt) @ Rt  # rows: R^T (p - t)
+        R0, t0 = se3_exp(xi0)
+        xi0 = se3_log(R0 @ Rt, R0 @ tt + t0)
     return dict(pts=np.ascontiguousarray(P), obs=np.ascontiguousarray(obs), inv_sigma=inv_sigma,
                 cam=CAM.copy(), pose0=xi0)
 
