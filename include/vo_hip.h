@@ -1055,6 +1055,80 @@ int vo_kfstore_cull_result(vo_kfstore *s, int32_t *n_candidates, int32_t *keyfra
                            int32_t *decision);
 int vo_kfstore_cull_state(vo_kfstore *s, int keyframe, int32_t *erased, int32_t *locked, int32_t *pending);
 int vo_kfstore_get_flags(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *bad);
+/* New map points created on the device: LocalMapping::createNewMapPoints (localMapping.cpp:132-361)
+ * with computeF12 (:526-536), Matcher::searchForTriangulation (matcher.cpp:867-1010) and the MapPoint constructor,
+ * addObservation, computeDescriptor and updateNormalAndDepth (mappoint.cpp:36-179) for a point with two holders, so that a
+ * store carries insert -> connections -> new points -> local map -> cull without the host computing anything.  A store
+ * that does not call enable_mapping allocates and behaves exactly as before; every entry point of this block except
+ * get_points returns VO_ERR_INVALID on it.
+ * enable_mapping: valid only on an EMPTY store on which vo_kfstore_enable_culling has succeeded (the step reads octave,
+ * depth, u_right, erased and the graph row), else VO_ERR_INVALID.  cam = fx, fy, cx, cy, bf, b as the floats Camera holds
+ * (b_ = bf_ / fx_ is the caller's); 1 <= n_levels <= 16 with scale_factors = scaleFactors_; first_point_id >= 0 = the first
+ * id the store hands out (MapPoint::factory_id_).  max_features above 16384 is VO_ERR_CAPACITY (k_node_replay's LDS).
+ * Allocates, with K = max_keyframes, N = max_features and every array rounded up to 16 bytes: Tcw per key-frame as 12
+ * doubles (R row-major, then t; zero until set) with the pose-set word in a thirteenth slot (104 K); unKeypoints_[i].pt per
+ * feature as two float columns, a key-frame's side by side (8 K N); the id counter (16); the result record (176) and its created rows (160 N); the scratch of ONE neighbour
+ * step -- query list and claims (32 N), claimable bytes (N), match12 (4 N), the argument block (304), the match count (16),
+ * the step's geometry (336): 8 K N + 104 K + 197 N + 848 bytes as listed, 4 249 848 at 500 key-frames of 1000 features,
+ * and 4 249 856 allocated there (the rounding adds 8 to the claimable bytes).  Synchronises once.
+ * set_pose: Tcw12 = R row-major then t (host, doubles); one copy, synchronises once.  set_pose_dev: the same from device
+ * memory, enqueues only.  set_keypoint_xy: xy [n][2] (host, floats; n as inserted) = unKeypoints_[i].pt; one copy,
+ * synchronises once.  set_keypoint_xy_dev: device array, enqueues only; it must stay untouched until the stream has passed
+ * the call.  All four validate the key-frame number against [0, size).  next_point_id: synchronises; the id the next
+ * created point gets.
+ * create_map_points(current, max_neighbors): current in [0, size) and max_neighbors in [1, 10] are validated (the
+ * reference leaves after the first neighbour when key-frames are waiting, :163: the caller says which case holds);
+ * everything else is ENQUEUED on the store's stream: no host synchronisation, no device-to-host copy, no allocation;
+ * three launches per neighbour step, 3 * max_neighbors per call.  The result is that of the reference called once:
+ *  1 neighbours: the first max_neighbors entries of current's graph row (getBestCovisibleKFs(10), copied at :136) as the
+ *    call finds them, in order.  bad(kf): skipped (:167).  (float)|Owi - Owc| < b: skipped (:172-174).  A neighbour without a
+ *    pose: skipped, and the sticky VO_KFSTORE_CONNECTIONS_INVALID is raised.  current erased or without a pose: the call
+ *    creates nothing, the record is empty and the same bit is raised.
+ *  2 per neighbour, in double with every operation rounded on its own, in the order DESIGN.md section 4j writes down:
+ *    Ow = -R^T t, R12 = R1 R2^T, t12 = t1 - R12 t2, F12 = K^-T [t12]x R12 K^-1 in closed form, and the epipole
+ *    camera2pixel(R2 Ow1 + t2) rounded to float (matcher.cpp:887-891).
+ *  3 searchForTriangulation(current, kf, F12, checkRot = true), bit-exact as vo_match_triangulation is; both FeatureVectors
+ *    are the store's; "has a map point" is flags bit 0 AS THE STEP FINDS IT (the reference tests the pointer, which is
+ *    non-null for a bad point too: the store folds "exists and is not bad" into bit 0 -- a choice of this restatement), so a
+ *    feature neighbour i received a point for is out of neighbour i + 1's search, claims nothing there and enters no
+ *    rotation histogram: what vo_match_triangulation_batch, whose searches are independent, cannot give.
+ *  4 per match (idx1, idx2) in ascending idx1 (:192-341): pcam through the float pixel2camera(kp, 1); cosParallaxRay in
+ *    double rounded to float; cosParallaxDepth1 when stereo1, cosParallaxDepth2 ONLY when !stereo1 && stereo2 (the
+ *    `else if` of :222 -- a quirk, reproduced); the point from the linear triangulation (vo_triangulate's arithmetic,
+ *    |x3| < 1e-8 skips), else key-point 1 back-projected at depth1, else key-point 2 at depth2, else the match is skipped;
+ *    z1 <= 0 and z2 <= 0 reject; the float reprojection gates 5.991 (no u_right) and 7.815 (with the u - bf / z term) over
+ *    scaleFactors[octave]^2; a distance below 1e-6 rejects; the scale-consistency gate with 1.5f * scaleFactors[1].
+ *  5 commit (:344-355): the id from the counter in creation order (neighbour order, then ascending idx1); into feature idx1
+ *    of current and idx2 of the neighbour: flags = 3 (bit 0 | bit 1), the id, the point (the float SVD result widened, or
+ *    the back-projection's doubles), point_desc = the descriptor of the LOWER-NUMBERED of the two key-frames
+ *    (computeDescriptor with two holders: both medians are 0 and the test is strict), min / max distance
+ *    (max = (float)|p - Owc| * scaleFactors[octave[idx1]], min = max / scaleFactors[n_levels - 1]) and, in the normals
+ *    column, the mean of the two unit vectors (p - Ow) / |p - Ow|.  Connection weights do not change (the reference does
+ *    not call updateConnections here).  The observation index is marked stale.
+ * new_points_result: synchronises; the record of the last call.  n_neighbors = the entries of current's row the call
+ * saw (at most 10); per entry the key-frame, a status (entries beyond max_neighbors: NOT_REACHED), the search's match_cnt
+ * and the number of points created (arrays [10], any may be NULL); created [sum][4] = (key-frame of the neighbour, idx1,
+ * idx2, id) per new point in creation order, at most created_capacity rows (the record holds 10 * max_features).  Returns
+ * VO_ERR_CAPACITY, with everything else filled in, when the call created more rows than created_capacity.
+ * get_points: synchronises; the map side of a key-frame as the store holds it, arrays [n] (n as inserted), any may be
+ * NULL: flags, ids, points [n][3], point_desc [n][32], min / max distance, normals [n][3].  Valid on every store. */
+#define VO_KFSTORE_NP_SEARCHED 0
+#define VO_KFSTORE_NP_SKIPPED_BAD 1
+#define VO_KFSTORE_NP_SKIPPED_BASELINE 2
+#define VO_KFSTORE_NP_SKIPPED_NO_POSE 3
+#define VO_KFSTORE_NP_NOT_REACHED 4
+int vo_kfstore_enable_mapping(vo_kfstore *s, const float cam[6], int n_levels, const float *scale_factors, int32_t first_point_id);
+int vo_kfstore_set_pose(vo_kfstore *s, int keyframe, const double *Tcw12);
+int vo_kfstore_set_pose_dev(vo_kfstore *s, int keyframe, const double *dev_Tcw12);
+int vo_kfstore_set_keypoint_xy(vo_kfstore *s, int keyframe, const float *xy /*[n][2]*/);
+int vo_kfstore_set_keypoint_xy_dev(vo_kfstore *s, int keyframe, const float *dev_xy /*[n][2]*/);
+int vo_kfstore_next_point_id(vo_kfstore *s, int32_t *id);
+int vo_kfstore_create_map_points(vo_kfstore *s, int current, int max_neighbors);
+int vo_kfstore_new_points_result(vo_kfstore *s, int32_t *n_neighbors, int32_t *neighbor_kf /*[10]*/, int32_t *status /*[10]*/,
+                                 int32_t *n_matches /*[10]*/, int32_t *n_created /*[10]*/, int32_t *created /*[sum][4]*/,
+                                 int created_capacity);
+int vo_kfstore_get_points(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *ids, double *points, uint8_t *point_desc,
+                          float *min_distance, float *max_distance, double *normals);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

@@ -59,6 +59,8 @@ SYMBOLS = [
     "vo_kfstore_connections_status", "vo_kfstore_get_connections",
     "vo_kfstore_enable_culling", "vo_kfstore_set_keypoints", "vo_kfstore_set_keypoints_dev", "vo_kfstore_set_erase_lock",
     "vo_kfstore_cull_keyframes", "vo_kfstore_erase_keyframe", "vo_kfstore_cull_result", "vo_kfstore_cull_state", "vo_kfstore_get_flags",
+    "vo_kfstore_enable_mapping", "vo_kfstore_set_pose", "vo_kfstore_set_pose_dev", "vo_kfstore_set_keypoint_xy", "vo_kfstore_set_keypoint_xy_dev",
+    "vo_kfstore_next_point_id", "vo_kfstore_create_map_points", "vo_kfstore_new_points_result", "vo_kfstore_get_points",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -143,6 +145,13 @@ def _p(a):
     if hasattr(a, "data_ptr"):
         return C.c_void_p(a.data_ptr())
     raise TypeError(type(a))
+
+
+def _need_tensor(t, dtype, numel, what):
+    """a device tensor handed through as a raw pointer: its element type, contiguity and (where fixed) its length"""
+    if str(t.dtype) != "torch." + dtype or not t.is_contiguous() or (numel is not None and t.numel() != numel):
+        raise VoError(f"{what}: a contiguous {dtype} tensor{'' if numel is None else f' of {numel} elements'} is required, "
+                      f"got {t.dtype} with shape {tuple(t.shape)}")
 
 
 class OrbExtractor:
@@ -1706,6 +1715,67 @@ class KeyFrameStore:
         bad = C.c_int32(0)
         check(lib().vo_kfstore_get_flags(self._h, int(keyframe), _p(f), C.byref(bad)), "vo_kfstore_get_flags")
         return [int(x) for x in (f if n is None else f[:n])], int(bad.value)
+
+    NP_SEARCHED, NP_SKIPPED_BAD, NP_SKIPPED_BASELINE, NP_SKIPPED_NO_POSE, NP_NOT_REACHED = 0, 1, 2, 3, 4
+
+    def enable_mapping(self, cam6, scale_factors, first_point_id=0):
+        """createNewMapPoints on the device from now on; valid on an empty store after enable_culling
+        only.  cam6 = fx, fy, cx, cy, bf, b; scale_factors = scaleFactors_ (at most 16 levels)"""
+        cam, sf = np.ascontiguousarray(cam6, np.float32).reshape(6), np.ascontiguousarray(scale_factors, np.float32).reshape(-1)
+        check(lib().vo_kfstore_enable_mapping(self._h, _p(cam), len(sf), _p(sf), int(first_point_id)), "vo_kfstore_enable_mapping")
+
+    def set_pose(self, keyframe, Tcw12):
+        """Tcw as 12 doubles, R row-major then t.  A numpy array is copied and synchronises once; a device tensor (float64) is
+        enqueued only"""
+        if hasattr(Tcw12, "data_ptr"):
+            _need_tensor(Tcw12, "float64", 12, "set_pose")
+            check(lib().vo_kfstore_set_pose_dev(self._h, int(keyframe), _p(Tcw12)), "vo_kfstore_set_pose_dev")
+            return
+        T = np.ascontiguousarray(Tcw12, np.float64).reshape(12)
+        check(lib().vo_kfstore_set_pose(self._h, int(keyframe), _p(T)), "vo_kfstore_set_pose")
+
+    def set_keypoint_xy(self, keyframe, xy):
+        """unKeypoints_[i].pt per feature [n, 2] (float32, n as inserted); numpy: copied, synchronises once; a device tensor:
+        enqueued only"""
+        if hasattr(xy, "data_ptr"):
+            _need_tensor(xy, "float32", None, "set_keypoint_xy")
+            check(lib().vo_kfstore_set_keypoint_xy_dev(self._h, int(keyframe), _p(xy)), "vo_kfstore_set_keypoint_xy_dev")
+            return
+        a = np.ascontiguousarray(xy, np.float32)
+        check(lib().vo_kfstore_set_keypoint_xy(self._h, int(keyframe), _p(a)), "vo_kfstore_set_keypoint_xy")
+
+    def next_point_id(self):
+        """the id the next created map point gets (MapPoint::factory_id_); synchronises"""
+        v = C.c_int32(0)
+        check(lib().vo_kfstore_next_point_id(self._h, C.byref(v)), "vo_kfstore_next_point_id")
+        return int(v.value)
+
+    def create_map_points(self, current, max_neighbors=10):
+        """LocalMapping::createNewMapPoints for the current key-frame against the first max_neighbors of its neighbours;
+        enqueued only"""
+        check(lib().vo_kfstore_create_map_points(self._h, int(current), int(max_neighbors)), "vo_kfstore_create_map_points")
+
+    def new_points_result(self):
+        """the last create_map_points call -> dict(neighbors [(key-frame, status, n_matches, n_created)] per entry of the
+        current key-frame's list the call saw, created [(neighbour key-frame, idx1, idx2, id)] in creation order)"""
+        kf, st, nm, nc = (np.zeros(self.MAX_NEIGHBORS, np.int32) for _ in range(4))
+        created = np.zeros((self.MAX_NEIGHBORS * self.max_features, 4), np.int32)
+        n = C.c_int32(0)
+        check(lib().vo_kfstore_new_points_result(self._h, C.byref(n), _p(kf), _p(st), _p(nm), _p(nc), _p(created), len(created)),
+              "vo_kfstore_new_points_result")
+        total = int(nc[:n.value].sum())
+        return dict(neighbors=[(int(kf[i]), int(st[i]), int(nm[i]), int(nc[i])) for i in range(n.value)],
+                    created=[tuple(int(x) for x in row) for row in created[:total]])
+
+    def points(self, keyframe, n):
+        """the map side of a key-frame as the store holds it (n as inserted) -> dict(flags, ids, points, point_desc, min_dist,
+        max_dist, normals) of numpy arrays"""
+        n = int(n)
+        out = dict(flags=np.zeros(n, np.uint8), ids=np.zeros(n, np.int32), points=np.zeros((n, 3)), point_desc=np.zeros((n, 32), np.uint8),
+                   min_dist=np.zeros(n, np.float32), max_dist=np.zeros(n, np.float32), normals=np.zeros((n, 3)))
+        check(lib().vo_kfstore_get_points(self._h, int(keyframe), *(_p(out[k]) for k in ("flags", "ids", "points", "point_desc", "min_dist",
+                                                                                         "max_dist", "normals"))), "vo_kfstore_get_points")
+        return out
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -39,6 +39,7 @@ SOURCES = [
     ("kfstore.hip", ["-ffp-contract=off"]),
     ("connections.hip", ["-ffp-contract=off"]),
     ("cull.hip", ["-ffp-contract=off"]),
+    ("new_points.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -99,6 +99,10 @@ struct vo_kfstore {
   vo::OwnedDevBuf cull;               // vo_kfstore_enable_culling: the columns and words of section 4i
   vo::KfCullView X{};
   bool culling = false;
+  vo::OwnedDevBuf map;                // vo_kfstore_enable_mapping: the arrays of section 4j
+  vo::KfMapView M{};
+  size_t map_bytes = 0;
+  bool mapping = false;
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -196,6 +200,12 @@ int need_connections(const vo_kfstore *s, const char *call) {
 int need_culling(const vo_kfstore *s, const char *call) {
   if (s && s->culling) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_culling has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_mapping(const vo_kfstore *s, const char *call) {
+  if (s && s->mapping) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_mapping has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -617,6 +627,153 @@ int vo_kfstore_get_flags(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *b
   VO_CHECK(vo::stream_sync(s->st, W));
   if (bad) *bad = head[1];
   return VO_OK;
+}
+
+int vo_kfstore_enable_mapping(vo_kfstore *s, const float cam[6], int n_levels, const float *scale_factors, int32_t first_point_id) {
+  const char *W = "vo_kfstore_enable_mapping";
+  VO_CHECK(need_culling(s, W));
+  if (!cam || !scale_factors || n_levels < 1 || n_levels > 16 || first_point_id < 0) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->mapping) return VO_OK;
+  if (s->NK > 16384) {
+    vo::set_error("%s: %d features per key-frame, the search kernel handles 16384", W, s->NK);
+    return VO_ERR_CAPACITY;
+  }
+  s->map_bytes = vo::mapping_bytes(s->max_kf, s->NK);
+  VO_CHECK(s->map.reserve(s->map_bytes));
+  s->M = vo::mapping_layout(s->map.p, s->max_kf, s->NK);
+  s->M.n_levels = n_levels;
+  for (int i = 0; i < 6; i++) s->M.cam[i] = cam[i];
+  for (int i = 0; i < 16; i++) s->M.sf[i] = scale_factors[i < n_levels ? i : n_levels - 1];
+  VO_CHECK(vo::mapping_init(s->M, s->map_bytes, first_point_id, s->st));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  s->mapping = true;
+  return VO_OK;
+}
+
+int vo_kfstore_set_pose(vo_kfstore *s, int keyframe, const double *Tcw12) {
+  const char *W = "vo_kfstore_set_pose";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  if (!Tcw12) return VO_ERR_INVALID;
+  // the pose-set word lies behind the pose (the thirteenth slot): one copy
+  double *h = reinterpret_cast<double *>(s->stage.data());
+  memcpy(h, Tcw12, 96);
+  const int32_t one[2] = {1, 0};
+  memcpy(h + 12, one, 8);
+  VO_CHECK(vo::copy_h2d(vo::np_pose(s->M, keyframe), h, vo::kNpPoseDoubles * 8, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_pose_dev(vo_kfstore *s, int keyframe, const double *dev_Tcw12) {
+  const char *W = "vo_kfstore_set_pose_dev";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  if (!dev_Tcw12) return VO_ERR_INVALID;
+  return vo::mapping_set_pose_dev(s->M, keyframe, dev_Tcw12, s->st);
+}
+
+int vo_kfstore_set_keypoint_xy(vo_kfstore *s, int keyframe, const float *xy) {
+  const char *W = "vo_kfstore_set_keypoint_xy";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
+  if (n == 0) return VO_OK;
+  if (!xy) return VO_ERR_INVALID;
+  // the two columns of a key-frame lie side by side: staged whole (zero beyond n), one copy
+  float *hx = reinterpret_cast<float *>(s->stage.data()), *hy = hx + NK;  // (a record is longer than 8 bytes a feature)
+  for (size_t i = 0; i < NK; i++) hx[i] = i < n ? xy[2 * i] : 0.f, hy[i] = i < n ? xy[2 * i + 1] : 0.f;
+  VO_CHECK(vo::copy_h2d(vo::np_x(s->M, keyframe), hx, NK * 8, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_keypoint_xy_dev(vo_kfstore *s, int keyframe, const float *dev_xy) {
+  const char *W = "vo_kfstore_set_keypoint_xy_dev";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const int n = s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_xy) return VO_ERR_INVALID;
+  return vo::mapping_split_xy(s->M, keyframe, n, dev_xy, s->st);
+}
+
+int vo_kfstore_next_point_id(vo_kfstore *s, int32_t *id) {
+  const char *W = "vo_kfstore_next_point_id";
+  VO_CHECK(need_mapping(s, W));
+  if (!id) return VO_ERR_INVALID;
+  VO_CHECK(vo::copy_d2h(id, s->M.counter, 4, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_create_map_points(vo_kfstore *s, int current, int max_neighbors) {
+  const char *W = "vo_kfstore_create_map_points";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  if (max_neighbors < 1 || max_neighbors > vo::kKfGraphNb) {
+    vo::set_error("%s: max_neighbors %d outside [1, %d]", W, max_neighbors, vo::kKfGraphNb);
+    return VO_ERR_INVALID;
+  }
+  // (that `current` has been erased or has no pose only the device knows: k_tri_walk then reaches no neighbour and raises
+  //  the sticky VO_KFSTORE_CONNECTIONS_INVALID)
+  const vo::KfStoreView V = vo::kfstore_view(s);
+  const vo::KfConnView C = vo::connections_view(s->conn);
+  for (int i = 0; i < max_neighbors; i++) {  // step i + 1 reads the flags step i wrote: walk, replay, create per neighbour
+    VO_CHECK(vo::tri_walk_replay(V, s->X, s->M, s->graph.as<int>(), C.status, current, i, s->st));
+    VO_CHECK(vo::np_create(V, s->X, s->M, s->normals.as<double>(), current, i, s->st));
+  }
+  s->obs_dirty = true;  // (whether anything was created only the device knows)
+  return VO_OK;
+}
+
+int vo_kfstore_new_points_result(vo_kfstore *s, int32_t *n_neighbors, int32_t *neighbor_kf, int32_t *status, int32_t *n_matches,
+                                 int32_t *n_created, int32_t *created, int created_capacity) {
+  const char *W = "vo_kfstore_new_points_result";
+  VO_CHECK(need_mapping(s, W));
+  if (!n_neighbors || created_capacity < 0 || (created_capacity > 0 && !created)) return VO_ERR_INVALID;
+  int32_t rec[vo::kNpRecInts] = {0};
+  VO_CHECK(vo::copy_d2h(rec, s->M.rec, sizeof(rec), s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  const int n = std::min(std::max(rec[0], 0), vo::kKfGraphNb);
+  const int total = std::min(std::max(rec[1], 0), vo::kKfGraphNb * s->NK);
+  *n_neighbors = n;
+  for (int i = 0; i < vo::kKfGraphNb; i++) {
+    if (neighbor_kf) neighbor_kf[i] = i < n ? rec[4 + 4 * i] : -1;
+    if (status) status[i] = i < n ? rec[4 + 4 * i + 1] : VO_KFSTORE_NP_NOT_REACHED;
+    if (n_matches) n_matches[i] = i < n ? rec[4 + 4 * i + 2] : 0;
+    if (n_created) n_created[i] = i < n ? rec[4 + 4 * i + 3] : 0;
+  }
+  const int rows = std::min(total, created_capacity);
+  if (rows > 0) {
+    VO_CHECK(vo::copy_d2h(created, s->M.created, (size_t)rows * 16, s->st, W));
+    VO_CHECK(vo::stream_sync(s->st, W));
+  }
+  if (total > created_capacity) {
+    vo::set_error("%s: the call created %d points, created_capacity is %d", W, total, created_capacity);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+int vo_kfstore_get_points(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *ids, double *points, uint8_t *point_desc,
+                          float *min_distance, float *max_distance, double *normals) {
+  const char *W = "vo_kfstore_get_points";
+  if (!s) return VO_ERR_INVALID;
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  const vo::KfStoreView &V = s->V;
+  const uint8_t *r = s->record(keyframe);
+  if (flags) VO_CHECK(vo::copy_d2h(flags, r + V.o_flags, n, s->st, W));
+  if (ids) VO_CHECK(vo::copy_d2h(ids, r + V.o_ids, n * 4, s->st, W));
+  if (points) VO_CHECK(vo::copy_d2h(points, r + V.o_points, n * 24, s->st, W));
+  if (point_desc) VO_CHECK(vo::copy_d2h(point_desc, r + V.o_pdesc, n * 32, s->st, W));
+  if (min_distance) VO_CHECK(vo::copy_d2h(min_distance, r + V.o_mind, n * 4, s->st, W));
+  if (max_distance) VO_CHECK(vo::copy_d2h(max_distance, r + V.o_maxd, n * 4, s->st, W));
+  if (normals) VO_CHECK(vo::copy_d2h(normals, s->normals.as<double>() + (size_t)keyframe * s->NK * 3, n * 24, s->st, W));
+  return vo::stream_sync(s->st, W);
 }
 
 int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {

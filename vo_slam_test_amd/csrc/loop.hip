@@ -7,42 +7,13 @@
 // Compiled with -ffp-contract=off (float gates that must round like the x86-64 reference build).
 #include "vo_common.h"
 
+#include "triangulate.h"
+
 #include <vector>
 
 namespace {
 
-// symmetric 4 x 4 eigen-decomposition, cyclic Jacobi (Eigen::EigenSolver of a symmetric matrix / cv::SVD of a 4 x 4:
-// same vectors up to sign and rounding)
-__device__ void sym4_eigen(double A[4][4], double V[4][4], double w[4]) {
-  for (int i = 0; i < 4; i++)
-    for (int j = 0; j < 4; j++) V[i][j] = i == j;
-  for (int sweep = 0; sweep < 60; sweep++) {
-    double off = 0;
-    for (int p = 0; p < 4; p++)
-      for (int q = p + 1; q < 4; q++) off += A[p][q] * A[p][q];
-    if (off < 1e-300) break;
-    for (int p = 0; p < 4; p++)
-      for (int q = p + 1; q < 4; q++) {
-        if (fabs(A[p][q]) < 1e-300) continue;
-        const double theta = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 4; k++) {
-          const double akp = A[k][p], akq = A[k][q];
-          A[k][p] = c * akp - s * akq, A[k][q] = s * akp + c * akq;
-        }
-        for (int k = 0; k < 4; k++) {
-          const double apk = A[p][k], aqk = A[q][k];
-          A[p][k] = c * apk - s * aqk, A[q][k] = s * apk + c * aqk;
-        }
-        for (int k = 0; k < 4; k++) {
-          const double vkp = V[k][p], vkq = V[k][q];
-          V[k][p] = c * vkp - s * vkq, V[k][q] = s * vkp + c * vkq;
-        }
-      }
-  }
-  for (int i = 0; i < 4; i++) w[i] = A[i][i];
-}
+using vo::sym4_eigen;  // (triangulate.h: shared with new_points.hip)
 
 // Sim3Solver::computeSim3 (:179-252)
 __device__ void sim3_horn(const double P1[9], const double P2[9], int fix_scale, double R[9], double t[3], double &s) {
@@ -147,28 +118,9 @@ __global__ __launch_bounds__(256) void k_triangulate(int n, const float *xn1, co
                                                      long long t2_stride, float *out, uint8_t *ok) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const float *t2 = T2 + (long long)i * t2_stride;
-  float A[4][4];
-  for (int c = 0; c < 4; c++) {
-    A[0][c] = xn1[2 * i] * T1[8 + c] - T1[c];
-    A[1][c] = xn1[2 * i + 1] * T1[8 + c] - T1[4 + c];
-    A[2][c] = xn2[2 * i] * t2[8 + c] - t2[c];
-    A[3][c] = xn2[2 * i + 1] * t2[8 + c] - t2[4 + c];
-  }
-  double G[4][4], V[4][4], w[4];
-  for (int a = 0; a < 4; a++)
-    for (int b = 0; b < 4; b++) {
-      G[a][b] = 0;
-      for (int r = 0; r < 4; r++) G[a][b] += (double)A[r][a] * (double)A[r][b];
-    }
-  sym4_eigen(G, V, w);
-  int best = 0;
-  for (int q = 1; q < 4; q++)
-    if (w[q] < w[best]) best = q;
-  const float x3 = (float)V[3][best];
-  const bool good = !(fabsf(x3) < 1e-8f);  // :245-246
-  ok[i] = good;
-  for (int a = 0; a < 3; a++) out[3 * i + a] = good ? (float)V[a][best] / x3 : 0.f;
+  float p[3];
+  ok[i] = vo::triangulate_pair(xn1[2 * i], xn1[2 * i + 1], xn2[2 * i], xn2[2 * i + 1], T1, T2 + (long long)i * t2_stride, p);
+  for (int a = 0; a < 3; a++) out[3 * i + a] = p[a];
 }
 
 // Map::score (map.cpp:335-376): L1 score of the query BoW vector against candidate c's (both ascending word ids)

@@ -5,6 +5,7 @@
 // so that match pairs stay identical to the reference's visiting order.
 #include "vo_common.h"
 #include "block_sort.h"
+#include "new_points_geom.h"
 
 #include <algorithm>
 #include <cmath>
@@ -1233,6 +1234,127 @@ __global__ __launch_bounds__(64) void k_bow_walk(BowWalkArgs A) {
   }
 }
 
+// The store-to-store form of k_bow_walk for one neighbour step of vo_kfstore_create_map_points:
+// A = `current`, B = entry `step` of current's graph row, both key-frames of the store.  One wavefront.  Every lane
+// derives the step's neighbour and status (uniform); lane 0 writes the record's entry (on step 0 the whole record), the
+// geometry block and the argument block.  The walk is searchForTriangulation's (matcher.cpp:893-978): A's CSR entries in
+// order, a feature of A is a query when its node is shared and it has no map point (flags bit 0 clear, :903); a feature of
+// B may be claimed when it has none (:920) -- bok.  A step that is not searched leaves nq = nA = 0: k_node_replay then
+// writes nothing but a match count of 0.
+struct TriWalkArgs {
+  vo::KfStoreView S;
+  vo::KfCullView X;
+  vo::KfMapView M;
+  const int *graph;
+  int *status;  // the store's sticky word
+  int current, step;
+};
+__global__ __launch_bounds__(64) void k_tri_walk(TriWalkArgs A) {
+  const int lane = threadIdx.x, cur = A.current, NK = A.S.NK;
+  const vo::KfMapView &M = A.M;
+  const int *row = A.graph + (size_t)cur * vo::kKfGraphInts;
+  const bool cur_ok = !A.X.erased[cur] && *vo::np_pose_set(M, cur) != 0;
+  const int n_list = cur_ok ? min(max(row[0], 0), vo::kKfGraphNb) : 0;
+  int sticky = A.step == 0 && !cur_ok ? VO_KFSTORE_CONNECTIONS_INVALID : 0;
+  int st = VO_KFSTORE_NP_NOT_REACHED, kf = -1;
+  vo::NpStep &G = *M.step;
+  if (A.step < n_list) {
+    kf = row[4 + A.step];
+    if (kf < 0 || kf >= A.S.size || kf == cur) {
+      st = VO_KFSTORE_NP_SKIPPED_NO_POSE, sticky = VO_KFSTORE_CONNECTIONS_INVALID, kf = -1;
+    } else if (vo::kf_head(A.S, kf)[1]) {
+      st = VO_KFSTORE_NP_SKIPPED_BAD;  // :167
+    } else if (!*vo::np_pose_set(M, kf)) {
+      st = VO_KFSTORE_NP_SKIPPED_NO_POSE, sticky = VO_KFSTORE_CONNECTIONS_INVALID;
+    } else {
+      st = VO_KFSTORE_NP_SEARCHED;
+    }
+  }
+  vo::NpStep L{};  // (every lane computes the same geometry: uniform values, no exchange; lane 0 stores it)
+  if (st == VO_KFSTORE_NP_SEARCHED) {
+    const double *T1 = vo::np_pose(M, cur), *T2 = vo::np_pose(M, kf);
+    for (int i = 0; i < 12; i++) L.T1[i] = T1[i], L.T2[i] = T2[i];
+    vo::np_geometry(L.T1, L.T2, M.cam, L);
+    if (L.bl < M.cam[5]) st = VO_KFSTORE_NP_SKIPPED_BASELINE;  // :172-174
+  }
+  L.kf = kf, L.status = st;
+  if (lane == 0) {
+    G = L;
+    if (A.step == 0) {
+      M.rec[0] = n_list, M.rec[1] = M.rec[2] = M.rec[3] = 0;
+      for (int i = 0; i < vo::kKfGraphNb; i++) {
+        const int k = i < n_list ? row[4 + i] : -1;
+        M.rec[4 + 4 * i] = k, M.rec[4 + 4 * i + 1] = VO_KFSTORE_NP_NOT_REACHED, M.rec[4 + 4 * i + 2] = M.rec[4 + 4 * i + 3] = 0;
+      }
+    }
+    if (A.step < n_list) M.rec[4 + 4 * A.step + 1] = st;
+    if (sticky) atomicOr(A.status, sticky);
+  }
+  const bool go = st == VO_KFSTORE_NP_SEARCHED;
+  int nq = 0, nA = 0, nB = 0;
+  if (go) {
+    const int *headA = vo::kf_head(A.S, cur), *headB = vo::kf_head(A.S, kf);
+    nA = min(max(headA[0], 0), NK), nB = min(max(headB[0], 0), NK);
+    const int nnA = min(max(headA[2], 0), NK), nnB = min(max(headB[2], 0), NK);
+    const uint8_t *flagsA = vo::kf_sec<uint8_t>(A.S, cur, A.S.o_flags), *flagsB = vo::kf_sec<uint8_t>(A.S, kf, A.S.o_flags);
+    for (int i = lane; i < nB; i += 64) M.bok[i] = (flagsB[i] & 1) ? 0 : 1;
+    if (nA > 0 && nB > 0 && nnA > 0 && nnB > 0) {
+      const int *nodeA = vo::kf_sec<int>(A.S, cur, A.S.o_node), *startA = vo::kf_sec<int>(A.S, cur, A.S.o_start);
+      const int *featA = vo::kf_sec<int>(A.S, cur, A.S.o_feat);
+      const int *nodeB = vo::kf_sec<int>(A.S, kf, A.S.o_node), *startB = vo::kf_sec<int>(A.S, kf, A.S.o_start);
+      const int total = min(max(startA[nnA], 0), NK);
+      for (int b = 0; b < total; b += 64) {
+        const int t = b + lane;
+        bool emit = false;
+        int4 q = make_int4(0, 0, 0, 0);
+        if (t < total) {
+          int lo = 0, hi = nnA;  // first node whose start is beyond t; the entry belongs to the node before it
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (startA[mid] <= t) lo = mid + 1;
+            else hi = mid;
+          }
+          const int nd = nodeA[max(lo - 1, 0)];
+          int l2 = 0, h2 = nnB;  // first node of B >= nd
+          while (l2 < h2) {
+            const int mid = (l2 + h2) >> 1;
+            if (nodeB[mid] < nd) l2 = mid + 1;
+            else h2 = mid;
+          }
+          if (l2 < nnB && nodeB[l2] == nd) {
+            const int i1 = featA[t];
+            const int s0 = min(max(startB[l2], 0), NK), s1 = min(max(startB[l2 + 1], s0), NK);
+            if (i1 >= 0 && i1 < nA && !(flagsA[i1] & 1)) {  // `if (mpk) continue;` :903-904
+              emit = true;
+              q = make_int4(i1, s0, s1, 0);
+            }
+          }
+        }
+        const unsigned long long mk = __builtin_amdgcn_ballot_w64(emit);
+        const int within = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+        if (emit) M.queries[nq + within] = q;
+        nq += (int)__popcll(mk);
+      }
+    }
+  }
+  if (lane == 0) {
+    NodeArgs &P = *reinterpret_cast<NodeArgs *>(M.args);
+    P.mode = kNodeTri, P.nq = nq, P.nA = nA, P.nB = nB, P.check_rot = 1;
+    P.ratio = 0.f, P.ex = go ? L.ex : 0.f, P.ey = go ? L.ey : 0.f;
+    for (int i = 0; i < 9; i++) P.F[i] = go ? L.F[i] : 0.0;
+    for (int i = 0; i < 16; i++) P.sf[i] = M.sf[i];
+    const int a = cur, b = go ? kf : cur;
+    P.queries = M.queries, P.bfeat = vo::kf_sec<uint32_t>(A.S, b, A.S.o_feat);
+    P.descA = vo::kf_sec<uint4>(A.S, a, A.S.o_desc), P.descB = vo::kf_sec<uint4>(A.S, b, A.S.o_desc);
+    P.angA = vo::kf_sec<float>(A.S, a, A.S.o_angle), P.angB = vo::kf_sec<float>(A.S, b, A.S.o_angle);
+    P.xA = vo::np_x(M, a), P.yA = vo::np_y(M, a), P.urA = vo::cull_uright(A.X, a);
+    P.xB = vo::np_x(M, b), P.yB = vo::np_y(M, b), P.urB = vo::cull_uright(A.X, b);
+    P.octB = vo::cull_octave(A.X, b);
+    P.b_ok = M.bok;
+    P.claims = M.claims, P.match = M.match, P.n_matches = M.nm;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_fill_u8(uint8_t *p, int n, uint8_t v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = v;
@@ -1318,6 +1440,21 @@ int vo::bow_walk_replay(vo_frames *frames, int B, int per, const vo::KfStoreView
   const size_t lds = (((size_t)b.cap + 15) & ~(size_t)15) * 5;
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
   hipLaunchKernelGGL(k_node_replay, dim3((unsigned)NP), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(b.args));
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+size_t vo::tri_args_bytes() { return sizeof(NodeArgs); }
+
+int vo::tri_walk_replay(const vo::KfStoreView &S, const vo::KfCullView &X, const vo::KfMapView &M, const int *graph, int *status,
+                        int current, int step, hipStream_t st) {
+  if (S.NK > kNodeMaxB || step < 0 || step >= vo::kKfGraphNb || !graph || !status) return VO_ERR_INVALID;
+  TriWalkArgs A{S, X, M, graph, status, current, step};
+  hipLaunchKernelGGL(k_tri_walk, dim3(1), dim3(64), 0, st, A);
+  VO_HIP_CHECK(hipGetLastError());
+  const size_t lds = (((size_t)S.NK + 15) & ~(size_t)15) * 5;  // taken[] / tmpb[] for the store's capacity
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
+  hipLaunchKernelGGL(k_node_replay, dim3(1), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(M.args));
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }

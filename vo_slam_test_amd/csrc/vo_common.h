@@ -362,6 +362,51 @@ int cull_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, 
                  hipStream_t st);
 int erase_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, int keyframe, hipStream_t st);
 
+// New map points on the device (new_points.hip, match.hip): LocalMapping::createNewMapPoints.  What
+// vo_kfstore_enable_mapping allocates, one block: pose [max_kf][13] doubles (R row-major, t, and in the thirteenth slot the
+// pose-set word, so that the host form of set_pose is one copy); xy [max_kf][2][NK] (unKeypoints_[i].pt: a key-frame's x
+// column, then its y column -- split so that k_node_replay reads them as it reads a frame view's, side by side so that the
+// host form of set_keypoint_xy is one copy); the id counter;
+// rec, the result record: [n_neighbors, created in all, 0, 0 | (key-frame, status, n_matches, n_created) x 10]; created
+// [10][NK] rows (key-frame, idx1, idx2, id); and the scratch of ONE neighbour step: query list, claims, the argument block
+// of k_node_replay (match.hip's NodeArgs: tri_args_bytes), the neighbour's claimable bytes, match12, the match count and
+// the step's geometry.
+constexpr int kNpRecInts = 4 + 4 * VO_KFSTORE_MAX_NEIGHBORS;
+struct NpStep {
+  double T1[12], T2[12], Ow1[3], Ow2[3], F[9];
+  float ex, ey, bl;
+  int kf, status;
+};
+struct KfMapView {
+  int NK, n_levels;
+  float cam[6], sf[16];  // fx, fy, cx, cy, bf, b; scaleFactors_ (entries beyond n_levels repeat the last)
+  double *pose;
+  float *xy;
+  int *counter, *rec;
+  int4 *created, *queries, *claims;
+  uint8_t *args, *bok;
+  int *match, *nm;
+  NpStep *step;
+};
+constexpr int kNpPoseDoubles = 13;
+__host__ __device__ __forceinline__ double *np_pose(const KfMapView &M, int k) { return M.pose + (size_t)k * kNpPoseDoubles; }
+__host__ __device__ __forceinline__ int *np_pose_set(const KfMapView &M, int k) { return reinterpret_cast<int *>(np_pose(M, k) + 12); }
+__host__ __device__ __forceinline__ float *np_x(const KfMapView &M, int k) { return M.xy + (size_t)k * 2 * M.NK; }
+__host__ __device__ __forceinline__ float *np_y(const KfMapView &M, int k) { return M.xy + ((size_t)k * 2 + 1) * M.NK; }
+size_t mapping_bytes(int max_kf, int NK);
+KfMapView mapping_layout(void *block, int max_kf, int NK);
+int mapping_init(const KfMapView &M, size_t bytes, int first_point_id, hipStream_t st);
+int mapping_set_pose_dev(const KfMapView &M, int k, const double *dev_Tcw12, hipStream_t st);
+int mapping_split_xy(const KfMapView &M, int k, int n, const float *dev_xy, hipStream_t st);
+// one neighbour step = three launches.  tri_walk_replay (match.hip): k_tri_walk -- the step's neighbour from `current`'s
+// graph row, its status and geometry (new_points_geom.h), the record's entry (the whole record on step 0), the store-to-
+// store common-node walk and the argument block -- then k_node_replay in triangulation mode; `status`: the store's sticky
+// word.  np_create (new_points.hip): k_np_create.
+size_t tri_args_bytes();
+int tri_walk_replay(const KfStoreView &S, const KfCullView &X, const KfMapView &M, const int *graph, int *status, int current, int step,
+                    hipStream_t st);
+int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int current, int step, hipStream_t st);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
