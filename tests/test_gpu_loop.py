@@ -6,6 +6,7 @@ import struct
 import numpy as np
 import pytest
 
+from loop_inputs import horn_numpy as _horn_numpy   # Horn's closed form with LAPACK's eigh
 from vo_slam_test_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -79,30 +80,47 @@ def test_triangulation(vo, orc):
     dpts, dok = vo.triangulate(np.zeros((1, 2), np.float32), np.zeros((1, 2), np.float32), np.eye(3, 4, dtype=np.float32),
                                np.eye(3, 4, dtype=np.float32))
     assert dok.shape == (1,)
+    want = np.zeros(3, np.float32)   # the oracle returns 0 and leaves its output alone; the device documents out = 0 (triangulate.h)
+    flag = orc.lib().orc_triangulate(np.zeros(2, np.float32), np.zeros(2, np.float32), np.eye(3, 4, dtype=np.float32).reshape(-1),
+                                     np.eye(3, 4, dtype=np.float32).reshape(-1), want)
+    assert flag == 0 and dok[0] == 0 and np.array_equal(dpts[0], want)
+    # the same pair in the middle of a batch that crosses a block: flagged there, and its neighbours are untouched by it
+    E = np.eye(3, 4, dtype=np.float32)
+    m = 257
+    xa = (P[:m, :2] / P[:m, 2:]).astype(np.float32)
+    xb = np.array([(T2s[i, :, :3] @ P[i] + T2s[i, :, 3])[:2] / (T2s[i, :, :3] @ P[i] + T2s[i, :, 3])[2] for i in range(m)], np.float32)
+    T2b = T2s[:m].copy()
+    xa[128], xb[128], T2b[128] = 0, 0, E
+    bpts, bok = vo.triangulate(xa, xb, E, T2b)
+    for i in range(m):
+        o = np.zeros(3, np.float32)
+        assert orc.lib().orc_triangulate(xa[i], xb[i], E.reshape(-1), T2b[i].reshape(-1), o) == bok[i] == (i != 128)
+        assert np.abs(o - bpts[i]).max() <= 1e-4 * max(1.0, np.abs(o).max())
+    assert np.array_equal(bpts[128], want)
 
 
-def _horn_numpy(P1, P2, fix_scale):
-    """Horn's closed form as Sim3Solver::computeSim3 writes it (sim3Solver.cpp:179-240), with numpy's LAPACK eigh instead
-    of the Jacobi sweeps the device and the oracle share: P1 = s R P2 + t for the three sampled correspondences"""
-    O1, O2 = P1.mean(0), P2.mean(0)
-    Pr1, Pr2 = (P1 - O1).T, (P2 - O2).T
-    M = Pr2 @ Pr1.T
-    N = np.array([[M[0, 0] + M[1, 1] + M[2, 2], M[1, 2] - M[2, 1], M[2, 0] - M[0, 2], M[0, 1] - M[1, 0]],
-                  [0, M[0, 0] - M[1, 1] - M[2, 2], M[0, 1] + M[1, 0], M[2, 0] + M[0, 2]],
-                  [0, 0, -M[0, 0] + M[1, 1] - M[2, 2], M[1, 2] + M[2, 1]],
-                  [0, 0, 0, -M[0, 0] - M[1, 1] + M[2, 2]]])
-    N = N + np.triu(N, 1).T
-    w, V = np.linalg.eigh(N)
-    q = V[:, -1]                                   # (w, x, y, z) of the largest eigenvalue
-    vec, nv = q[1:], np.linalg.norm(q[1:])
-    rv = 2.0 * np.arctan2(nv, q[0]) * vec / nv     # the reference goes through the angle-axis vector and cv::Rodrigues
-    th = np.linalg.norm(rv)
-    k = rv / th
-    K = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
-    R = np.eye(3) + np.sin(th) * K + (1 - np.cos(th)) * (K @ K)
-    P3 = R @ Pr2
-    s = 1.0 if fix_scale else float((Pr1 * P3).sum() / (P3 * P3).sum())
-    return R, O1 - s * R @ O2, s
+@pytest.mark.parametrize("n", [1, 255, 257])
+@pytest.mark.parametrize("angle", [2.2, 3.0])
+def test_triangulation_with_the_second_camera_turned_far(vo, orc, n, angle):
+    """the second camera turned 2.2 and 3.0 rad about y and placed beyond the points (every point in front of both); one
+    pair, one short of a block, one into the second block: against the oracle and numpy's SVD at the file's 1e-4 rule"""
+    import loop_inputs as li
+    P, T1, T2, xn1, xn2, (z1, z2) = li.triangulation_inputs(n, n, angle)
+    assert z1.min() > 0.5 and z2.min() > 0.5
+    pts, ok = vo.triangulate(xn1, xn2, T1, T2)
+    assert ok.shape == (n,) and ok.all()
+    worst = 0.0
+    for i in range(n):
+        o = np.zeros(3, np.float32)
+        assert orc.lib().orc_triangulate(xn1[i], xn2[i], T1.reshape(-1), T2.reshape(-1), o) == 1
+        assert np.abs(o - pts[i]).max() <= 1e-4 * max(1.0, np.abs(o).max())
+        A = np.stack([xn1[i, 0] * T1[2] - T1[0], xn1[i, 1] * T1[2] - T1[1], xn2[i, 0] * T2[2] - T2[0], xn2[i, 1] * T2[2] - T2[1]])
+        x = np.linalg.svd(A.astype(np.float64))[2][3]
+        x = x[:3] / x[3]
+        worst = max(worst, np.abs(pts[i] - x).max() / max(1.0, np.abs(x).max()))
+        assert np.abs(pts[i] - x).max() <= 1e-4 * max(1.0, np.abs(x).max())
+    assert np.abs(pts - P).max() < 1e-4          # float32 rows, a baseline of several metres
+    print(f"E: triangulate n {n}, {angle} rad: worst device - numpy SVD {worst:.3g} (bound 1e-4)")
 
 
 @pytest.mark.parametrize("fix_scale,scale", [(True, 1.0), (False, 0.8)])
@@ -165,6 +183,24 @@ def test_rgb_to_gray(vo, orc):
         assert np.array_equal(vo.rgb_to_gray(img, first_is_red).reshape(-1), want)
     y = (0.299 * img[..., 0] + 0.587 * img[..., 1] + 0.114 * img[..., 2])
     assert np.abs(vo.rgb_to_gray(img, True).astype(float) - y).max() <= 1.0   # the fixed-point weights of cv::cvtColor
+
+
+@pytest.mark.parametrize("shape", [(1, 1), (5, 51), (257, 1), (37, 29)])
+@pytest.mark.parametrize("channels", [3, 4])
+def test_rgb_to_gray_shapes_and_channels(vo, orc, shape, channels):
+    """the test above is twelve blocks exactly; these end inside a block (1, 255, 257 and 1073 pixels); with 4 channels the
+    fourth is skipped; both channel orders against the oracle and the float formula"""
+    rng = np.random.default_rng(4)
+    h, w = shape
+    img = rng.integers(0, 256, (h, w, channels), dtype=np.uint8)
+    for first_is_red in (True, False):
+        want = np.zeros(h * w, np.uint8)
+        orc.lib().orc_rgb_to_gray(img.reshape(-1), h * w, channels, int(first_is_red), want)
+        got = vo.rgb_to_gray(img, first_is_red)
+        assert got.shape == (h, w) and np.array_equal(got.reshape(-1), want)
+        r, b = (img[..., 0], img[..., 2]) if first_is_red else (img[..., 2], img[..., 0])
+        y = 0.299 * r + 0.587 * img[..., 1] + 0.114 * b
+        assert np.abs(got.astype(float) - y).max() <= 1.0   # the fixed-point weights of cv::cvtColor
 
 
 def _write_dbow3_binary(path, k, L, parent, weight, word_id, desc, children=None, compressed=False, truncate=None, bad_parent=False,
