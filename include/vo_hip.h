@@ -1129,6 +1129,102 @@ int vo_kfstore_new_points_result(vo_kfstore *s, int32_t *n_neighbors, int32_t *n
                                  int created_capacity);
 int vo_kfstore_get_points(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *ids, double *points, uint8_t *point_desc,
                           float *min_distance, float *max_distance, double *normals);
+/* Local bundle adjustment from the store: Optimizer::solveLocalBAPoseAndPoint
+ * (optimizer_ceres.cpp:446-808) with the window gathered (:449-592) and the result written back (:757-804) on the device,
+ * MapPoint::eraseObservedKF / eraseMapPoint (mappoint.cpp:333-381) and MapPoint::updateNormalAndDepth (mappoint.cpp:66-116)
+ * included; the solve in between is vo_ba's, unchanged.  A store that does not call enable_local_ba allocates and behaves
+ * exactly as before; every entry point of this block returns VO_ERR_INVALID on it.  "holds", "observation", obs(p) and bad(j)
+ * are section 4i's definitions above; pointer-keyed containers are walked in ascending key-frame number.
+ * enable_local_ba(max_cams, max_points, max_edges): valid only on an EMPTY store on which vo_kfstore_enable_mapping has
+ * succeeded, else VO_ERR_INVALID; capacities below 1 are VO_ERR_INVALID.  Allocates, with K = max_keyframes, N =
+ * max_features, C / P / E the capacities and every array rounded up to 16 bytes: ref_kf = MapPoint::keyFrame_ref_ per
+ * feature (int32, default -1: unknown; 4 K N); three words per key-frame (12 K); the point grid's workgroup counts
+ * (4 ceil(K N / 256)); per point the edge offsets, refresh_points' list and the dead byte (9 P + 4); the window -- the
+ * record (64), cameras (53 C), points (28 P), edges (44 E); the apply's inputs (96 C + 24 P + E): 4 K N + 4 ceil(K N / 256) +
+ * 12 K + 149 C + 61 P + 45 E + 68 bytes as listed, 5 472 252 at 500 key-frames of 1000 features with 64 cameras, 8192 points
+ * and 65536 edges, and 5 472 272 allocated there; and ONE page-locked staging block of the larger of the window and the inputs
+ * (host memory, 3 116 416 bytes there, before the allocator's headroom).  Synchronises once.
+ * set_point_refs: ref_kf [n] (host, n as inserted) of a key-frame's features; values in [-1, size), else VO_ERR_INVALID; one
+ * copy, synchronises once.  set_point_refs_dev: device array [n], enqueues only, not validated (a value outside the holders
+ * resolves like -1); it must stay untouched until the stream has passed the call.  create_map_points writes ref_kf = current
+ * into both features of a point it creates (mappoint.cpp:37).  An erase (section 4i) leaves the column alone: a reference
+ * key-frame that no longer holds the point is resolved by the next refresh (mappoint.cpp:350-351).
+ * local_ba_window(current): current in [0, size) is validated; everything else is ENQUEUED on the store's stream -- the index
+ * rebuilt first when stale, then five launches; no host synchronisation, no device-to-host copy, no allocation.  The window
+ * is that of the reference called once:
+ *  1 cameras: camera 0 is current; then current's WHOLE ordered list (getOrderedKFs(): vo_kfstore_get_connections' `ordered`,
+ *    not the ten-entry graph row) as the call finds it, in its order, entries with bad(j) skipped (:461).  A skipped entry is
+ *    still marked local (:459 comes before the test) and never becomes a fixed camera.
+ *  2 points: the local cameras in list order, their features ascending, bit 0 set: the FIRST occurrence of an id is point j,
+ *    its position the store's row at that occurrence (:480-499).
+ *  3 fixed cameras: every key-frame with !bad that holds a local point and is neither current nor in the ordered list,
+ *    appended in ascending key-frame number (:502-528).  cam_fixed = fixed, or the key-frame is number 0 (:578).
+ *  4 edges: points in order, per point its holders in ascending key-frame number, each at its observation: camera, point
+ *    and feature index, obs = (x, y, u_right) widened to double, inv_sigma = 1.0 / (double)scale_factors[octave] (:555-591).
+ *    A holder without a camera -- a bad one, in the list or not -- gets no edge and is counted in n_dropped (the reference
+ *    dereferences a null pose block there, :561).
+ *  5 poses6 = [upsilon; omega] of Tcw through vo_se3_log's arithmetic.
+ *  6 current erased or without a pose, or any camera without a pose: the window is EMPTY (all counts 0) and the sticky
+ *    VO_KFSTORE_CONNECTIONS_INVALID is raised.  More cameras, points or edges than the capacities: the window is OVERFLOWED,
+ *    the sticky VO_KFSTORE_LOCAL_BA_CAPACITY is raised (vo_kfstore_connections_status reads and clears both), the record
+ *    holds the TRUE counts and no array is valid; nothing is truncated.
+ * local_ba_window_result: synchronises (one copy into the staging block); record [16] = n_cams, n_local (current and the
+ * list's cameras), n_fixed, n_points, n_edges, n_dropped, status (VO_KFSTORE_BA_WINDOW_*), current, and of the last apply
+ * n_erased, n_feature0, n_dead; five zeros.  Arrays sized by the capacities, filled to the counts when the status is OK: cam_keyframe,
+ * cam_fixed, poses6 [n_cams][6], point_id, points [n_points][3], edge_cam, edge_point, edge_feature, edge_obs [n_edges][3],
+ * edge_inv_sigma.  Any pointer may be NULL.
+ * local_ba_apply(poses6, points, edge_erase): a solver's result for the LAST window, host arrays in the window's order
+ * ([n_cams][6], [n_points][3], [n_edges]); one copy out of the staging block, two launches, one synchronisation at the end
+ * (the staging block is free on return).  VO_ERR_INVALID when there
+ * is no window, the last one is empty or overflowed, or the store has been changed since (every call of this header that
+ * writes the store, an apply included, advances a generation word; reads do not).  The record is fetched first when no
+ * local_ba_window_result has done so (one synchronisation).  In the reference's order:
+ *  a erased edges (k, p): k leaves the holders of p -- bit 0 is cleared in EVERY feature of k that carries p.  The store has
+ *    one fact where the reference has two (mappoints_[idx] and observedKFs_), so quirk Q-B3 (`if (idx > 0)` at :768 leaves
+ *    feature 0 pointing at a point that no longer lists the key-frame) cannot be stored: n_feature0 counts the erased edges
+ *    whose observation is feature 0, for a caller that keeps the pointer model; and a second feature of k that carries p does
+ *    not turn k back into a holder.
+ *  b a point with an erased edge whose remaining obs(p) <= 2 dies (mappoint.cpp:353-381): bit 0 is cleared in every
+ *    feature that carries it.  The order of the erases does not matter: obs only falls.
+ *  c free cameras get SE3::exp(poses6) -- vo_se3_exp, evaluated on the host while staging -- as Tcw12 in the pose column;
+ *    fixed cameras keep their bytes.
+ *  d the new position of p goes to every live feature that carries p, in every key-frame; then p is refreshed (below) on the
+ *    poses of c and the holders of a / b.  Dead points are not refreshed; rows of cleared features keep their bytes.
+ *  e the index is marked stale.  Connection weights do not change.
+ * refresh_points(n, ids): MapPoint::updateNormalAndDepth for a host list of ids (n <= max_points, else VO_ERR_CAPACITY; ids
+ * >= 0); one copy, synchronises once (the list is free on return), the index rebuilt first when stale, one launch.  Per id:
+ *  - its holders in ascending key-frame number, bad ones INCLUDED (:93-100 do not test isBad); a holder without a pose is left
+ *    out of the sum and raises the sticky VO_KFSTORE_CONNECTIONS_INVALID;
+ *  - ref(p) = ref_kf at p's first live key, or, when that is -1 or no longer a holder, the lowest-numbered holder; the
+ *    resolved value is written to every live feature that carries p;
+ *  - in double, every operation rounded on its own (DESIGN.md section 4k has the order): Ow = -(R^T t) as in section 4j,
+ *    d = p - Ow, normal = (sum over the holders of d / |d|) / n; max = (float)|p - Ow_ref| * scale_factors[octave at ref's
+ *    observation], min = max / scale_factors[n_levels - 1] in float;
+ *  - the normal and min / max go to every live feature that carries p (no holder has a pose: the normal stays; ref has none:
+ *    min / max stay).
+ * local_ba(ba, current, stop, summaries): window, ONE device-to-host copy into the staging block, vo_ba_reset(ba, ...) +
+ * vo_ba_local_ba(ba, stop, ...) on the CALLER's handle (one per thread, any previous problem is replaced; cam = the store's
+ * fx, fy, cx, cy, bf widened), apply.  VO_ERR_STOPPED as vo_ba_local_ba returns it (the reference's return at :594): nothing
+ * is written back.  VO_ERR_CAPACITY for an overflowed window, VO_ERR_INVALID for an empty one, and whatever vo_ba_reset
+ * refuses: nothing is written back.  summaries: NULL or [2].  `map_->getAllKeyFramesCnt() > 2` stays the caller's test.
+ * (Declared behind vo_ba below.)
+ * get_point_refs / get_pose: synchronise; the ref_kf column [n] of a key-frame, and its Tcw12 with the pose-set word, as the
+ * store holds them (get_pose: valid on every store with mapping). */
+#define VO_KFSTORE_LOCAL_BA_CAPACITY 4
+#define VO_KFSTORE_BA_WINDOW_OK 0
+#define VO_KFSTORE_BA_WINDOW_EMPTY 1
+#define VO_KFSTORE_BA_WINDOW_OVERFLOW 2
+int vo_kfstore_enable_local_ba(vo_kfstore *s, int max_cams, int max_points, int max_edges);
+int vo_kfstore_set_point_refs(vo_kfstore *s, int keyframe, const int32_t *ref_kf);
+int vo_kfstore_set_point_refs_dev(vo_kfstore *s, int keyframe, const int32_t *dev_ref_kf);
+int vo_kfstore_get_point_refs(vo_kfstore *s, int keyframe, int32_t *ref_kf);
+int vo_kfstore_local_ba_window(vo_kfstore *s, int current);
+int vo_kfstore_local_ba_window_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *cam_keyframe, uint8_t *cam_fixed,
+                                      double *poses6, int32_t *point_id, double *points, int32_t *edge_cam, int32_t *edge_point,
+                                      int32_t *edge_feature, double *edge_obs, double *edge_inv_sigma);
+int vo_kfstore_local_ba_apply(vo_kfstore *s, const double *poses6, const double *points, const uint8_t *edge_erase);
+int vo_kfstore_refresh_points(vo_kfstore *s, int n, const int32_t *ids);
+int vo_kfstore_get_pose(vo_kfstore *s, int keyframe, double *Tcw12, int32_t *pose_set);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors
@@ -1414,6 +1510,8 @@ int vo_ba_local_ba(vo_ba *h, const volatile unsigned char *stop, uint8_t *edge_e
  * so that several independent problems (handles) overlap on one GPU. */
 int vo_ba_local_ba_enqueue(vo_ba *h, const volatile unsigned char *stop);
 int vo_ba_local_ba_finish(vo_ba *h, uint8_t *edge_erase, vo_lm_summary *summaries);
+/* The same for a key-frame of a store, gathered and written back on the device (the contract: the vo_kfstore block above). */
+int vo_kfstore_local_ba(vo_kfstore *s, vo_ba *ba, int current, const volatile unsigned char *stop, vo_lm_summary *summaries);
 /* One Ceres-style LM solve (ceres::Solve with DENSE_SCHUR at :604 / :699) on the current state.
  * huber_* <= 0 disables the loss.  edge_active: NULL or host mask in caller's edge order. */
 int vo_ba_solve(vo_ba *h, double huber_mono, double huber_stereo, int max_iterations,

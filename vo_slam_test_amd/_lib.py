@@ -61,6 +61,9 @@ SYMBOLS = [
     "vo_kfstore_cull_keyframes", "vo_kfstore_erase_keyframe", "vo_kfstore_cull_result", "vo_kfstore_cull_state", "vo_kfstore_get_flags",
     "vo_kfstore_enable_mapping", "vo_kfstore_set_pose", "vo_kfstore_set_pose_dev", "vo_kfstore_set_keypoint_xy", "vo_kfstore_set_keypoint_xy_dev",
     "vo_kfstore_next_point_id", "vo_kfstore_create_map_points", "vo_kfstore_new_points_result", "vo_kfstore_get_points",
+    "vo_kfstore_enable_local_ba", "vo_kfstore_set_point_refs", "vo_kfstore_set_point_refs_dev", "vo_kfstore_get_point_refs",
+    "vo_kfstore_local_ba_window", "vo_kfstore_local_ba_window_result", "vo_kfstore_local_ba_apply", "vo_kfstore_refresh_points",
+    "vo_kfstore_get_pose", "vo_kfstore_local_ba",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1554,6 +1557,7 @@ class KeyFrameStore:
         self._h = C.c_void_p()
         check(lib().vo_kfstore_create(C.byref(self._h), int(max_keyframes), int(max_features)), "vo_kfstore_create")
         self.max_features = int(max_features)
+        self._ba_caps = (1, 1, 1)   # (until enable_local_ba: the library refuses the calls that size their arrays by it)
         if stream is not None:
             check(lib().vo_kfstore_set_stream(self._h, _p(stream)), "vo_kfstore_set_stream")
 
@@ -1776,6 +1780,75 @@ class KeyFrameStore:
         check(lib().vo_kfstore_get_points(self._h, int(keyframe), *(_p(out[k]) for k in ("flags", "ids", "points", "point_desc", "min_dist",
                                                                                          "max_dist", "normals"))), "vo_kfstore_get_points")
         return out
+
+    def pose(self, keyframe):
+        """-> (Tcw12 as the store holds it, whether it has been set)"""
+        T, on = np.zeros(12), C.c_int32(0)
+        check(lib().vo_kfstore_get_pose(self._h, int(keyframe), _p(T), C.byref(on)), "vo_kfstore_get_pose")
+        return T, bool(on.value)
+
+    CONNECTIONS_LOCAL_BA_CAPACITY = 4
+    BA_WINDOW_OK, BA_WINDOW_EMPTY, BA_WINDOW_OVERFLOW = 0, 1, 2
+    BA_RECORD = ("n_cams", "n_local", "n_fixed", "n_points", "n_edges", "n_dropped", "status", "current", "n_erased", "n_feature0", "n_dead")
+
+    def enable_local_ba(self, max_cams, max_points, max_edges):
+        """solveLocalBAPoseAndPoint's window and write-back on the device from now on; valid on an
+        empty store after enable_mapping only"""
+        check(lib().vo_kfstore_enable_local_ba(self._h, int(max_cams), int(max_points), int(max_edges)), "vo_kfstore_enable_local_ba")
+        self._ba_caps = (int(max_cams), int(max_points), int(max_edges))
+
+    def set_point_refs(self, keyframe, ref_kf):
+        """MapPoint::keyFrame_ref_ per feature [n] as a key-frame number, -1: unknown.  numpy: validated, copied, synchronises
+        once; a device tensor (int32): enqueued only"""
+        if hasattr(ref_kf, "data_ptr"):
+            _need_tensor(ref_kf, "int32", None, "set_point_refs")
+            check(lib().vo_kfstore_set_point_refs_dev(self._h, int(keyframe), _p(ref_kf)), "vo_kfstore_set_point_refs_dev")
+            return
+        r = np.ascontiguousarray(ref_kf, np.int32)
+        check(lib().vo_kfstore_set_point_refs(self._h, int(keyframe), _p(r)), "vo_kfstore_set_point_refs")
+
+    def point_refs(self, keyframe, n):
+        r = np.zeros(int(n), np.int32)
+        check(lib().vo_kfstore_get_point_refs(self._h, int(keyframe), _p(r)), "vo_kfstore_get_point_refs")
+        return r
+
+    def local_ba_window(self, current):
+        """the window of Optimizer::solveLocalBAPoseAndPoint for the current key-frame; enqueued only"""
+        check(lib().vo_kfstore_local_ba_window(self._h, int(current)), "vo_kfstore_local_ba_window")
+
+    def local_ba_window_result(self):
+        """the last window -> dict(record (dict over BA_RECORD), cam_keyframe, fixed, poses, point_id, points, e_cam, e_pt,
+        e_feature, e_obs, e_inv_sigma) cut to the record's counts; the solver's names, so that dict(w, cam=...) is a problem
+        of BundleAdjuster"""
+        nc, npt, ne = self._ba_caps
+        rec = np.zeros(16, np.int32)
+        a = dict(cam_keyframe=np.zeros(nc, np.int32), fixed=np.zeros(nc, np.uint8), poses=np.zeros((nc, 6)), point_id=np.zeros(npt, np.int32),
+                 points=np.zeros((npt, 3)), e_cam=np.zeros(ne, np.int32), e_pt=np.zeros(ne, np.int32), e_feature=np.zeros(ne, np.int32),
+                 e_obs=np.zeros((ne, 3)), e_inv_sigma=np.zeros(ne))
+        check(lib().vo_kfstore_local_ba_window_result(self._h, _p(rec), *(_p(v) for v in a.values())), "vo_kfstore_local_ba_window_result")
+        r = {k: int(rec[i]) for i, k in enumerate(self.BA_RECORD)}
+        ok = r["status"] == self.BA_WINDOW_OK
+        cut = dict(cam_keyframe="n_cams", fixed="n_cams", poses="n_cams", point_id="n_points", points="n_points")
+        return dict({k: v[:r[cut.get(k, "n_edges")] if ok else 0].copy() for k, v in a.items()}, record=r)
+
+    def local_ba_apply(self, poses6, points, edge_erase):
+        """a solver's result for the last window written back (host arrays in the window's order)"""
+        po, pt, er = np.ascontiguousarray(poses6, np.float64), np.ascontiguousarray(points, np.float64), np.ascontiguousarray(edge_erase, np.uint8)
+        check(lib().vo_kfstore_local_ba_apply(self._h, _p(po), _p(pt), _p(er)), "vo_kfstore_local_ba_apply")
+
+    def refresh_points(self, ids):
+        """MapPoint::updateNormalAndDepth for the listed map-point ids"""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        check(lib().vo_kfstore_refresh_points(self._h, len(a), _p(a)), "vo_kfstore_refresh_points")
+
+    def local_ba(self, ba, current, stop=None):
+        """window, solve on the caller's BundleAdjuster (its problem is replaced), write-back -> (summaries, status): status 0,
+        or -5 when the stop flag (a ctypes.c_ubyte, or None) was set before the first solve; other failures raise"""
+        sums = (LmSummary * 2)()
+        rc = lib().vo_kfstore_local_ba(self._h, ba._h, int(current), None if stop is None else C.byref(stop), C.byref(sums))
+        if rc not in (0, -5):
+            check(rc, "vo_kfstore_local_ba")
+        return sums, rc
 
 
 def rgb_to_gray(img, first_is_red=True):

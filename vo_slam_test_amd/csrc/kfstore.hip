@@ -4,6 +4,7 @@
 // kernels reach a key-frame's arrays from its number alone.
 #include "vo_common.h"
 
+#include <algorithm>
 #include <new>
 #include <vector>
 
@@ -103,6 +104,16 @@ struct vo_kfstore {
   vo::KfMapView M{};
   size_t map_bytes = 0;
   bool mapping = false;
+  vo::OwnedDevBuf ba;                 // vo_kfstore_enable_local_ba: the arrays of section 4k
+  vo::OwnedPinnedBuf ba_stage;        // the window coming down, or a solver's result going up: one copy each
+  vo::KfBaView B{};
+  bool local_ba = false;
+  // the generation word: every call that writes the store advances it; an apply is valid for the window of its generation
+  unsigned long long gen = 0, ba_gen = 0;
+  bool ba_window = false, ba_rec_known = false;  // a window has been enqueued; its record has been fetched
+  int32_t ba_rec[vo::kBaRecInts] = {0};
+  std::vector<double> ba_poses, ba_points;  // the composed call's solver state (sized by the capacities: no allocation per call)
+  std::vector<uint8_t> ba_erase;
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -206,6 +217,12 @@ int need_culling(const vo_kfstore *s, const char *call) {
 int need_mapping(const vo_kfstore *s, const char *call) {
   if (s && s->mapping) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_mapping has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_local_ba(const vo_kfstore *s, const char *call) {
+  if (s && s->local_ba) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_local_ba has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -363,7 +380,7 @@ int vo_kfstore_insert(vo_kfstore *s, const vo_reloc_candidate *kf, int32_t *inde
   if (index) *index = s->size;
   s->n.push_back(K.n);
   s->size++;
-  s->obs_dirty = true;
+  s->obs_dirty = true, s->gen++;
   return VO_OK;
 }
 
@@ -411,12 +428,13 @@ int vo_kfstore_insert_dev(vo_kfstore *s, int n, int bad, const float *dev_angle,
   if (index) *index = s->size;
   s->n.push_back(n);
   s->size++;
-  s->obs_dirty = true;
+  s->obs_dirty = true, s->gen++;
   return VO_OK;
 }
 
 int vo_kfstore_set_bad(vo_kfstore *s, int keyframe, int bad) {
   if (!s || keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  s->gen++;
   hipLaunchKernelGGL(k_kfstore_bad, dim3(1), dim3(64), 0, s->st, reinterpret_cast<int *>(s->record(keyframe)), bad ? 1 : 0);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
@@ -452,7 +470,7 @@ int vo_kfstore_update_points(vo_kfstore *s, int keyframe, const uint8_t *flags, 
   VO_CHECK(up(V.o_pdesc, n * 32));
   VO_CHECK(up(V.o_mind, n * 4));
   VO_CHECK(up(V.o_maxd, n * 4));
-  s->obs_dirty = true;
+  s->obs_dirty = true, s->gen++;
   VO_HIP_CHECK(hipStreamSynchronize(s->st));
   return VO_OK;
 }
@@ -463,6 +481,7 @@ int vo_kfstore_set_graph(vo_kfstore *s, int keyframe, int n_neighbors, const int
   if (s->conn) return graph_has_writer("vo_kfstore_set_graph");
   int32_t row[vo::kKfGraphInts];
   VO_CHECK(graph_row(s, "vo_kfstore_set_graph", keyframe, n_neighbors, neighbors, n_children, children, parent, row));
+  s->gen++;
   const char *W = "vo_kfstore_set_graph";
   VO_CHECK(vo::copy_h2d(s->graph.as<int>() + (size_t)keyframe * vo::kKfGraphInts, row, sizeof(row), s->st, W));
   return vo::stream_sync(s->st, W);  // (row is a local: the copy must have read it)
@@ -480,6 +499,7 @@ int vo_kfstore_set_graph_batch(vo_kfstore *s, int first, int count, const int32_
     VO_CHECK(graph_row(s, "vo_kfstore_set_graph_batch", first + k, n_neighbors[k], neighbors + (size_t)k * vo::kKfGraphNb, n_children[k],
                        children + (size_t)k * vo::kKfGraphCh, parent[k], rows.data() + (size_t)k * vo::kKfGraphInts));
   const char *W = "vo_kfstore_set_graph_batch";
+  s->gen++;
   VO_CHECK(vo::copy_h2d(s->graph.as<int>() + (size_t)first * vo::kKfGraphInts, rows.data(), rows.size() * 4, s->st, W));
   return vo::stream_sync(s->st, W);
 }
@@ -489,6 +509,7 @@ int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals) {
   const size_t n = (size_t)s->n[(size_t)keyframe];
   if (n == 0) return VO_OK;
   if (!normals) return VO_ERR_INVALID;
+  s->gen++;
   const char *W = "vo_kfstore_set_normals";
   VO_CHECK(vo::copy_h2d(s->normals.as<double>() + (size_t)keyframe * s->NK * 3, normals, n * 24, s->st, W));
   return vo::stream_sync(s->st, W);
@@ -528,6 +549,7 @@ int vo_kfstore_set_keypoints(vo_kfstore *s, int keyframe, const int32_t *octave,
   const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
   if (n == 0) return VO_OK;
   if (!octave || !depth || !u_right) return VO_ERR_INVALID;
+  s->gen++;
   // the three columns of a key-frame lie side by side: staged whole (the defaults beyond n), one copy
   uint8_t *h = s->stage.data();  // (a record is longer than 12 bytes a feature)
   int32_t *ho = reinterpret_cast<int32_t *>(h);
@@ -544,6 +566,7 @@ int vo_kfstore_set_keypoints_dev(vo_kfstore *s, int keyframe, const int32_t *dev
   const size_t n = (size_t)s->n[(size_t)keyframe];
   if (n == 0) return VO_OK;
   if (!dev_octave || !dev_depth || !dev_u_right) return VO_ERR_INVALID;
+  s->gen++;
   VO_HIP_CHECK(hipMemcpyAsync(vo::cull_octave(s->X, keyframe), dev_octave, n * 4, hipMemcpyDeviceToDevice, s->st));
   VO_HIP_CHECK(hipMemcpyAsync(vo::cull_depth(s->X, keyframe), dev_depth, n * 4, hipMemcpyDeviceToDevice, s->st));
   VO_HIP_CHECK(hipMemcpyAsync(vo::cull_uright(s->X, keyframe), dev_u_right, n * 4, hipMemcpyDeviceToDevice, s->st));
@@ -554,6 +577,7 @@ int vo_kfstore_set_erase_lock(vo_kfstore *s, int keyframe, int on) {
   const char *W = "vo_kfstore_set_erase_lock";
   VO_CHECK(need_culling(s, W));
   VO_CHECK(need_keyframe(s, W, keyframe));
+  s->gen++;
   return vo::cull_set_lock(s->X, keyframe, on, s->st);
 }
 
@@ -566,7 +590,7 @@ int vo_kfstore_cull_keyframes(vo_kfstore *s, int current, float th_depth) {
   vo::KfObsView O;
   VO_CHECK(vo::kfstore_obs_view(s, &O));
   VO_CHECK(vo::cull_enqueue(vo::kfstore_view(s), O, vo::connections_view(s->conn), s->X, current, th_depth, s->st));
-  s->obs_dirty = true;  // (whether anything was erased only the device knows)
+  s->obs_dirty = true, s->gen++;  // (whether anything was erased only the device knows)
   return vo::connections_order(s->conn, s->size, s->st);
 }
 
@@ -577,7 +601,7 @@ int vo_kfstore_erase_keyframe(vo_kfstore *s, int keyframe) {
   vo::KfObsView O;
   VO_CHECK(vo::kfstore_obs_view(s, &O));
   VO_CHECK(vo::erase_enqueue(vo::kfstore_view(s), O, vo::connections_view(s->conn), s->X, keyframe, s->st));
-  s->obs_dirty = true;
+  s->obs_dirty = true, s->gen++;
   return vo::connections_order(s->conn, s->size, s->st);
 }
 
@@ -659,6 +683,7 @@ int vo_kfstore_set_pose(vo_kfstore *s, int keyframe, const double *Tcw12) {
   VO_CHECK(need_mapping(s, W));
   VO_CHECK(need_keyframe(s, W, keyframe));
   if (!Tcw12) return VO_ERR_INVALID;
+  s->gen++;
   // the pose-set word lies behind the pose (the thirteenth slot): one copy
   double *h = reinterpret_cast<double *>(s->stage.data());
   memcpy(h, Tcw12, 96);
@@ -673,6 +698,7 @@ int vo_kfstore_set_pose_dev(vo_kfstore *s, int keyframe, const double *dev_Tcw12
   VO_CHECK(need_mapping(s, W));
   VO_CHECK(need_keyframe(s, W, keyframe));
   if (!dev_Tcw12) return VO_ERR_INVALID;
+  s->gen++;
   return vo::mapping_set_pose_dev(s->M, keyframe, dev_Tcw12, s->st);
 }
 
@@ -683,6 +709,7 @@ int vo_kfstore_set_keypoint_xy(vo_kfstore *s, int keyframe, const float *xy) {
   const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
   if (n == 0) return VO_OK;
   if (!xy) return VO_ERR_INVALID;
+  s->gen++;
   // the two columns of a key-frame lie side by side: staged whole (zero beyond n), one copy
   float *hx = reinterpret_cast<float *>(s->stage.data()), *hy = hx + NK;  // (a record is longer than 8 bytes a feature)
   for (size_t i = 0; i < NK; i++) hx[i] = i < n ? xy[2 * i] : 0.f, hy[i] = i < n ? xy[2 * i + 1] : 0.f;
@@ -697,6 +724,7 @@ int vo_kfstore_set_keypoint_xy_dev(vo_kfstore *s, int keyframe, const float *dev
   const int n = s->n[(size_t)keyframe];
   if (n == 0) return VO_OK;
   if (!dev_xy) return VO_ERR_INVALID;
+  s->gen++;
   return vo::mapping_split_xy(s->M, keyframe, n, dev_xy, s->st);
 }
 
@@ -722,9 +750,9 @@ int vo_kfstore_create_map_points(vo_kfstore *s, int current, int max_neighbors) 
   const vo::KfConnView C = vo::connections_view(s->conn);
   for (int i = 0; i < max_neighbors; i++) {  // step i + 1 reads the flags step i wrote: walk, replay, create per neighbour
     VO_CHECK(vo::tri_walk_replay(V, s->X, s->M, s->graph.as<int>(), C.status, current, i, s->st));
-    VO_CHECK(vo::np_create(V, s->X, s->M, s->normals.as<double>(), current, i, s->st));
+    VO_CHECK(vo::np_create(V, s->X, s->M, s->normals.as<double>(), s->local_ba ? s->B.ref_kf : nullptr, current, i, s->st));
   }
-  s->obs_dirty = true;  // (whether anything was created only the device knows)
+  s->obs_dirty = true, s->gen++;  // (whether anything was created only the device knows)
   return VO_OK;
 }
 
@@ -776,6 +804,214 @@ int vo_kfstore_get_points(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *
   return vo::stream_sync(s->st, W);
 }
 
+int vo_kfstore_get_pose(vo_kfstore *s, int keyframe, double *Tcw12, int32_t *pose_set) {
+  const char *W = "vo_kfstore_get_pose";
+  VO_CHECK(need_mapping(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  double h[vo::kNpPoseDoubles];
+  VO_CHECK(vo::copy_d2h(h, vo::np_pose(s->M, keyframe), sizeof(h), s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  if (Tcw12) memcpy(Tcw12, h, 96);
+  if (pose_set) memcpy(pose_set, h + 12, 4);
+  return VO_OK;
+}
+
+int vo_kfstore_enable_local_ba(vo_kfstore *s, int max_cams, int max_points, int max_edges) {
+  const char *W = "vo_kfstore_enable_local_ba";
+  VO_CHECK(need_mapping(s, W));
+  if (max_cams < 1 || max_points < 1 || max_edges < 1) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->local_ba) return VO_OK;
+  VO_CHECK(s->ba.reserve(vo::ba_store_bytes(s->max_kf, s->NK, max_cams, max_points, max_edges)));
+  s->B = vo::ba_store_layout(s->ba.p, s->max_kf, s->NK, max_cams, max_points, max_edges);
+  VO_CHECK(s->ba_stage.reserve(std::max(s->B.win_bytes, s->B.in_bytes)));
+  s->ba_poses.resize((size_t)max_cams * 6), s->ba_points.resize((size_t)max_points * 3), s->ba_erase.resize((size_t)max_edges + 1);
+  VO_CHECK(vo::ba_store_init(s->B, s->max_kf, s->st));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  s->local_ba = true;
+  return VO_OK;
+}
+
+int vo_kfstore_set_point_refs(vo_kfstore *s, int keyframe, const int32_t *ref_kf) {
+  const char *W = "vo_kfstore_set_point_refs";
+  VO_CHECK(need_local_ba(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!ref_kf) return VO_ERR_INVALID;
+  for (size_t i = 0; i < n; i++)
+    if (ref_kf[i] < -1 || ref_kf[i] >= s->size) {
+      vo::set_error("%s: feature %zu: reference key-frame %d outside [-1, %d)", W, i, ref_kf[i], s->size);
+      return VO_ERR_INVALID;
+    }
+  s->gen++;
+  VO_CHECK(vo::copy_h2d(s->B.ref_kf + (size_t)keyframe * s->NK, ref_kf, n * 4, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_point_refs_dev(vo_kfstore *s, int keyframe, const int32_t *dev_ref_kf) {
+  const char *W = "vo_kfstore_set_point_refs_dev";
+  VO_CHECK(need_local_ba(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_ref_kf) return VO_ERR_INVALID;
+  s->gen++;
+  VO_HIP_CHECK(hipMemcpyAsync(s->B.ref_kf + (size_t)keyframe * s->NK, dev_ref_kf, n * 4, hipMemcpyDeviceToDevice, s->st));
+  return VO_OK;
+}
+
+int vo_kfstore_get_point_refs(vo_kfstore *s, int keyframe, int32_t *ref_kf) {
+  const char *W = "vo_kfstore_get_point_refs";
+  VO_CHECK(need_local_ba(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!ref_kf) return VO_ERR_INVALID;
+  VO_CHECK(vo::copy_d2h(ref_kf, s->B.ref_kf + (size_t)keyframe * s->NK, n * 4, s->st, W));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_local_ba_window(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_local_ba_window";
+  VO_CHECK(need_local_ba(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has been erased, or that a camera has no pose, only the device knows: the window is then empty)
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::ba_window_enqueue(vo::kfstore_view(s), O, vo::connections_view(s->conn), s->X, s->M, s->B, current, s->st));
+  s->ba_window = true, s->ba_rec_known = false, s->ba_gen = s->gen;
+  return VO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the window as one copy into the staging block; the record is then known on the host
+int ba_fetch_window(vo_kfstore *s, const char *W, bool record_only) {
+  VO_CHECK(vo::copy_d2h(s->ba_stage.data(), s->B.win, record_only ? sizeof(s->ba_rec) : s->B.win_bytes, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  memcpy(s->ba_rec, s->ba_stage.data(), sizeof(s->ba_rec));
+  s->ba_rec_known = true;
+  return VO_OK;
+}
+
+template <class T>
+const T *ba_staged(const vo_kfstore *s, const T *dev) {
+  return reinterpret_cast<const T *>(s->ba_stage.data() + (reinterpret_cast<const uint8_t *>(dev) - s->B.win));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_local_ba_window_result(vo_kfstore *s, int32_t *record, int32_t *cam_keyframe, uint8_t *cam_fixed, double *poses6,
+                                      int32_t *point_id, double *points, int32_t *edge_cam, int32_t *edge_point,
+                                      int32_t *edge_feature, double *edge_obs, double *edge_inv_sigma) {
+  const char *W = "vo_kfstore_local_ba_window_result";
+  VO_CHECK(need_local_ba(s, W));
+  VO_CHECK(ba_fetch_window(s, W, false));
+  const int32_t *r = s->ba_rec;
+  if (record) memcpy(record, r, sizeof(s->ba_rec));
+  if (r[vo::kBaStatus] != VO_KFSTORE_BA_WINDOW_OK) return VO_OK;
+  const size_t nc = (size_t)r[vo::kBaNCams], np = (size_t)r[vo::kBaNPoints], ne = (size_t)r[vo::kBaNEdges];
+  const vo::KfBaView &B = s->B;
+  if (cam_keyframe) memcpy(cam_keyframe, ba_staged(s, B.cam_kf), nc * 4);
+  if (cam_fixed) memcpy(cam_fixed, ba_staged(s, B.cam_fixed), nc);
+  if (poses6) memcpy(poses6, ba_staged(s, B.poses6), nc * 48);
+  if (point_id) memcpy(point_id, ba_staged(s, B.pt_id), np * 4);
+  if (points) memcpy(points, ba_staged(s, B.points), np * 24);
+  if (edge_cam) memcpy(edge_cam, ba_staged(s, B.e_cam), ne * 4);
+  if (edge_point) memcpy(edge_point, ba_staged(s, B.e_pt), ne * 4);
+  if (edge_feature) memcpy(edge_feature, ba_staged(s, B.e_feat), ne * 4);
+  if (edge_obs) memcpy(edge_obs, ba_staged(s, B.e_obs), ne * 24);
+  if (edge_inv_sigma) memcpy(edge_inv_sigma, ba_staged(s, B.e_isg), ne * 8);
+  return VO_OK;
+}
+
+int vo_kfstore_local_ba_apply(vo_kfstore *s, const double *poses6, const double *points, const uint8_t *edge_erase) {
+  const char *W = "vo_kfstore_local_ba_apply";
+  VO_CHECK(need_local_ba(s, W));
+  if (!s->ba_window || s->ba_gen != s->gen) {
+    vo::set_error("%s: no window, or the store has been changed since the last one", W);
+    return VO_ERR_INVALID;
+  }
+  if (!s->ba_rec_known) VO_CHECK(ba_fetch_window(s, W, true));
+  const int32_t *r = s->ba_rec;
+  if (r[vo::kBaStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    vo::set_error("%s: the last window is %s", W, r[vo::kBaStatus] == VO_KFSTORE_BA_WINDOW_EMPTY ? "empty" : "overflowed");
+    return VO_ERR_INVALID;
+  }
+  const size_t nc = (size_t)r[vo::kBaNCams], np = (size_t)r[vo::kBaNPoints], ne = (size_t)r[vo::kBaNEdges];
+  if (!poses6 || (np > 0 && !points) || (ne > 0 && !edge_erase)) return VO_ERR_INVALID;
+  // staged as the kernels read it: Tcw12 per camera (SE3::exp on the host, :786-788) | points | erase bytes
+  uint8_t *h = s->ba_stage.data();
+  double *T = reinterpret_cast<double *>(h);
+  for (size_t c = 0; c < nc; c++) VO_CHECK(vo_se3_exp(poses6 + 6 * c, T + 12 * c, T + 12 * c + 9));
+  if (np) memcpy(h + nc * 96, points, np * 24);
+  if (ne) memcpy(h + nc * 96 + np * 24, edge_erase, ne);
+  const size_t bytes = nc * 96 + np * 24 + ne;
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));  // (not stale: nothing has changed since the window)
+  VO_CHECK(vo::copy_h2d(s->B.in, h, bytes, s->st, W));
+  VO_CHECK(vo::ba_apply_enqueue(vo::kfstore_view(s), O, s->X, s->M, s->B, s->normals.as<double>(), vo::connections_view(s->conn).status,
+                                (int)nc, (int)np, (int)ne, s->st));
+  s->obs_dirty = true, s->gen++;
+  return vo::stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_refresh_points(vo_kfstore *s, int n, const int32_t *ids) {
+  const char *W = "vo_kfstore_refresh_points";
+  VO_CHECK(need_local_ba(s, W));
+  if (n < 0 || (n > 0 && !ids)) return VO_ERR_INVALID;
+  if (n > s->B.max_points) {
+    vo::set_error("%s: %d ids, the store was enabled for %d points", W, n, s->B.max_points);
+    return VO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0) {
+      vo::set_error("%s: entry %d: id %d is negative", W, i, ids[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::copy_h2d(s->B.ids_in, ids, (size_t)n * 4, s->st, W));
+  VO_CHECK(vo::ba_refresh_enqueue(vo::kfstore_view(s), O, s->X, s->M, s->B, s->normals.as<double>(), vo::connections_view(s->conn).status, n,
+                                  s->st));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_local_ba(vo_kfstore *s, vo_ba *ba, int current, const volatile unsigned char *stop, vo_lm_summary *summaries) {
+  const char *W = "vo_kfstore_local_ba";
+  VO_CHECK(need_local_ba(s, W));
+  if (!ba) return VO_ERR_INVALID;
+  VO_CHECK(vo_kfstore_local_ba_window(s, current));
+  VO_CHECK(ba_fetch_window(s, W, false));  // the ONE device-to-host copy
+  const int32_t *r = s->ba_rec;
+  if (r[vo::kBaStatus] == VO_KFSTORE_BA_WINDOW_OVERFLOW) {
+    vo::set_error("%s: %d cameras, %d points, %d edges; the store was enabled for %d, %d, %d", W, r[vo::kBaNCams], r[vo::kBaNPoints],
+                  r[vo::kBaNEdges], s->B.max_cams, s->B.max_points, s->B.max_edges);
+    return VO_ERR_CAPACITY;
+  }
+  if (r[vo::kBaStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    vo::set_error("%s: the window of key-frame %d is empty (erased, or a camera without a pose)", W, current);
+    return VO_ERR_INVALID;
+  }
+  const vo::KfBaView &B = s->B;
+  const double cam[5] = {s->M.cam[0], s->M.cam[1], s->M.cam[2], s->M.cam[3], s->M.cam[4]};  // float members widened (:543-548)
+  VO_CHECK(vo_ba_reset(ba, r[vo::kBaNCams], ba_staged(s, B.poses6), ba_staged(s, B.cam_fixed), r[vo::kBaNPoints], ba_staged(s, B.points),
+                       r[vo::kBaNEdges], ba_staged(s, B.e_cam), ba_staged(s, B.e_pt), ba_staged(s, B.e_obs), ba_staged(s, B.e_isg), cam));
+  VO_CHECK(vo_ba_local_ba(ba, stop, s->ba_erase.data(), summaries));  // (VO_ERR_STOPPED: the return at :594, no write-back)
+  VO_CHECK(vo_ba_get_state(ba, s->ba_poses.data(), s->ba_points.data()));
+  return vo_kfstore_local_ba_apply(s, s->ba_poses.data(), s->ba_points.data(), s->ba_erase.data());
+}
+
 int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {
   VO_CHECK(need_connections(s, "vo_kfstore_update_connections_dev"));
   if (n < 0 || (n > 0 && !dev_keyframes)) return VO_ERR_INVALID;
@@ -783,6 +1019,7 @@ int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_k
   VO_CHECK(vo::connections_reserve(s->conn, n, nullptr));  // (before the index: nothing is enqueued when it fails)
   vo::KfObsView O;
   VO_CHECK(vo::kfstore_obs_view(s, &O));
+  s->gen++;  // (the ordered lists are what a window starts from)
   return vo::connections_update(s->conn, vo::kfstore_view(s), O, n, dev_keyframes, s->st);
 }
 

@@ -1,0 +1,498 @@
+// local_ba_store.hip -- local bundle adjustment from the key-frame store: the window of
+// Optimizer::solveLocalBAPoseAndPoint (optimizer_ceres.cpp:449-592) assembled on the device from the observation index, its
+// write-back (:757-804) with MapPoint::eraseObservedKF / eraseMapPoint (mappoint.cpp:333-381), and
+// MapPoint::updateNormalAndDepth (mappoint.cpp:66-116).  The solve in between is vo_ba's, unchanged (kfstore.hip).
+//   k_ba_cams    ONE workgroup: `current`, then its ordered list in list order, bad entries marked but left out
+//   k_ba_count   a thread per (list position, feature): is this entry the first occurrence of its id?  Counts per workgroup
+//   k_ba_points  the same grid: the first occurrences ranked in order (workgroup counts summed, ballot ranks inside), the
+//                point's id and position, and ONE walk over its holders: edges counted, holders without a camera counted,
+//                non-local non-bad holders marked as fixed cameras
+//   k_ba_layout  ONE workgroup: fixed cameras in ascending key-frame number, the capacities, a camera per thread for
+//                [upsilon; omega] = log(Tcw), the exclusive scan of the points' edge counts
+//   k_ba_edges   a lane per point: its holders again, each edge written at the point's offset
+//   k_ba_erase   a lane per point: the erased edges' key-frames leave the holders, the point dies when obs <= 2; a thread
+//                per free camera writes its pose
+//   k_ba_refresh a lane per point: the new position into every live feature that carries it, then updateNormalAndDepth
+// Nothing depends on which thread runs when: positions come from counts and scans, the atomics are integer sums, and every
+// byte and word of the store has one writer per launch (an entry of the index carries one id, a point has one lane).
+// Compiled with -ffp-contract=off: the refresh rounds every double operation on its own, in the order section 4k writes down.
+#include "vo_common.h"
+
+#include "ba_math.h"
+#include "new_points_geom.h"
+#include "obs_walk.h"
+
+namespace {
+
+using namespace vo;
+
+enum { kOk = VO_KFSTORE_BA_WINDOW_OK, kEmpty = VO_KFSTORE_BA_WINDOW_EMPTY, kOverflow = VO_KFSTORE_BA_WINDOW_OVERFLOW };
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct BaLayout {
+  uint8_t *block;
+  size_t at = 0;
+  template <class T>
+  void take(T *&field, size_t bytes) {
+    field = block ? reinterpret_cast<T *>(block + at) : nullptr;
+    at += up16(bytes);
+  }
+};
+
+void ba_layout(BaLayout &L, KfBaView &B, int max_kf, int NK, int C, int P, int E) {
+  const size_t K = (size_t)max_kf, N = (size_t)NK;
+  L.take(B.ref_kf, K * N * 4);
+  L.take(B.mark, K * 4);
+  L.take(B.fixm, K * 4);
+  L.take(B.lcam, K * 4);
+  L.take(B.blk, ((K * N + 255) / 256) * 4);
+  L.take(B.pt_ne, ((size_t)P + 1) * 4);
+  L.take(B.ids_in, (size_t)P * 4);
+  L.take(B.dead, (size_t)P);
+  const size_t w0 = L.at;
+  L.take(B.rec, (size_t)kBaRecInts * 4);
+  L.take(B.cam_kf, (size_t)C * 4);
+  L.take(B.cam_fixed, (size_t)C);
+  L.take(B.poses6, (size_t)C * 48);
+  L.take(B.pt_id, (size_t)P * 4);
+  L.take(B.points, (size_t)P * 24);
+  L.take(B.e_cam, (size_t)E * 4);
+  L.take(B.e_pt, (size_t)E * 4);
+  L.take(B.e_feat, (size_t)E * 4);
+  L.take(B.e_obs, (size_t)E * 24);
+  L.take(B.e_isg, (size_t)E * 8);
+  B.win = reinterpret_cast<uint8_t *>(B.rec), B.win_bytes = L.at - w0;
+  B.in_bytes = up16((size_t)C * 96 + (size_t)P * 24 + (size_t)E);
+  L.take(B.in, B.in_bytes);
+}
+
+__device__ __forceinline__ int n_features(const KfStoreView &S, int k) { return min(max(kf_head(S, k)[0], 0), S.NK); }
+__device__ __forceinline__ bool kf_bad(const KfStoreView &S, int k) { return kf_head(S, k)[1] != 0; }
+__device__ __forceinline__ uint8_t *flag_byte(const KfStoreView &S, unsigned entry) {
+  const unsigned k = entry / (unsigned)S.NK;
+  return const_cast<uint8_t *>(kf_sec<uint8_t>(S, (int)k, S.o_flags)) + (entry - k * (unsigned)S.NK);
+}
+
+// exclusive prefix of `flag` over the workgroup in thread order; *total = the workgroup's sum (local_map.hip's block_rank).
+// s_w: one int per wavefront.  Two barriers.
+__device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = (int)blockDim.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  const int below = __popcll(m & ((1ull << lane) - 1ull));
+  __syncthreads();
+  if (lane == 0) s_w[w] = __popcll(m);
+  __syncthreads();
+  int base = 0, sum = 0;
+  for (int i = 0; i < nw; i++) {
+    const int c = s_w[i];
+    if (i < w) base += c;
+    sum += c;
+  }
+  *total = sum;
+  return base + below;
+}
+
+// first key position whose id is >= `id`
+__device__ __forceinline__ int obs_lower_bound(const KfObsView &O, int id) {
+  const unsigned long long first = (unsigned long long)(unsigned)id << 32;
+  int lo = 0, hi = O.n_keys;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (O.keys[mid] < first) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
+
+struct WinArgs {
+  KfStoreView S;
+  KfObsView O;
+  KfConnView C;
+  KfCullView X;
+  KfMapView M;
+  KfBaView B;
+  int current;
+};
+
+// ---- 1. local cameras (:449-463)
+__global__ __launch_bounds__(1024) void k_ba_cams(WinArgs A) {
+  __shared__ int s_w[16];
+  const int tid = threadIdx.x, size = A.S.size, cur = A.current;
+  const KfBaView &B = A.B;
+  for (int k = tid; k < size; k += 1024) B.mark[k] = 0, B.fixm[k] = 0;
+  if (tid < kBaRecInts) B.rec[tid] = tid == kBaCurrent ? cur : 0;
+  __syncthreads();
+  if (A.X.erased[cur] || !*np_pose_set(A.M, cur)) {  // (uniform) the window is empty
+    if (tid == 0) B.rec[kBaStatus] = kEmpty, atomicOr(A.C.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
+    return;
+  }
+  if (tid == 0) B.mark[cur] = 1, B.lcam[0] = cur;
+  const int n = min(max(A.C.n_ordered[cur], 0), size);
+  const int *list = A.C.ordered + (size_t)cur * A.C.max_kf;
+  int base = 1;
+  for (int t0 = 0; t0 < n; t0 += 1024) {
+    const int t = t0 + tid, j = t < n ? list[t] : -1;
+    const bool valid = j >= 0 && j < size && j != cur;
+    const bool take = valid && !kf_bad(A.S, j);  // `if (!kf->isBad())` (:461)
+    int total;
+    const int pos = base + block_rank(take, s_w, &total);
+    if (take && pos < size) B.mark[j] = pos + 1, B.lcam[pos] = j;  // (a list without repeats never reaches size)
+    else if (valid) B.mark[j] = -1;  // localBAKFId_ is set before the test (:459): never a fixed camera
+    base += total;
+  }
+  if (tid == 0) B.rec[kBaNLocal] = base;
+}
+
+// entry x = (list position, feature) of the local cameras: does it hold the FIRST occurrence of its id (:480-499)?  The keys of
+// an id ascend in (key-frame, feature); an occurrence at a smaller (list position, entry) ends the walk (local_map.hip's test)
+__device__ __forceinline__ bool ba_first(const WinArgs &A, int x, int n_local, int &k, int &i, int &id, unsigned &e) {
+  const int NK = A.S.NK, size = A.S.size;
+  if (x >= n_local * NK) return false;
+  const int j = x / NK;
+  i = x - j * NK, k = A.B.lcam[j];
+  if (i >= n_features(A.S, k) || !(kf_sec<uint8_t>(A.S, k, A.S.o_flags)[i] & 1)) return false;
+  id = kf_sec<int>(A.S, k, A.S.o_ids)[i];
+  if (id < 0) return false;
+  e = (unsigned)k * (unsigned)NK + (unsigned)i;
+  const int own = j + 1;
+  for (int s = max(A.O.run[e], 0); s < A.O.n_keys && (int)(A.O.keys[s] >> 32) == id; s++) {
+    const unsigned ee = (unsigned)(A.O.keys[s] & 0xffffffffu);
+    const int kk = (int)(ee / (unsigned)NK);
+    if (kk >= size) continue;
+    const int p = A.B.mark[kk];
+    if (p > 0 && (p < own || (p == own && ee < e))) return false;
+  }
+  return true;
+}
+
+__global__ __launch_bounds__(256) void k_ba_count(WinArgs A) {
+  int cnt = 0;
+  if (A.B.rec[kBaStatus] == kOk) {
+    int k, i, id;
+    unsigned e;
+    cnt = __syncthreads_count(ba_first(A, blockIdx.x * 256 + threadIdx.x, A.B.rec[kBaNLocal], k, i, id, e));
+  }
+  if (threadIdx.x == 0) A.B.blk[blockIdx.x] = cnt;
+}
+
+// ---- 2. points (:465-500), and per point the holder walk of :502-528 / :555-591 for counts and fixed marks
+__global__ __launch_bounds__(256) void k_ba_points(WinArgs A) {
+  __shared__ int s_w[4], s_sum[256];
+  const KfBaView &B = A.B;
+  if (B.rec[kBaStatus] != kOk) return;  // (uniform)
+  const int tid = threadIdx.x, b = blockIdx.x, NK = A.S.NK, size = A.S.size;
+  int part = 0;
+  for (int t = tid; t < b; t += 256) part += B.blk[t];
+  s_sum[tid] = part;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (tid < w) s_sum[tid] += s_sum[tid + w];
+    __syncthreads();
+  }
+  const int base = s_sum[0];
+  int k = 0, i = 0, id = -1;
+  unsigned e = 0;
+  const bool first = B.blk[b] > 0 && ba_first(A, b * 256 + tid, B.rec[kBaNLocal], k, i, id, e);
+  int total;
+  const int q = base + block_rank(first, s_w, &total);
+  if (first) {
+    int n_edges = 0, n_dropped = 0;
+    obs_run_holders(
+        A.O, NK, size, A.O.run[e], id, [](int, unsigned) { return true; },
+        [&](int kk, int) {
+          const int m = B.mark[kk];
+          if (m > 0) n_edges++;
+          else if (m == 0 && !kf_bad(A.S, kk)) B.fixm[kk] = 1, n_edges++;  // (:512-525; every writer writes 1)
+          else n_dropped++;  // a bad holder has no pose block (:561 would dereference null)
+          return true;
+        });
+    if (q < B.max_points) {
+      const double *P = kf_sec<double>(A.S, k, A.S.o_points) + 3 * (size_t)i;
+      B.pt_id[q] = id, B.pt_ne[q] = n_edges;
+      B.points[3 * (size_t)q] = P[0], B.points[3 * (size_t)q + 1] = P[1], B.points[3 * (size_t)q + 2] = P[2];
+    }
+    if (n_edges) atomicAdd(B.rec + kBaNEdges, n_edges);
+    if (n_dropped) atomicAdd(B.rec + kBaNDropped, n_dropped);
+  }
+  if (b == (int)gridDim.x - 1 && tid == 0) B.rec[kBaNPoints] = base + total;
+}
+
+// ---- 3. fixed cameras (:502-528), capacities, 5. poses, and the edge offsets
+__global__ __launch_bounds__(1024) void k_ba_layout(WinArgs A) {
+  __shared__ int s_w[16], s_scan[1024];
+  const KfBaView &B = A.B;
+  if (B.rec[kBaStatus] != kOk) return;  // (uniform, like every return below)
+  const int tid = threadIdx.x, size = A.S.size;
+  const int n_local = B.rec[kBaNLocal], n_points = B.rec[kBaNPoints], n_edges = B.rec[kBaNEdges];
+  for (int c = tid; c < min(n_local, B.max_cams); c += 1024) B.cam_kf[c] = B.lcam[c];
+  int base = n_local;
+  for (int k0 = 0; k0 < size; k0 += 1024) {
+    const int k = k0 + tid;
+    const bool f = k < size && B.fixm[k] != 0;
+    int total;
+    const int pos = base + block_rank(f, s_w, &total);
+    if (f) {
+      B.mark[k] = pos + 1;
+      if (pos < B.max_cams) B.cam_kf[pos] = k;
+    }
+    base += total;
+  }
+  const int n_cams = base;
+  if (tid == 0) B.rec[kBaNCams] = n_cams, B.rec[kBaNFixed] = n_cams - n_local;
+  if (n_cams > B.max_cams || n_points > B.max_points || n_edges > B.max_edges) {  // nothing is truncated: the counts are true
+    if (tid == 0) B.rec[kBaStatus] = kOverflow, atomicOr(A.C.status, (int)VO_KFSTORE_LOCAL_BA_CAPACITY);
+    return;
+  }
+  __syncthreads();  // cam_kf is complete
+  int no_pose = 0;
+  for (int c = tid; c < n_cams; c += 1024) {
+    const int k = B.cam_kf[c];
+    B.cam_fixed[c] = (c >= n_local || k == 0) ? 1 : 0;  // (:578)
+    if (!*np_pose_set(A.M, k)) {
+      no_pose = 1;
+      continue;
+    }
+    const double *T = np_pose(A.M, k);
+    ba::se3_log_from_R(T, T + 9, B.poses6 + 6 * (size_t)c);
+  }
+  if (__syncthreads_or(no_pose)) {
+    if (tid == 0) {
+      for (int r = kBaNCams; r <= kBaNDropped; r++) B.rec[r] = 0;
+      B.rec[kBaStatus] = kEmpty, atomicOr(A.C.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
+    }
+    return;
+  }
+  // pt_ne: counts -> exclusive offsets, pt_ne[n_points] = n_edges
+  int carry = 0;
+  for (int p0 = 0; p0 < n_points; p0 += 1024) {
+    const int p = p0 + tid, v = p < n_points ? B.pt_ne[p] : 0;
+    s_scan[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < 1024; d <<= 1) {
+      const int add = tid >= d ? s_scan[tid - d] : 0;
+      __syncthreads();
+      s_scan[tid] += add;
+      __syncthreads();
+    }
+    if (p < n_points) B.pt_ne[p] = carry + s_scan[tid] - v;
+    carry += s_scan[1023];
+    __syncthreads();
+  }
+  if (tid == 0) B.pt_ne[n_points] = n_edges;
+}
+
+// ---- 4. edges (:550-592)
+__global__ __launch_bounds__(256) void k_ba_edges(WinArgs A) {
+  const KfBaView &B = A.B;
+  if (B.rec[kBaStatus] != kOk) return;
+  const int j = blockIdx.x * 256 + threadIdx.x;
+  if (j >= B.rec[kBaNPoints]) return;
+  const int id = B.pt_id[j];
+  int at = B.pt_ne[j];
+  obs_run_holders(
+      A.O, A.S.NK, A.S.size, obs_lower_bound(A.O, id), id, [](int, unsigned) { return true; },
+      [&](int kk, int f) {
+        const int c = B.mark[kk];
+        if (c <= 0) return true;
+        const size_t d = (size_t)at++;
+        B.e_cam[d] = c - 1, B.e_pt[d] = j, B.e_feat[d] = f;
+        B.e_obs[3 * d] = (double)np_x(A.M, kk)[f], B.e_obs[3 * d + 1] = (double)np_y(A.M, kk)[f];
+        B.e_obs[3 * d + 2] = (double)cull_uright(A.X, kk)[f];
+        B.e_isg[d] = __ddiv_rn(1.0, (double)A.M.sf[min(max(cull_octave(A.X, kk)[f], 0), 15)]);  // (:564)
+        return true;
+      });
+}
+
+struct ApplyArgs {
+  KfStoreView S;
+  KfObsView O;
+  KfCullView X;
+  KfMapView M;
+  KfBaView B;
+  double *normals;
+  int *status;
+  int n_cams, n_points, n_edges;
+};
+
+// ---- a. erased edges, b. point death, c. poses (:760-791)
+__global__ __launch_bounds__(256) void k_ba_erase(ApplyArgs A) {
+  const KfBaView &B = A.B;
+  const int t = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK, size = A.S.size;
+  if (t < A.n_cams && !B.cam_fixed[t]) {
+    const double *src = reinterpret_cast<const double *>(B.in) + 12 * (size_t)t;
+    double *dst = np_pose(A.M, B.cam_kf[t]);
+    for (int c = 0; c < 12; c++) dst[c] = src[c];
+  }
+  if (t >= A.n_points) return;
+  const uint8_t *erase = B.in + (size_t)A.n_cams * 96 + (size_t)A.n_points * 24;
+  const int id = B.pt_id[t], end = B.pt_ne[t + 1], start = obs_lower_bound(A.O, id);
+  int ei = B.pt_ne[t], prev = -1, left = 0, n_erased = 0, n_f0 = 0;
+  // the point's edges and its keys both ascend in key-frame number: one merge.  Bit 0 goes in EVERY feature of an erased
+  // edge's key-frame that carries the id (the store has one fact where the reference has two: no Q-B3, and a second feature
+  // does not turn the key-frame back into a holder)
+  obs_run_each(A.O, start, id, [&](unsigned e) {
+    const int kk = (int)(e / (unsigned)NK);
+    if (kk >= size) return true;
+    while (ei < end && B.cam_kf[B.e_cam[ei]] < kk) ei++;
+    if (ei < end && B.cam_kf[B.e_cam[ei]] == kk && erase[ei]) {
+      uint8_t *fb = flag_byte(A.S, e);
+      *fb = (uint8_t)(*fb & ~1);
+      if (kk != prev) n_erased++, n_f0 += e - (unsigned)kk * (unsigned)NK == 0u;
+    } else if (kk != prev) {
+      left += cull_uright(A.X, kk)[e - (unsigned)kk * (unsigned)NK] >= 0.f ? 2 : 1;  // observe_cnt_ of what remains
+    }
+    prev = kk;
+    return true;
+  });
+  const bool dies = n_erased > 0 && left <= 2;  // (mappoint.cpp:353: only an erase looks at the count)
+  B.dead[t] = dies ? 1 : 0;
+  if (dies)  // eraseMapPoint (mappoint.cpp:362-381), as section 4i does: bit 0 in every feature that carries the id
+    obs_run_each(A.O, start, id, [&](unsigned e) {
+      if ((int)(e / (unsigned)NK) < size) {
+        uint8_t *fb = flag_byte(A.S, e);
+        *fb = (uint8_t)(*fb & ~1);
+      }
+      return true;
+    });
+  if (n_erased) atomicAdd(B.rec + kBaNErased, n_erased);
+  if (n_f0) atomicAdd(B.rec + kBaNFeature0, n_f0);
+  if (dies) atomicAdd(B.rec + kBaNDead, 1);
+}
+
+// ---- d. points (:793-803) and MapPoint::updateNormalAndDepth (mappoint.cpp:66-116) for the n ids of `ids`; new_pos: [n][3]
+// or NULL (the position is the store's row at the id's first live key); dead: [n] or NULL.  The index may be older than the
+// flags: a key is live iff its flags byte has bit 0 now.
+__global__ __launch_bounds__(256) void k_ba_refresh(ApplyArgs A, int n, const int *ids, const double *new_pos, const uint8_t *dead) {
+  const int t = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK, size = A.S.size;
+  if (t >= n || (dead && dead[t])) return;  // dead points are not refreshed, rows of cleared features keep their bytes
+  const int id = ids[t], start = obs_lower_bound(A.O, id);
+  auto live = [&](int kk, unsigned e) { return !A.X.erased[kk] && (*flag_byte(A.S, e) & 1); };
+  double p[3] = {0, 0, 0}, sum[3] = {0, 0, 0};
+  if (new_pos) p[0] = new_pos[3 * (size_t)t], p[1] = new_pos[3 * (size_t)t + 1], p[2] = new_pos[3 * (size_t)t + 2];
+  int r0 = -2, lowest = -1, cnt = 0;
+  bool r0_holds = false, no_pose = false;
+  double len_r0 = -1, len_low = -1;  // |p - Ow| of the two reference candidates (< 0: without a pose)
+  int oct_r0 = 0, oct_low = 0;
+  obs_run_holders(A.O, NK, size, start, id, live, [&](int kk, int f) {
+    if (r0 == -2) {  // the first live key
+      r0 = A.B.ref_kf[(size_t)kk * NK + f], lowest = kk;
+      if (!new_pos) {
+        const double *P = kf_sec<double>(A.S, kk, A.S.o_points) + 3 * (size_t)f;
+        p[0] = P[0], p[1] = P[1], p[2] = P[2];
+      }
+    }
+    double len = -1;
+    if (*np_pose_set(A.M, kk)) {
+      double Ow[3], d[3];
+      np_center(np_pose(A.M, kk), Ow);
+      for (int c = 0; c < 3; c++) d[c] = __dadd_rn(p[c], -Ow[c]);
+      len = __dsqrt_rn(np_dot3(d[0], d[0], d[1], d[1], d[2], d[2]));
+      for (int c = 0; c < 3; c++) sum[c] = __dadd_rn(sum[c], __ddiv_rn(d[c], len));
+      cnt++;
+    } else {
+      no_pose = true;
+    }
+    const int oct = min(max(cull_octave(A.X, kk)[f], 0), 15);
+    if (kk == lowest) len_low = len, oct_low = oct;
+    if (kk == r0) r0_holds = true, len_r0 = len, oct_r0 = oct;
+    return true;
+  });
+  if (no_pose) atomicOr(A.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
+  if (lowest < 0) return;  // no holder: nothing to write
+  const int ref = r0_holds ? r0 : lowest;  // (mappoint.cpp:350-351 under the ascending rule)
+  const double len_ref = r0_holds ? len_r0 : len_low;
+  const bool has_dist = len_ref >= 0, has_normal = cnt > 0;
+  float maxd = 0.f, mind = 0.f;
+  if (has_dist) {
+    maxd = (float)len_ref * A.M.sf[r0_holds ? oct_r0 : oct_low];
+    mind = maxd / A.M.sf[min(max(A.M.n_levels - 1, 0), 15)];
+  }
+  double nrm[3] = {0, 0, 0};
+  if (has_normal)
+    for (int c = 0; c < 3; c++) nrm[c] = __ddiv_rn(sum[c], (double)cnt);
+  obs_run_each(A.O, start, id, [&](unsigned e) {
+    const int kk = (int)(e / (unsigned)NK);
+    if (kk >= size || !live(kk, e)) return true;
+    const int f = (int)(e - (unsigned)kk * (unsigned)NK);
+    uint8_t *r = const_cast<uint8_t *>(A.S.base) + (size_t)kk * A.S.rec;
+    if (new_pos) {
+      double *pt = reinterpret_cast<double *>(r + A.S.o_points) + 3 * (size_t)f;
+      pt[0] = p[0], pt[1] = p[1], pt[2] = p[2];
+    }
+    A.B.ref_kf[(size_t)kk * NK + f] = ref;
+    if (has_normal) {
+      double *nv = A.normals + ((size_t)kk * NK + f) * 3;
+      nv[0] = nrm[0], nv[1] = nrm[1], nv[2] = nrm[2];
+    }
+    if (has_dist) reinterpret_cast<float *>(r + A.S.o_mind)[f] = mind, reinterpret_cast<float *>(r + A.S.o_maxd)[f] = maxd;
+    return true;
+  });
+}
+
+__global__ void k_ba_init(KfBaView B) {
+  if (threadIdx.x < kBaRecInts) B.rec[threadIdx.x] = threadIdx.x == kBaStatus ? (int)kEmpty : 0;
+}
+
+}  // namespace
+
+namespace vo {
+
+size_t ba_store_bytes(int max_kf, int NK, int max_cams, int max_points, int max_edges) {
+  BaLayout L{nullptr};
+  KfBaView B{};
+  ba_layout(L, B, max_kf, NK, max_cams, max_points, max_edges);
+  return L.at;
+}
+
+KfBaView ba_store_layout(void *block, int max_kf, int NK, int max_cams, int max_points, int max_edges) {
+  BaLayout L{reinterpret_cast<uint8_t *>(block)};
+  KfBaView B{};
+  ba_layout(L, B, max_kf, NK, max_cams, max_points, max_edges);
+  B.max_cams = max_cams, B.max_points = max_points, B.max_edges = max_edges, B.NK = NK;
+  return B;
+}
+
+int ba_store_init(const KfBaView &B, int max_kf, hipStream_t st) {
+  VO_HIP_CHECK(hipMemsetAsync(B.ref_kf, 0xff, (size_t)max_kf * B.NK * 4, st));  // -1: unknown
+  hipLaunchKernelGGL(k_ba_init, dim3(1), dim3(64), 0, st, B);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int ba_window_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, const KfMapView &M,
+                      const KfBaView &B, int current, hipStream_t st) {
+  WinArgs A{S, O, C, X, M, B, current};
+  const unsigned grid = (unsigned)(((size_t)S.size * S.NK + 255) / 256);  // (the local cameras are at most `size`)
+  hipLaunchKernelGGL(k_ba_cams, dim3(1), dim3(1024), 0, st, A);
+  hipLaunchKernelGGL(k_ba_count, dim3(grid), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(k_ba_points, dim3(grid), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(k_ba_layout, dim3(1), dim3(1024), 0, st, A);
+  hipLaunchKernelGGL(k_ba_edges, dim3((unsigned)((B.max_points + 255) / 256)), dim3(256), 0, st, A);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int ba_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                     double *normals, int *status, int n_cams, int n_points, int n_edges, hipStream_t st) {
+  ApplyArgs A{S, O, X, M, B, normals, status, n_cams, n_points, n_edges};
+  const int n = n_cams > n_points ? n_cams : n_points;
+  hipLaunchKernelGGL(k_ba_erase, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A);
+  if (n_points > 0)
+    hipLaunchKernelGGL(k_ba_refresh, dim3((unsigned)((n_points + 255) / 256)), dim3(256), 0, st, A, n_points, (const int *)B.pt_id,
+                       reinterpret_cast<const double *>(B.in + (size_t)n_cams * 96), (const uint8_t *)B.dead);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                       double *normals, int *status, int n, hipStream_t st) {
+  if (n <= 0) return VO_OK;
+  ApplyArgs A{S, O, X, M, B, normals, status, 0, 0, 0};
+  hipLaunchKernelGGL(k_ba_refresh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, (const int *)B.ids_in,
+                     (const double *)nullptr, (const uint8_t *)nullptr);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+}  // namespace vo

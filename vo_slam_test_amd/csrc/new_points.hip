@@ -161,6 +161,7 @@ struct CreateArgs {
   vo::KfCullView X;
   vo::KfMapView M;
   double *normals;  // [max_kf][NK][3]
+  int *ref_kf;      // [max_kf][NK] MapPoint::keyFrame_ref_ of a store with local BA, else NULL
   int current, step;
 };
 
@@ -246,6 +247,7 @@ __global__ __launch_bounds__(256) void k_np_create(CreateArgs A) {
         reinterpret_cast<float *>(r + A.S.o_mind)[i] = mind, reinterpret_cast<float *>(r + A.S.o_maxd)[i] = maxd;
         double *n = A.normals + ((size_t)k * NK + i) * 3;
         n[0] = nrm[0], n[1] = nrm[1], n[2] = nrm[2];
+        if (A.ref_kf) A.ref_kf[(size_t)k * NK + i] = cur;  // keyFrame_ref_(keyframe) (mappoint.cpp:37)
       }
       M.created[row0 + rank] = make_int4(kf, i1, i2, id);
     }
@@ -297,8 +299,9 @@ int mapping_split_xy(const KfMapView &M, int k, int n, const float *dev_xy, hipS
   return VO_OK;
 }
 
-int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int current, int step, hipStream_t st) {
-  CreateArgs A{S, X, M, normals, current, step};
+int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int *ref_kf, int current, int step,
+              hipStream_t st) {
+  CreateArgs A{S, X, M, normals, ref_kf, current, step};
   hipLaunchKernelGGL(k_np_create, dim3(1), dim3(256), 0, st, A);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;

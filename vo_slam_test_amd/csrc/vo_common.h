@@ -405,7 +405,51 @@ int mapping_split_xy(const KfMapView &M, int k, int n, const float *dev_xy, hipS
 size_t tri_args_bytes();
 int tri_walk_replay(const KfStoreView &S, const KfCullView &X, const KfMapView &M, const int *graph, int *status, int current, int step,
                     hipStream_t st);
-int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int current, int step, hipStream_t st);
+// (ref_kf: the column of a store with local BA, else NULL -- a created point's keyFrame_ref_ is `current`, mappoint.cpp:37)
+int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int *ref_kf, int current, int step,
+              hipStream_t st);
+
+// Local BA from the store (local_ba_store.hip): the window of Optimizer::solveLocalBAPoseAndPoint
+// (optimizer_ceres.cpp:449-592) assembled from the observation index, its write-back (:757-804) and
+// MapPoint::updateNormalAndDepth (mappoint.cpp:66-116).  What vo_kfstore_enable_local_ba allocates, one block: ref_kf
+// [max_kf][NK] (MapPoint::keyFrame_ref_ per feature, -1: unknown); mark / fixm / lcam [max_kf] (camera index + 1 of a
+// key-frame, -1: marked local but bad; "holds a local point without being local"; the local cameras in list order); blk, the
+// first-occurrence count of every workgroup of the point grid; pt_ne [max_points + 1], edges per point, then their exclusive
+// offsets; dead [max_points]; ids_in [max_points], refresh_points' list; the WINDOW, contiguous so that one copy fetches it:
+// rec (kBaRecInts ints: n_cams, n_local, n_fixed, n_points, n_edges, n_dropped, status, current, n_erased, n_feature0, n_dead),
+// cam_kf, cam_fixed, poses6, pt_id, points, e_cam, e_pt, e_feat, e_obs, e_isg; and `in`, the apply's inputs as the one staging
+// copy brings them: Tcw12 per camera | points | erase bytes, packed by the window's counts.
+constexpr int kBaRecInts = 16;
+enum { kBaNCams = 0, kBaNLocal, kBaNFixed, kBaNPoints, kBaNEdges, kBaNDropped, kBaStatus, kBaCurrent, kBaNErased, kBaNFeature0, kBaNDead };
+struct KfBaView {
+  int max_cams, max_points, max_edges, NK;
+  int *ref_kf, *mark, *fixm, *lcam, *blk, *pt_ne, *ids_in;
+  uint8_t *dead;
+  uint8_t *win;
+  size_t win_bytes;
+  int *rec, *cam_kf;
+  uint8_t *cam_fixed;
+  double *poses6;
+  int *pt_id;
+  double *points;
+  int *e_cam, *e_pt, *e_feat;
+  double *e_obs, *e_isg;
+  uint8_t *in;
+  size_t in_bytes;
+};
+size_t ba_store_bytes(int max_kf, int NK, int max_cams, int max_points, int max_edges);
+KfBaView ba_store_layout(void *block, int max_kf, int NK, int max_cams, int max_points, int max_edges);
+int ba_store_init(const KfBaView &B, int max_kf, hipStream_t st);
+// five launches: local cameras, first-occurrence counts, points (with their edge counts and the fixed marks), layout (fixed
+// cameras, capacities, poses, edge offsets), edges
+int ba_window_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, const KfMapView &M,
+                      const KfBaView &B, int current, hipStream_t st);
+// two launches on the inputs in B.in: erase + death (and the poses), then write + refresh
+int ba_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                     double *normals, int *status, int n_cams, int n_points, int n_edges, hipStream_t st);
+// the refresh alone for the n ids in B.ids_in
+int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                       double *normals, int *status, int n, hipStream_t st);
 
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
