@@ -1225,6 +1225,78 @@ int vo_kfstore_local_ba_window_result(vo_kfstore *s, int32_t *record /*[16]*/, i
 int vo_kfstore_local_ba_apply(vo_kfstore *s, const double *poses6, const double *points, const uint8_t *edge_erase);
 int vo_kfstore_refresh_points(vo_kfstore *s, int n, const int32_t *ids);
 int vo_kfstore_get_pose(vo_kfstore *s, int keyframe, double *Tcw12, int32_t *pose_set);
+/* Map-point upkeep on the device: the two steps that open every iteration of LocalMapping::run --
+ * processNewKeyFrame (localMapping.cpp:100-130) and cullingMapPoints (:496-524) -- with MapPoint::computeDescriptor
+ * (mappoint.cpp:118-179) and eraseMapPoint (:362-381), for a caller who inserts with vo_kfstore_insert_dev and keeps no host
+ * copy of ids or flags.  Opt-in and additive: a store without it allocates and behaves as before.  The definitions are section
+ * 4i's (j HOLDS p, j's OBSERVATION of p, obs(p), bad(j)).
+ * enable_point_upkeep(max_recent): valid on an EMPTY store on which vo_kfstore_enable_local_ba has succeeded (the steps use
+ * ref_kf and the refresh), max_recent >= 1; anything else VO_ERR_INVALID.  One device block of
+ *   16 + 6 * up16(4 R) + 64 + up16(12 (R + NK)) + up16(4 (R + NK)) + up16(4 NK)   bytes, R = max_recent, NK = max_features,
+ *   up16(x) = x rounded up to 16:
+ * the head words; the RECENT LIST, addedMapPoints_ (:355, :124) -- id, first_kf (firstAddedIdxofKF_ as a key-frame number),
+ * found, visible (found_cnt_, visible_cnt_; int32) per entry, at most R entries; the record of the last upkeep call (16 ints)
+ * with its erased ids (R) and a cull call's branch per entry (R); and the scratch: a call's id list with its two counter
+ * columns (3 (R + NK)), the overflow list of compute_descriptors (R + NK), process_new_keyframe's candidates (NK).  No
+ * per-point outcome depends on the order of the list; the getter reports ascending id.  Synchronises once.
+ * compute_descriptors(n, ids): a host list, n <= max_recent + max_features (else VO_ERR_CAPACITY), ids >= 0 (else
+ * VO_ERR_INVALID); one copy, one synchronisation at the end.  compute_descriptors_dev(n, dev_ids): the same bound on n; a
+ * negative id is skipped; ENQUEUED only -- the index rebuilt first when stale, a 4-byte memset and two launches; no host
+ * synchronisation, no device-to-host copy, no allocation; the list must stay untouched until the stream has passed the call.
+ * Per id p: desp = the `desc` rows of p's holders in ascending key-frame number, each at its observation, holders with
+ * bad(j) left out (:138).  desp empty (no holder, or every holder bad): nothing changes (:131, :142).  Otherwise the winner
+ * is the FIRST row with the strictly smallest median, the median being entry int(0.5 * (N - 1)) of the sorted row of Hamming
+ * distances, diagonal 0 included (:160-173; vo_median_descriptor's rule).  Its 32 bytes go to point_desc of every live
+ * feature that carries p, in every non-erased key-frame (bad ones included), as vo_kfstore_refresh_points writes normals.
+ * Repeated ids give the same bytes.  A point with more than VO_KFSTORE_DESC_MAX_HOLDERS non-bad holders keeps its descriptor
+ * and raises the sticky VO_KFSTORE_UPKEEP_CAPACITY (read and cleared by vo_kfstore_connections_status).
+ * process_new_keyframe(current): for the key-frame just inserted (computeBow, :108, and map_->insertKeyFrame, :129, are the
+ * insert).  current in [0, size) is validated; the rest is ENQUEUED (index rebuild when stale, classify, refresh, descriptors,
+ * append, vo_kfstore_update_connections_dev's launches for `current`, :128): no host synchronisation, no copy back, no
+ * allocation.  current erased: nothing changes, the sticky VO_KFSTORE_CONNECTIONS_INVALID is raised.  Every id p that current
+ * holds is handled once, at current's observation of it:
+ *  - TRACKED, another non-erased key-frame holds p (the !beObserved branch, :116-121; the store has one fact where the
+ *    reference has mappoints_[i] and observedKFs_, so addObservation is the insert): p is refreshed as by
+ *    vo_kfstore_refresh_points and gets compute_descriptors, over its holders, current included;
+ *  - CREATED WITH THE KEY-FRAME, only current holds p (createNewKeyFrame's stereo points, visualOdometry.cpp:496-503): p is
+ *    appended to the recent list with first_kf = current, found = visible = 1 (mappoint.cpp:38-41), unless listed already
+ *    (the call is idempotent).
+ *  The split by holders is this restatement's; it differs from a pointer model for a tracked point whose other holders have
+ *  all been erased (here: created-with).  If the appends would exceed max_recent NONE is made, VO_KFSTORE_UPKEEP_CAPACITY is
+ *  raised, the record holds the true count, and the refreshes and the connection update still happen.
+ * vo_kfstore_create_map_points on a store with upkeep enqueues one more launch: the ids of its created rows are appended
+ * (addedMapPoints_.push_back, :355) with first_kf = current, found = visible = 1, under the same capacity rule.
+ * add_point_stats(n, ids, visible, found): host lists, n <= max_recent + max_features, increments >= 0 (else VO_ERR_INVALID);
+ * one copy, one synchronisation.  add_point_stats_dev: ENQUEUED only (one launch).  visible[i] / found[i] are added to the
+ * entry of ids[i]; a negative id is skipped, an id without an entry ignored (getFoundRatio's only caller is :509), repeats
+ * accumulate.
+ * cull_map_points(current): current in [0, size) validated; ENQUEUED (index rebuild when stale, two launches).  Per entry, in
+ * the reference's branch order:
+ *  1 no non-erased key-frame holds the id (isBad()): the entry leaves the list;
+ *  2 (float)found / (float)visible < 0.25f (a correctly rounded float division, compared in float): eraseMapPoint, leaves;
+ *  3 current > first_kf + 2 && obs(p) <= 3: eraseMapPoint, leaves;
+ *  4 current > first_kf + 3: leaves, the point lives;
+ *  5 otherwise the entry stays.
+ * eraseMapPoint clears bit 0 in EVERY feature that carries the id, in every non-erased key-frame; rows keep their other
+ * bytes; connection weights do not change.  Afterwards the index is stale and the generation word has advanced.
+ * recent_points(n, ids, first_kf, found, visible) and upkeep_result(record, erased_ids) synchronise; any pointer may be NULL;
+ * arrays of max_recent entries.  record [16] = kind (VO_KFSTORE_UPKEEP_*), current, n_tracked, n_new (the appends the call
+ * wanted), n_appended, then of a cull call the counts of branches 1 .. 5 and n_erased (branches 2 + 3, the length of
+ * erased_ids, ascending), the list's length after the call, four zeros. */
+#define VO_KFSTORE_UPKEEP_CAPACITY 8
+#define VO_KFSTORE_DESC_MAX_HOLDERS 1024
+#define VO_KFSTORE_UPKEEP_PROCESS 1
+#define VO_KFSTORE_UPKEEP_CULL 2
+#define VO_KFSTORE_UPKEEP_CREATED 3
+int vo_kfstore_enable_point_upkeep(vo_kfstore *s, int max_recent);
+int vo_kfstore_compute_descriptors(vo_kfstore *s, int n, const int32_t *ids);
+int vo_kfstore_compute_descriptors_dev(vo_kfstore *s, int n, const int32_t *dev_ids);
+int vo_kfstore_process_new_keyframe(vo_kfstore *s, int current);
+int vo_kfstore_add_point_stats(vo_kfstore *s, int n, const int32_t *ids, const int32_t *visible, const int32_t *found);
+int vo_kfstore_add_point_stats_dev(vo_kfstore *s, int n, const int32_t *dev_ids, const int32_t *dev_visible, const int32_t *dev_found);
+int vo_kfstore_cull_map_points(vo_kfstore *s, int current);
+int vo_kfstore_recent_points(vo_kfstore *s, int32_t *n, int32_t *ids, int32_t *first_kf, int32_t *found, int32_t *visible);
+int vo_kfstore_upkeep_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *erased_ids);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

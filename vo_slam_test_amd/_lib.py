@@ -64,6 +64,9 @@ SYMBOLS = [
     "vo_kfstore_enable_local_ba", "vo_kfstore_set_point_refs", "vo_kfstore_set_point_refs_dev", "vo_kfstore_get_point_refs",
     "vo_kfstore_local_ba_window", "vo_kfstore_local_ba_window_result", "vo_kfstore_local_ba_apply", "vo_kfstore_refresh_points",
     "vo_kfstore_get_pose", "vo_kfstore_local_ba",
+    "vo_kfstore_enable_point_upkeep", "vo_kfstore_compute_descriptors", "vo_kfstore_compute_descriptors_dev",
+    "vo_kfstore_process_new_keyframe", "vo_kfstore_add_point_stats", "vo_kfstore_add_point_stats_dev", "vo_kfstore_cull_map_points",
+    "vo_kfstore_recent_points", "vo_kfstore_upkeep_result",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1849,6 +1852,66 @@ class KeyFrameStore:
         if rc not in (0, -5):
             check(rc, "vo_kfstore_local_ba")
         return sums, rc
+
+    CONNECTIONS_UPKEEP_CAPACITY = 8
+    DESC_MAX_HOLDERS = 1024
+    UPKEEP_PROCESS, UPKEEP_CULL, UPKEEP_CREATED = 1, 2, 3
+    UPKEEP_RECORD = ("kind", "current", "n_tracked", "n_new", "n_appended", "n_dead", "n_ratio", "n_few_obs", "n_matured", "n_kept",
+                     "n_erased", "n_recent")
+
+    def enable_point_upkeep(self, max_recent):
+        """processNewKeyFrame / cullingMapPoints on the device from now on; valid on an empty store after
+        enable_local_ba only.  max_recent: the entries addedMapPoints_ may hold"""
+        check(lib().vo_kfstore_enable_point_upkeep(self._h, int(max_recent)), "vo_kfstore_enable_point_upkeep")
+        self._max_recent = int(max_recent)
+
+    def compute_descriptors(self, ids):
+        """MapPoint::computeDescriptor for the listed map-point ids.  A list / numpy array is validated, copied and synchronises
+        once; a device tensor (int32; negative entries are skipped) is enqueued only"""
+        if hasattr(ids, "data_ptr"):
+            _need_tensor(ids, "int32", None, "compute_descriptors")
+            check(lib().vo_kfstore_compute_descriptors_dev(self._h, int(ids.numel()), _p(ids)), "vo_kfstore_compute_descriptors_dev")
+            return
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        check(lib().vo_kfstore_compute_descriptors(self._h, len(a), _p(a)), "vo_kfstore_compute_descriptors")
+
+    def process_new_keyframe(self, current):
+        """LocalMapping::processNewKeyFrame for the key-frame just inserted; enqueued only"""
+        check(lib().vo_kfstore_process_new_keyframe(self._h, int(current)), "vo_kfstore_process_new_keyframe")
+
+    def add_point_stats(self, ids, visible, found):
+        """visible_cnt_ / found_cnt_ of the listed recent points grown by the increments.  Lists / numpy arrays are validated,
+        copied and synchronise once; device tensors (int32, all three) are enqueued only"""
+        if hasattr(ids, "data_ptr"):
+            n = int(ids.numel())
+            for t in (ids, visible, found):
+                _need_tensor(t, "int32", n, "add_point_stats")
+            check(lib().vo_kfstore_add_point_stats_dev(self._h, n, _p(ids), _p(visible), _p(found)), "vo_kfstore_add_point_stats_dev")
+            return
+        a, v, f = (np.ascontiguousarray(x, np.int32).reshape(-1) for x in (ids, visible, found))
+        if not len(a) == len(v) == len(f):
+            raise VoError("add_point_stats: ids, visible and found differ in length")
+        check(lib().vo_kfstore_add_point_stats(self._h, len(a), _p(a), _p(v), _p(f)), "vo_kfstore_add_point_stats")
+
+    def cull_map_points(self, current):
+        """LocalMapping::cullingMapPoints for the current key-frame; enqueued only"""
+        check(lib().vo_kfstore_cull_map_points(self._h, int(current)), "vo_kfstore_cull_map_points")
+
+    def recent_points(self):
+        """addedMapPoints_ -> [(id, first_kf, found, visible)] in ascending id; synchronises"""
+        r = getattr(self, "_max_recent", 1)
+        cols = [np.zeros(r, np.int32) for _ in range(4)]
+        n = C.c_int32(0)
+        check(lib().vo_kfstore_recent_points(self._h, C.byref(n), *(_p(c) for c in cols)), "vo_kfstore_recent_points")
+        return [tuple(int(c[i]) for c in cols) for i in range(n.value)]
+
+    def upkeep_result(self):
+        """the last upkeep call -> dict over UPKEEP_RECORD plus erased (the ids a cull call erased, ascending); synchronises"""
+        rec, er = np.zeros(16, np.int32), np.zeros(getattr(self, "_max_recent", 1), np.int32)
+        check(lib().vo_kfstore_upkeep_result(self._h, _p(rec), _p(er)), "vo_kfstore_upkeep_result")
+        out = {k: int(rec[i]) for i, k in enumerate(self.UPKEEP_RECORD)}
+        out["erased"] = [int(x) for x in er[:out["n_erased"] if out["kind"] == self.UPKEEP_CULL else 0]]
+        return out
 
 
 def rgb_to_gray(img, first_is_red=True):

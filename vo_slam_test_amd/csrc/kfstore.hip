@@ -114,6 +114,10 @@ struct vo_kfstore {
   int32_t ba_rec[vo::kBaRecInts] = {0};
   std::vector<double> ba_poses, ba_points;  // the composed call's solver state (sized by the capacities: no allocation per call)
   std::vector<uint8_t> ba_erase;
+  vo::OwnedDevBuf up;                 // vo_kfstore_enable_point_upkeep: the block of section 4l
+  vo::OwnedPinnedBuf up_stage;        // a host form's lists going up: one copy
+  vo::KfUpkeepView U{};
+  bool upkeep = false;
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -223,6 +227,12 @@ int need_mapping(const vo_kfstore *s, const char *call) {
 int need_local_ba(const vo_kfstore *s, const char *call) {
   if (s && s->local_ba) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_local_ba has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_upkeep(const vo_kfstore *s, const char *call) {
+  if (s && s->upkeep) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_point_upkeep has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -753,6 +763,7 @@ int vo_kfstore_create_map_points(vo_kfstore *s, int current, int max_neighbors) 
     VO_CHECK(vo::np_create(V, s->X, s->M, s->normals.as<double>(), s->local_ba ? s->B.ref_kf : nullptr, current, i, s->st));
   }
   s->obs_dirty = true, s->gen++;  // (whether anything was created only the device knows)
+  if (s->upkeep) VO_CHECK(vo::upkeep_created_enqueue(s->M, s->U, C.status, current, s->st));  // addedMapPoints_.push_back (:355)
   return VO_OK;
 }
 
@@ -1055,6 +1066,156 @@ int vo_kfstore_get_connections(vo_kfstore *s, int keyframe, int32_t *n_connected
   if (keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
   return vo::connections_get(s->conn, s->size, keyframe, s->st, n_connected, weights, n_ordered, ordered, ordered_weights, parent,
                              n_children, children);
+}
+
+int vo_kfstore_enable_point_upkeep(vo_kfstore *s, int max_recent) {
+  const char *W = "vo_kfstore_enable_point_upkeep";
+  VO_CHECK(need_local_ba(s, W));
+  if (max_recent < 1) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->upkeep) return VO_OK;
+  VO_CHECK(s->up.reserve(vo::upkeep_bytes(max_recent, s->NK)));
+  s->U = vo::upkeep_layout(s->up.p, max_recent, s->NK);
+  VO_CHECK(s->up_stage.reserve((size_t)s->U.L * 12));
+  VO_CHECK(vo::connections_reserve(s->conn, 1, nullptr));  // process_new_keyframe's update of one key-frame allocates nothing
+  VO_CHECK(vo::upkeep_init(s->U, s->st));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  s->upkeep = true;
+  return VO_OK;
+}
+
+int vo_kfstore_compute_descriptors_dev(vo_kfstore *s, int n, const int32_t *dev_ids) {
+  const char *W = "vo_kfstore_compute_descriptors_dev";
+  VO_CHECK(need_upkeep(s, W));
+  if (n < 0 || (n > 0 && !dev_ids)) return VO_ERR_INVALID;
+  if (n > s->U.L) {
+    vo::set_error("%s: %d ids, the store takes %d (max_recent + max_features)", W, n, s->U.L);
+    return VO_ERR_CAPACITY;
+  }
+  if (n == 0) return VO_OK;
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return vo::upkeep_descriptors_enqueue(vo::kfstore_view(s), O, s->U, vo::connections_view(s->conn).status, n, dev_ids, s->st);
+}
+
+int vo_kfstore_compute_descriptors(vo_kfstore *s, int n, const int32_t *ids) {
+  const char *W = "vo_kfstore_compute_descriptors";
+  VO_CHECK(need_upkeep(s, W));
+  if (n < 0 || (n > 0 && !ids)) return VO_ERR_INVALID;
+  if (n > s->U.L) {
+    vo::set_error("%s: %d ids, the store takes %d (max_recent + max_features)", W, n, s->U.L);
+    return VO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0) {
+      vo::set_error("%s: entry %d: id %d is negative", W, i, ids[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  memcpy(s->up_stage.data(), ids, (size_t)n * 4);
+  VO_CHECK(vo::copy_h2d(s->U.list, s->up_stage.data(), (size_t)n * 4, s->st, W));
+  VO_CHECK(vo_kfstore_compute_descriptors_dev(s, n, s->U.list));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_process_new_keyframe(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_process_new_keyframe";
+  VO_CHECK(need_upkeep(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has been erased only the device knows: nothing is then listed, and the sticky INVALID is raised)
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  const vo::KfStoreView V = vo::kfstore_view(s);
+  VO_CHECK(vo::upkeep_process_enqueue(V, O, s->X, s->M, s->B, s->U, s->normals.as<double>(), vo::connections_view(s->conn).status, current,
+                                      s->st));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return vo::connections_update(s->conn, V, O, 1, s->U.head + 2, s->st);  // keyframe_curr_->updateConnections() (:128)
+}
+
+int vo_kfstore_add_point_stats_dev(vo_kfstore *s, int n, const int32_t *dev_ids, const int32_t *dev_visible, const int32_t *dev_found) {
+  const char *W = "vo_kfstore_add_point_stats_dev";
+  VO_CHECK(need_upkeep(s, W));
+  if (n < 0 || (n > 0 && (!dev_ids || !dev_visible || !dev_found))) return VO_ERR_INVALID;
+  s->gen++;
+  return vo::upkeep_stats_enqueue(s->U, n, dev_ids, dev_visible, dev_found, s->st);
+}
+
+int vo_kfstore_add_point_stats(vo_kfstore *s, int n, const int32_t *ids, const int32_t *visible, const int32_t *found) {
+  const char *W = "vo_kfstore_add_point_stats";
+  VO_CHECK(need_upkeep(s, W));
+  if (n < 0 || (n > 0 && (!ids || !visible || !found))) return VO_ERR_INVALID;
+  if (n > s->U.L) {
+    vo::set_error("%s: %d ids, the store takes %d (max_recent + max_features)", W, n, s->U.L);
+    return VO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; i++)
+    if (visible[i] < 0 || found[i] < 0) {
+      vo::set_error("%s: entry %d: a negative increment (%d visible, %d found)", W, i, visible[i], found[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  // staged as the block's list holds them: ids | visible | found, L entries each; one copy
+  const size_t L = (size_t)s->U.L;
+  int32_t *h = reinterpret_cast<int32_t *>(s->up_stage.data());
+  memset(h, 0xff, L * 4), memset(h + L, 0, L * 8);  // (beyond n: no id, no increment)
+  memcpy(h, ids, (size_t)n * 4), memcpy(h + L, visible, (size_t)n * 4), memcpy(h + 2 * L, found, (size_t)n * 4);
+  VO_CHECK(vo::copy_h2d(s->U.list, h, L * 12, s->st, W));
+  VO_CHECK(vo_kfstore_add_point_stats_dev(s, n, s->U.list, s->U.list + L, s->U.list + 2 * L));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_cull_map_points(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_cull_map_points";
+  VO_CHECK(need_upkeep(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::upkeep_cull_enqueue(vo::kfstore_view(s), O, s->X, s->U, current, s->st));
+  s->obs_dirty = true, s->gen++;  // (whether anything was erased only the device knows)
+  return VO_OK;
+}
+
+int vo_kfstore_recent_points(vo_kfstore *s, int32_t *n, int32_t *ids, int32_t *first_kf, int32_t *found, int32_t *visible) {
+  const char *W = "vo_kfstore_recent_points";
+  VO_CHECK(need_upkeep(s, W));
+  const size_t R = (size_t)s->U.R;
+  std::vector<int32_t> h(4 * R + 4);
+  VO_CHECK(vo::copy_d2h(h.data(), s->U.head, 16, s->st, W));
+  const int32_t *cols[4] = {s->U.id, s->U.first_kf, s->U.found, s->U.visible};
+  for (int c = 0; c < 4; c++) VO_CHECK(vo::copy_d2h(h.data() + 4 + c * R, cols[c], R * 4, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  const int cnt = std::min(std::max(h[0], 0), s->U.R);
+  std::vector<int> order((size_t)cnt);
+  for (int i = 0; i < cnt; i++) order[(size_t)i] = i;
+  const int32_t *id = h.data() + 4;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return id[a] < id[b]; });  // (an id has one entry)
+  int32_t *out[4] = {ids, first_kf, found, visible};
+  for (int c = 0; c < 4; c++)
+    if (out[c])
+      for (int i = 0; i < cnt; i++) out[c][i] = h[4 + c * R + (size_t)order[(size_t)i]];
+  if (n) *n = cnt;
+  return VO_OK;
+}
+
+int vo_kfstore_upkeep_result(vo_kfstore *s, int32_t *record, int32_t *erased_ids) {
+  const char *W = "vo_kfstore_upkeep_result";
+  VO_CHECK(need_upkeep(s, W));
+  int32_t rec[vo::kUpRecInts];
+  std::vector<int32_t> er((size_t)s->U.R);
+  VO_CHECK(vo::copy_d2h(rec, s->U.rec, sizeof(rec), s->st, W));
+  if (erased_ids) VO_CHECK(vo::copy_d2h(er.data(), s->U.erased, er.size() * 4, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  if (record) memcpy(record, rec, sizeof(rec));
+  if (erased_ids) {
+    const int ne = rec[vo::kUpKind] == VO_KFSTORE_UPKEEP_CULL ? std::min(std::max(rec[vo::kUpNErased], 0), s->U.R) : 0;
+    std::sort(er.begin(), er.begin() + ne);
+    memcpy(erased_ids, er.data(), (size_t)ne * 4);
+  }
+  return VO_OK;
 }
 
 }  // extern "C"

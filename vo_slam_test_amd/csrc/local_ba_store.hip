@@ -93,18 +93,6 @@ __device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total) {
   return base + below;
 }
 
-// first key position whose id is >= `id`
-__device__ __forceinline__ int obs_lower_bound(const KfObsView &O, int id) {
-  const unsigned long long first = (unsigned long long)(unsigned)id << 32;
-  int lo = 0, hi = O.n_keys;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (O.keys[mid] < first) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo;
-}
-
 struct WinArgs {
   KfStoreView S;
   KfObsView O;
@@ -366,7 +354,9 @@ __global__ __launch_bounds__(256) void k_ba_erase(ApplyArgs A) {
 __global__ __launch_bounds__(256) void k_ba_refresh(ApplyArgs A, int n, const int *ids, const double *new_pos, const uint8_t *dead) {
   const int t = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK, size = A.S.size;
   if (t >= n || (dead && dead[t])) return;  // dead points are not refreshed, rows of cleared features keep their bytes
-  const int id = ids[t], start = obs_lower_bound(A.O, id);
+  const int id = ids[t];
+  if (id < 0) return;  // (a device list's "no point here": the host forms validate their ids)
+  const int start = obs_lower_bound(A.O, id);
   auto live = [&](int kk, unsigned e) { return !A.X.erased[kk] && (*flag_byte(A.S, e) & 1); };
   double p[3] = {0, 0, 0}, sum[3] = {0, 0, 0};
   if (new_pos) p[0] = new_pos[3 * (size_t)t], p[1] = new_pos[3 * (size_t)t + 1], p[2] = new_pos[3 * (size_t)t + 2];
@@ -491,6 +481,16 @@ int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullVie
   ApplyArgs A{S, O, X, M, B, normals, status, 0, 0, 0};
   hipLaunchKernelGGL(k_ba_refresh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, (const int *)B.ids_in,
                      (const double *)nullptr, (const uint8_t *)nullptr);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int ba_refresh_list_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                            double *normals, int *status, int n, const int *dev_ids, hipStream_t st) {
+  if (n <= 0) return VO_OK;
+  ApplyArgs A{S, O, X, M, B, normals, status, 0, 0, 0};
+  hipLaunchKernelGGL(k_ba_refresh, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A, n, dev_ids, (const double *)nullptr,
+                     (const uint8_t *)nullptr);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }

@@ -1,9 +1,22 @@
 // obs_walk.h -- the walk over one id's run of the observation index (vo_common.h: KfObsView), shared
-// by the kernels that read "who holds this id": k_conn_count (connections.hip) and the culling kernels (cull.hip).
+// by the kernels that read "who holds this id": k_conn_count (connections.hip), the culling kernels (cull.hip), the local-BA
+// window and write-back (local_ba_store.hip) and the map-point upkeep (point_upkeep.hip).
 #pragma once
 #include "vo_common.h"
 
 namespace vo {
+
+// first key position whose id is >= `id` (id >= 0)
+__device__ __forceinline__ int obs_lower_bound(const KfObsView &O, int id) {
+  const unsigned long long first = (unsigned long long)(unsigned)id << 32;
+  int lo = 0, hi = O.n_keys;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (O.keys[mid] < first) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo;
+}
 
 // every key of id's run from position `start` (run[entry] of one of the id's entries) in ascending entry;
 // f(entry) -> false ends the walk

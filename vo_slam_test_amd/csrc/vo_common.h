@@ -450,6 +450,39 @@ int ba_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView 
 // the refresh alone for the n ids in B.ids_in
 int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                        double *normals, int *status, int n, hipStream_t st);
+// the refresh for the n entries of a device list; a negative entry is skipped (point_upkeep.hip's tracked points)
+int ba_refresh_list_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                            double *normals, int *status, int n, const int *dev_ids, hipStream_t st);
+
+// Map-point upkeep on the device (point_upkeep.hip): LocalMapping::processNewKeyFrame,
+// cullingMapPoints, MapPoint::computeDescriptor and eraseMapPoint from the store.  What vo_kfstore_enable_point_upkeep
+// allocates, one block (R = max_recent, L = R + NK, the longest id list a call takes): head [4] (entries in the recent
+// list, ids in the overflow list, the key-frame number process_new_keyframe hands to the connection update, 0); the recent
+// list id / first_kf / found / visible [R] each (addedMapPoints_ with firstAddedIdxofKF_, found_cnt_, visible_cnt_); rec
+// [kUpRecInts] and erased [R], the last call's record and the ids it erased; list [3][L], the id list of a call (the host
+// forms' one copy lands here: ids | visible | found); over [L], the ids whose holders exceed a wavefront; cand [NK], the
+// ids process_new_keyframe may append; outcome [R], a cull call's branch per entry.
+constexpr int kUpRecInts = 16;
+enum { kUpKind = 0, kUpCurrent, kUpNTracked, kUpNNew, kUpNAppended, kUpNDead, kUpNRatio, kUpNFewObs, kUpNMatured, kUpNKept, kUpNErased,
+       kUpNRecent };
+constexpr int kUpDescMaxHolders = VO_KFSTORE_DESC_MAX_HOLDERS;
+struct KfUpkeepView {
+  int R, NK, L;
+  int *head, *id, *first_kf, *found, *visible, *rec, *erased, *list, *over, *cand, *outcome;
+};
+size_t upkeep_bytes(int max_recent, int NK);
+KfUpkeepView upkeep_layout(void *block, int max_recent, int NK);
+int upkeep_init(const KfUpkeepView &U, hipStream_t st);
+// computeDescriptor for the n entries of a device list (negative: skipped): a memset of the overflow count and two launches
+int upkeep_descriptors_enqueue(const KfStoreView &S, const KfObsView &O, const KfUpkeepView &U, int *status, int n, const int *dev_ids,
+                               hipStream_t st);
+// processNewKeyFrame up to the connection update: classify (U.list = the tracked ids, U.cand = the ids to append, per feature
+// of `current`), refresh, descriptors, append
+int upkeep_process_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                           const KfUpkeepView &U, double *normals, int *status, int current, hipStream_t st);
+int upkeep_created_enqueue(const KfMapView &M, const KfUpkeepView &U, int *status, int current, hipStream_t st);
+int upkeep_stats_enqueue(const KfUpkeepView &U, int n, const int *dev_ids, const int *dev_visible, const int *dev_found, hipStream_t st);
+int upkeep_cull_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfUpkeepView &U, int current, hipStream_t st);
 
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
