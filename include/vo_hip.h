@@ -1297,6 +1297,60 @@ int vo_kfstore_add_point_stats_dev(vo_kfstore *s, int n, const int32_t *dev_ids,
 int vo_kfstore_cull_map_points(vo_kfstore *s, int current);
 int vo_kfstore_recent_points(vo_kfstore *s, int32_t *n, int32_t *ids, int32_t *first_kf, int32_t *found, int32_t *visible);
 int vo_kfstore_upkeep_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *erased_ids);
+/* Map-point fusion on the device: LocalMapping::searchInNeighbors (localMapping.cpp:363-432) with
+ * Matcher::fuseMapPoints (matcher.cpp:1012-1133) and MapPoint::replaceMapPoint (mappoint.cpp:214-253) on the store.  Opt-in
+ * and additive: a store without it allocates and behaves as before.  The definitions are section 4i's (j HOLDS p, j's
+ * OBSERVATION of p, obs(p), bad(j)); a map point "isBad" when no key-frame holds it, beObserved(T) means T holds it, and its
+ * ATTRIBUTES are the ones replicated on its carriers, read from the lowest live one: position, normal, min / max distance,
+ * ref_kf, point_desc.
+ * enable_fuse(bounds, max_candidates): valid on an EMPTY store on which vo_kfstore_enable_point_upkeep has succeeded; bounds =
+ * xMin, xMax, yMin, yMax of the undistorted image (xMax > xMin, yMax > yMin), the grid constants are 64 / (xMax - xMin) and
+ * 48 / (yMax - yMin) in float (camera.cpp:47-48); max_candidates >= 1 bounds the candidates of one step and the matches of one
+ * call, each of which reserves one node of the overlay; max_features above 4096 is VO_ERR_CAPACITY (a target's key-points are staged in 64 KB).  One device
+ * block of 16 * index capacity + 28 * max_candidates + 244 * max_features bytes and a little.  Synchronises once.
+ * fuse(T, list, threshold), the reference's loop in list order.  A candidate p is skipped unless: p >= 0; somebody holds it;
+ * T does not; z >= 0 (float) in T's camera; isInImg(u, v) (keyframe.cpp:64-67, float); 0.8f * min <= dist <= 1.2f * max;
+ * line . normal >= 0.5 * dist (double); level = predictScale (mappoint.cpp:198-212, as VO_TRACKER_* projections compute it).
+ * Its window (keyframe.cpp:268-309) holds the features whose ROUNDED cell (frame.cpp:83-86; outside the 64 x 48 grid: none)
+ * lies in the FLOOR-computed cell range of (u, v) +- radius, radius = threshold * scale_factors[level], and that have
+ * |dx| < radius && |dy| < radius.  Of those with octave in [level - 1, level] and chi-square <= 7.815 (u_right >= 0; three
+ * terms) or 5.991 (two), the strictly smallest Hamming distance between the candidate's point_desc and the feature's desc wins
+ * in the order cell column, cell row, feature; a match needs distance <= 50.  Feature EMPTY (bit 0 clear): it gets p, bit 0
+ * and p's attributes.  Feature carries org: obs(org) > obs(p) replaces p by org, otherwise org by p.
+ * replace(A -> B): every holder j of A with observation i: j does not hold B -> feature (j, i) takes B's id and attributes;
+ * else bit 0 of (j, i) is cleared.  Every other feature that carries A loses bit 0 too (a choice of this restatement: the
+ * pointer model leaves a dangling bad pointer there).  When BOTH have an entry in the recent list B's found / visible grow by
+ * A's; A's entry stays (the next cull removes it, branch 1).  Then compute_descriptors(B).
+ * fuse_map_points(target, n, ids, threshold): one fuse call on its own.  target in [0, size), n in [0, 60 * max_features]
+ * (else VO_ERR_CAPACITY), threshold > 0; one copy, one synchronisation at the end.  fuse_map_points_dev: ids in device memory,
+ * ENQUEUED only (the index rebuilt first when stale, one memset, four launches).  target erased or without a pose: nothing
+ * changes, VO_KFSTORE_CONNECTIONS_INVALID.  Afterwards the index is stale and the generation word has advanced.
+ * search_in_neighbors(current): current in [0, size) validated, then ENQUEUED only.  The target list (:365-386): the first
+ * 10 of current's ordered list, bad ones skipped, each followed by its own first 5 without the bad ones, the first neighbours
+ * seen so far and current; only first neighbours are marked, so a key-frame can come several times and is fused several times
+ * (at most 60 targets; the marks are per call, which differs from fuseKFId_ for key-frame id 0 only).  Then fuse(T, current's
+ * ids in feature order as the call found them, 3) per target in list order; fuse(current, the targets' ids by first
+ * occurrence over the target list, 3); compute_descriptors and vo_kfstore_refresh_points for current's live points; the
+ * connection update of current.  The observation index is rebuilt once in front when stale and once before the closing
+ * descriptors, whatever the number of targets; afterwards it is fresh.  current erased or without a pose: only the
+ * connection update runs, VO_KFSTORE_CONNECTIONS_INVALID.
+ * Capacity, three limits on the device: more than max_candidates candidates passing the gates in ONE step leave that step
+ * undone; when the MATCHES of a call (each reserves one overlay node) exceed max_candidates, the step that meets the limit and
+ * every later one are left undone; a replace between points of which one has more than VO_KFSTORE_FUSE_MAX_CARRIERS live
+ * features is left undone.  Each raises the sticky VO_KFSTORE_FUSE_CAPACITY, which vo_kfstore_connections_status reads and
+ * clears with 1 / 2 / 4 / 8; the record of an undone step keeps its candidates and matches.
+ * fuse_result(record, targets, per_target): synchronises; any pointer may be NULL.  record [8] = number of steps, then the
+ * totals of the six columns, 0; targets [61] = the target of every step (the closing step's is current); per_target [61][6] =
+ * candidates that passed the gates, matches, adds, replaces that kept org, replaces that kept the candidate, features
+ * cleared. */
+#define VO_KFSTORE_FUSE_CAPACITY 16
+#define VO_KFSTORE_FUSE_MAX_CARRIERS 1024
+#define VO_KFSTORE_FUSE_MAX_STEPS 61
+int vo_kfstore_enable_fuse(vo_kfstore *s, const float bounds[4] /*xMin xMax yMin yMax*/, int max_candidates);
+int vo_kfstore_fuse_map_points(vo_kfstore *s, int target, int n, const int32_t *ids, float threshold);
+int vo_kfstore_fuse_map_points_dev(vo_kfstore *s, int target, int n, const int32_t *dev_ids, float threshold);
+int vo_kfstore_search_in_neighbors(vo_kfstore *s, int current);
+int vo_kfstore_fuse_result(vo_kfstore *s, int32_t *record /*[8]*/, int32_t *targets /*[61]*/, int32_t *per_target /*[61][6]*/);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

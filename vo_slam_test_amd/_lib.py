@@ -67,6 +67,8 @@ SYMBOLS = [
     "vo_kfstore_enable_point_upkeep", "vo_kfstore_compute_descriptors", "vo_kfstore_compute_descriptors_dev",
     "vo_kfstore_process_new_keyframe", "vo_kfstore_add_point_stats", "vo_kfstore_add_point_stats_dev", "vo_kfstore_cull_map_points",
     "vo_kfstore_recent_points", "vo_kfstore_upkeep_result",
+    "vo_kfstore_enable_fuse", "vo_kfstore_fuse_map_points", "vo_kfstore_fuse_map_points_dev", "vo_kfstore_search_in_neighbors",
+    "vo_kfstore_fuse_result",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1912,6 +1914,41 @@ class KeyFrameStore:
         out = {k: int(rec[i]) for i, k in enumerate(self.UPKEEP_RECORD)}
         out["erased"] = [int(x) for x in er[:out["n_erased"] if out["kind"] == self.UPKEEP_CULL else 0]]
         return out
+
+    CONNECTIONS_FUSE_CAPACITY = 16
+    FUSE_MAX_CARRIERS, FUSE_MAX_STEPS = 1024, 61
+    FUSE_COLUMNS = ("passed", "matches", "adds", "kept_org", "kept_candidate", "cleared")
+
+    def enable_fuse(self, bounds, max_candidates):
+        """searchInNeighbors / fuseMapPoints on the device from now on; valid on an empty store after
+        enable_point_upkeep only.  bounds: xMin, xMax, yMin, yMax of the undistorted image; max_candidates: the matches a call
+        may make"""
+        b = np.ascontiguousarray(bounds, np.float32).reshape(4)
+        check(lib().vo_kfstore_enable_fuse(self._h, _p(b), int(max_candidates)), "vo_kfstore_enable_fuse")
+
+    def fuse_map_points(self, target, ids, threshold=3.0):
+        """Matcher::fuseMapPoints(target, ids, threshold): one fuse call on its own.  A list / numpy array is copied and
+        synchronises once; a device tensor (int32; negative entries are skipped) is enqueued only"""
+        if hasattr(ids, "data_ptr"):
+            _need_tensor(ids, "int32", None, "fuse_map_points")
+            check(lib().vo_kfstore_fuse_map_points_dev(self._h, int(target), int(ids.numel()), _p(ids), C.c_float(threshold)),
+                  "vo_kfstore_fuse_map_points_dev")
+            return
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        check(lib().vo_kfstore_fuse_map_points(self._h, int(target), len(a), _p(a), C.c_float(threshold)), "vo_kfstore_fuse_map_points")
+
+    def search_in_neighbors(self, current):
+        """LocalMapping::searchInNeighbors for the current key-frame; enqueued only"""
+        check(lib().vo_kfstore_search_in_neighbors(self._h, int(current)), "vo_kfstore_search_in_neighbors")
+
+    def fuse_result(self):
+        """the last fuse call -> dict(targets, per_target [(passed, matches, adds, kept_org, kept_candidate, cleared)], totals);
+        synchronises"""
+        rec, tg, per = np.zeros(8, np.int32), np.zeros(self.FUSE_MAX_STEPS, np.int32), np.zeros((self.FUSE_MAX_STEPS, 6), np.int32)
+        check(lib().vo_kfstore_fuse_result(self._h, _p(rec), _p(tg), _p(per)), "vo_kfstore_fuse_result")
+        n = int(rec[0])
+        return dict(targets=[int(t) for t in tg[:n]], per_target=[tuple(int(x) for x in row) for row in per[:n]],
+                    totals=tuple(int(x) for x in rec[1:7]))
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -1,0 +1,649 @@
+// fuse.hip -- map-point fusion on the device: LocalMapping::searchInNeighbors
+// (localMapping.cpp:363-432), Matcher::fuseMapPoints (matcher.cpp:1012-1133) and MapPoint::replaceMapPoint
+// (mappoint.cpp:214-253) over the key-frame store's observation index AS IT STOOD AT THE START OF THE CALL plus an overlay
+// (vo_common.h: KfOverlay; obs_walk.h: obs_overlay_wave), so that a call of up to 61 fuse steps never rebuilds the index.
+//   k_fuse_begin    the target list from section 4h's ordered lists (one thread) and `current`'s ids (a thread per feature)
+//   k_fuse_mark     a thread per list entry: the id's slot (the start of its run), an atomic maximum there decides the first
+//                   occurrence of the id in the list without a sort
+//   k_fuse_search   a workgroup stages the target's x, y, octave and u_right in LDS; a wavefront per list entry: holders
+//                   through the overlay, the gates of a candidate, then lanes over the target's features -- cell rule, radius,
+//                   octave and chi-square gates, a descriptor fetched only behind them -- and a wave minimum over (distance,
+//                   cell column, cell row, feature).  A match reserves its number in the call's match list.
+//   k_fuse_mutate   a wavefront (a workgroup of 64) per CHAIN of matches -- the matches that hit one feature of the target,
+//                   or features that carried one id when the step began -- in list order, lanes over carriers: add, or
+//                   replace in either direction with the counters and computeDescriptor of the survivor
+//   k_fuse_gather   the closing step's list: the targets' ids, a thread per (target, feature)
+//   k_fuse_live     `current`'s live ids, each once, for the closing descriptors and refresh
+// No kernel waits on another workgroup; every loop is bounded by a count read once or by an array's size; chains read and
+// write disjoint ids and disjoint features, so every byte has one writer per launch.
+#include "vo_common.h"
+
+#include "new_points_geom.h"
+#include "obs_walk.h"
+
+namespace {
+
+using namespace vo;
+
+constexpr int kMaxC = kFuseMaxCarriers;
+constexpr int kMutateGrid = 256, kSearchGrid = 1024;
+constexpr int kThLow = 50;
+constexpr int kGridCols = 64, kGridRows = 48;
+
+__device__ __forceinline__ int n_features(const KfStoreView &S, int k) { return min(max(kf_head(S, k)[0], 0), S.NK); }
+__device__ __forceinline__ bool kf_bad(const KfStoreView &S, int k) { return kf_head(S, k)[1] != 0; }
+__device__ __forceinline__ uint8_t *record_of(const KfStoreView &S, int k) { return const_cast<uint8_t *>(S.base) + (size_t)k * S.rec; }
+__device__ __forceinline__ int *id_word(const KfStoreView &S, unsigned e) {
+  const unsigned kk = e / (unsigned)S.NK;
+  return reinterpret_cast<int *>(record_of(S, (int)kk) + S.o_ids) + (e - kk * (unsigned)S.NK);
+}
+__device__ __forceinline__ uint8_t *flag_byte(const KfStoreView &S, unsigned e) {
+  const unsigned kk = e / (unsigned)S.NK;
+  return record_of(S, (int)kk) + S.o_flags + (e - kk * (unsigned)S.NK);
+}
+// does the live feature word of entry e say "carries id"?
+__device__ __forceinline__ bool carries(const KfStoreView &S, unsigned e, int id) {
+  if (e / (unsigned)S.NK >= (unsigned)S.size) return false;
+  return *id_word(S, e) == id && (*flag_byte(S, e) & 1);
+}
+__device__ __forceinline__ unsigned first_code(int step, int pos) { return ((unsigned)(step + 1) << 24) | (0xffffffu - (unsigned)pos); }
+__device__ __forceinline__ int slot_of(const KfObsView &O, int id) {
+  const int p = obs_lower_bound(O, id);
+  return p < O.n_keys && (int)(O.keys[p] >> 32) == id ? p : -1;
+}
+__device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = w < v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ int wave_sum_int(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ bool target_ready(const FuseArgs &A, int T) {
+  return T >= 0 && T < A.S.size && !A.X.erased[T] && *np_pose_set(A.M, T) != 0;
+}
+
+// ---- the target list (localMapping.cpp:365-386) and current's ids (:390)
+__global__ __launch_bounds__(256) void k_fuse_begin(FuseArgs A, int current) {
+  const int i = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK;
+  const bool ok = target_ready(A, current);
+  if (i < NK) {
+    int id = -1;
+    if (ok && i < n_features(A.S, current) && (kf_sec<uint8_t>(A.S, current, A.S.o_flags)[i] & 1)) id = kf_sec<int>(A.S, current, A.S.o_ids)[i];
+    A.F.snap[i] = id;
+  }
+  if (i != 0) return;
+  int n = 0;
+  if (!ok) atomicOr(A.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
+  if (ok) {
+    const int size = A.S.size, n1 = min(min(max(A.C.n_ordered[current], 0), min(size, A.C.max_kf)), 10);
+    const int *l1 = A.C.ordered + (size_t)current * A.C.max_kf;
+    int marked[10], n_marked = 0;
+    auto is_marked = [&](int k) {
+      for (int m = 0; m < n_marked; m++)
+        if (marked[m] == k) return true;
+      return false;
+    };
+    for (int a = 0; a < n1; a++) {
+      const int kfn = l1[a];
+      if (kfn < 0 || kfn >= size || kf_bad(A.S, kfn) || is_marked(kfn)) continue;  // (:371)
+      A.F.targets[n++] = kfn, marked[n_marked++] = kfn;
+      const int n2 = min(min(max(A.C.n_ordered[kfn], 0), min(size, A.C.max_kf)), 5);
+      const int *l2 = A.C.ordered + (size_t)kfn * A.C.max_kf;
+      for (int b = 0; b < n2; b++) {
+        const int kfs = l2[b];
+        if (kfs < 0 || kfs >= size || kf_bad(A.S, kfs) || is_marked(kfs) || kfs == current) continue;  // (:381)
+        A.F.targets[n++] = kfs;  // (only first neighbours are marked: a key-frame may come again)
+      }
+    }
+  }
+  for (int t = n; t < kFuseFinal; t++) A.F.targets[t] = -1;
+  A.F.targets[kFuseFinal] = ok ? current : -1;
+  A.F.head[0] = n, A.F.head[2] = current;
+}
+
+__global__ void k_fuse_begin_single(KfFuseView F, int target) {
+  if (threadIdx.x == 0) F.targets[0] = target, F.targets[kFuseFinal] = -1, F.head[0] = 1, F.head[2] = target;
+}
+
+// ---- a step's list: the first occurrence of every id
+__global__ __launch_bounds__(256) void k_fuse_mark(FuseArgs A, int step, const int *list, int n_max, const int *n_dev) {
+  const int pos = blockIdx.x * 256 + threadIdx.x;
+  const int T = A.F.targets[step];
+  if (pos == 0) {
+    int *rec = A.F.rec + step * kFuseRecInts;
+    rec[kFuTarget] = T;
+    A.F.base[step] = A.F.head[1];
+    if (T >= 0 && !target_ready(A, T)) rec[kFuUndone] = 2, atomicOr(A.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
+  }
+  if (T < 0) return;
+  const int n = n_dev ? min(max(*n_dev, 0), n_max) : n_max;
+  if (pos >= n) return;
+  const int id = list[pos];
+  if (id < 0) return;
+  const int p = slot_of(A.O, id);
+  if (p >= 0 && p < A.F.V.n_slots) atomicMax(reinterpret_cast<unsigned *>(A.F.first) + p, first_code(step, pos));
+}
+
+// ---- the gates of a candidate and its best match
+__global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, int step, const int *list, int n_max, const int *n_dev, float threshold) {
+  extern __shared__ float4 s_feat[];  // x, y, u_right, octave (as int bits)
+  const int T = A.F.targets[step];
+  if (T < 0 || !target_ready(A, T)) return;  // (uniform over the grid)
+  const KfStoreView &S = A.S;
+  const int NK = S.NK, nT = n_features(S, T), tid = threadIdx.x, lane = tid & 63;
+  {
+    const float *x = np_x(A.M, T), *y = np_y(A.M, T), *ur = cull_uright(A.X, T);
+    const int *oc = cull_octave(A.X, T);
+    for (int f = tid; f < nT; f += 256) s_feat[f] = make_float4(x[f], y[f], ur[f], __int_as_float(oc[f]));
+  }
+  __syncthreads();
+  const int n = n_dev ? min(max(*n_dev, 0), n_max) : n_max;
+  const float fx = A.M.cam[0], fy = A.M.cam[1], cx = A.M.cam[2], cy = A.M.cam[3], bf = A.M.cam[4];
+  const int n_levels = min(max(A.M.n_levels, 1), 16);
+  const float log_sf1 = (float)log((double)A.M.sf[1]);
+  const double *Tp = np_pose(A.M, T);
+  double Ow[3];
+  np_center(Tp, Ow);
+  int *rec = A.F.rec + step * kFuseRecInts;
+  for (int pos = blockIdx.x * 4 + (tid >> 6); pos < n; pos += (int)gridDim.x * 4) {  // (uniform over the wavefront)
+    const int id = list[pos];
+    if (id < 0) continue;
+    const int p = slot_of(A.O, id);
+    if (p < 0 || p >= A.F.V.n_slots || (unsigned)A.F.first[p] != first_code(step, pos)) continue;  // a second occurrence is always skipped
+    // `mp->isBad() || mp->beObserved(keyframe)` (:1029): the holders through the overlay; the attributes of the first live carrier
+    unsigned lowest = ~0u;
+    bool in_T = false;
+    obs_overlay_wave(A.O, A.F.V, p, [&](bool valid, unsigned e) {
+      if (valid && carries(S, e, id)) {
+        lowest = min(lowest, e);
+        if ((int)(e / (unsigned)NK) == T) in_T = true;
+      }
+    });
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) lowest = min(lowest, (unsigned)__shfl_xor((int)lowest, o));
+    if (lowest == ~0u || __ballot(in_T) != 0ull) continue;
+    const int kk = (int)(lowest / (unsigned)NK), ff = (int)(lowest - (unsigned)kk * (unsigned)NK);
+    const double *pw = kf_sec<double>(S, kk, S.o_points) + 3 * (size_t)ff;
+    double pc[3];
+    for (int r = 0; r < 3; r++) pc[r] = __dadd_rn(np_dot3(Tp[3 * r], pw[0], Tp[3 * r + 1], pw[1], Tp[3 * r + 2], pw[2]), Tp[9 + r]);
+    const float z = (float)pc[2];
+    if (z < 0.0f) continue;  // (:1036)
+    const float invz = __fdiv_rn(1.0f, z);
+    const float xn = __fmul_rn((float)pc[0], invz), yn = __fmul_rn((float)pc[1], invz);
+    const float u = __fadd_rn(__fmul_rn(fx, xn), cx), v = __fadd_rn(__fmul_rn(fy, yn), cy);
+    if (!(u >= A.F.xmin && v >= A.F.ymin && u < A.F.xmax && v < A.F.ymax)) continue;  // isInImg (keyframe.cpp:64-67)
+    const float ur = __fsub_rn(u, __fmul_rn(bf, invz));
+    double line[3];
+    for (int c = 0; c < 3; c++) line[c] = __dadd_rn(pw[c], -Ow[c]);
+    const float dist = (float)__dsqrt_rn(np_dot3(line[0], line[0], line[1], line[1], line[2], line[2]));
+    const float maxd = kf_sec<float>(S, kk, S.o_maxd)[ff], mind = kf_sec<float>(S, kk, S.o_mind)[ff];
+    if (dist < __fmul_rn(0.8f, mind) || dist > __fmul_rn(1.2f, maxd)) continue;  // (:1055, mappoint.cpp:391-401)
+    const double *pn = A.O.normals + ((size_t)kk * NK + ff) * 3;
+    if (np_dot3(line[0], pn[0], line[1], pn[1], line[2], pn[2]) < __dmul_rn(0.5, (double)dist)) continue;  // (:1059)
+    const float ratio = __fdiv_rn(maxd, dist);  // predictScale (mappoint.cpp:198-212), as reloc.hip does it
+    const float lg = (float)log((double)ratio);
+    const int sc = (int)ceilf(__fdiv_rn(lg, log_sf1));
+    const int level = sc < 0 ? 0 : (sc >= n_levels ? n_levels - 1 : sc);
+    const float radius = __fmul_rn(threshold, A.M.sf[level]);
+    if (lane == 0) atomicAdd(rec + kFuPassed, 1);
+    // getFeaturesInArea (keyframe.cpp:268-309): the floor-computed cell range
+    const float gpw = A.F.gpw, gph = A.F.gph;
+    const int x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, A.F.xmin), radius), gpw)));
+    const int x1 = min(kGridCols - 1, (int)floorf(__fmul_rn(__fadd_rn(__fsub_rn(u, A.F.xmin), radius), gpw)));
+    const int y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, A.F.ymin), radius), gph)));
+    const int y1 = min(kGridRows - 1, (int)floorf(__fmul_rn(__fadd_rn(__fsub_rn(v, A.F.ymin), radius), gph)));
+    if (x0 >= kGridCols || x1 < 0 || y0 >= kGridRows || y1 < 0) continue;
+    const uint4 *qd = reinterpret_cast<const uint4 *>(record_of(S, kk) + S.o_pdesc) + 2 * (size_t)ff;
+    const uint4 qa = qd[0], qb = qd[1];
+    unsigned long long best = ~0ull;
+    for (int f = lane; f < nT; f += 64) {
+      const float4 t = s_feat[f];
+      // the feature's own cell is ROUNDED (frame.cpp:83-86); outside the grid it is in no cell
+      const int gx = (int)roundf(__fmul_rn(__fsub_rn(t.x, A.F.xmin), gpw)), gy = (int)roundf(__fmul_rn(__fsub_rn(t.y, A.F.ymin), gph));
+      if (gx < 0 || gx >= kGridCols || gy < 0 || gy >= kGridRows || gx < x0 || gx > x1 || gy < y0 || gy > y1) continue;
+      if (!(fabsf(__fsub_rn(t.x, u)) < radius && fabsf(__fsub_rn(t.y, v)) < radius)) continue;
+      const int oct = __float_as_int(t.w);
+      if (oct < level - 1 || oct > level) continue;  // (:1077)
+      const float ex = __fsub_rn(u, t.x), ey = __fsub_rn(v, t.y);
+      const float inv = __fdiv_rn(1.0f, A.M.sf[min(max(oct, 0), 15)]);
+      float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey)), th = 5.991f;
+      if (t.z >= 0.f) {
+        const float er = __fsub_rn(ur, t.z);
+        e2 = __fadd_rn(e2, __fmul_rn(er, er)), th = 7.815f;
+      }
+      if (__fmul_rn(__fmul_rn(e2, inv), inv) > th) continue;  // (:1090, :1097)
+      const uint4 *dd = reinterpret_cast<const uint4 *>(kf_sec<uint8_t>(S, T, S.o_desc)) + 2 * (size_t)f;
+      const uint4 da = dd[0], db = dd[1];
+      const int d = __popc(qa.x ^ da.x) + __popc(qa.y ^ da.y) + __popc(qa.z ^ da.z) + __popc(qa.w ^ da.w) + __popc(qb.x ^ db.x) +
+                    __popc(qb.y ^ db.y) + __popc(qb.z ^ db.z) + __popc(qb.w ^ db.w);
+      // the strictly smallest distance in the visiting order: cell column, cell row, feature
+      const unsigned long long key = ((unsigned long long)d << 44) | ((unsigned long long)gx << 38) | ((unsigned long long)gy << 32) | (unsigned)f;
+      best = key < best ? key : best;
+    }
+    best = wave_min_u64(best);
+    if (best == ~0ull || (int)(best >> 44) > kThLow) continue;  // (:1109)
+    if (lane == 0) {
+      const int f = (int)(best & 0xffffffffu);
+      atomicAdd(rec + kFuMatches, 1);
+      const int m = atomicAdd(A.F.head + 1, 1);
+      if (m >= 0 && m < A.F.M) {
+        // the chain of the match: the id the feature carries as the step begins, else the feature
+        const unsigned eT = (unsigned)T * (unsigned)NK + (unsigned)f;
+        const int org = *id_word(S, eT);
+        int key = A.O.n_keys + f;
+        if ((*flag_byte(S, eT) & 1) && org >= 0) {
+          const int po = slot_of(A.O, org);
+          if (po >= 0) key = po;
+        }
+        A.F.mt[m] = make_int4(pos, id, p, f), A.F.key[m] = key;
+      }
+    }
+  }
+}
+
+// ---- the carriers of id (slot p) through the overlay into `out` (at most kMaxC are stored): their number
+__device__ int collect(const FuseArgs &A, int id, int p, unsigned *out) {
+  const int lane = threadIdx.x & 63;
+  int n = 0;
+  obs_overlay_wave(A.O, A.F.V, p, [&](bool valid, unsigned e) {
+    const bool live = valid && carries(A.S, e, id);
+    const unsigned long long m = __ballot(live);
+    const int r = n + __popcll(m & ((1ull << lane) - 1ull));
+    if (live && r < kMaxC) out[r] = e;
+    n += __popcll(m);
+  });
+  __syncthreads();
+  return n;
+}
+
+// cls[c] of the n carriers: 0 an entry listed before, 1 its key-frame's observation (the lowest entry), 2 another feature of a
+// holder; -> obs(id) (mappoint.cpp:60-63)
+__device__ int classify(const FuseArgs &A, const unsigned *L, int n, uint8_t *cls) {
+  const int lane = threadIdx.x & 63;
+  const unsigned NK = (unsigned)A.S.NK;
+  int obs = 0;
+  for (int c = lane; c < n; c += 64) {
+    const unsigned e = L[c], kk = e / NK;
+    int k = 1;
+    for (int o = 0; o < n && k; o++) {
+      const unsigned eo = L[o];
+      if (o < c && eo == e) k = 0;
+      else if (eo / NK == kk && eo < e) k = 2;
+    }
+    if (k == 2)
+      for (int o = 0; o < c; o++)
+        if (L[o] == e) k = 0;
+    cls[c] = (uint8_t)k;
+    if (k == 1) obs += cull_uright(A.X, (int)kk)[e - kk * NK] >= 0.f ? 2 : 1;
+  }
+  obs = wave_sum_int(obs);
+  __syncthreads();
+  return obs;
+}
+
+struct Attr {
+  double p[3], n[3];
+  float mind, maxd;
+  int ref;
+  uint4 d0, d1;
+};
+__device__ __forceinline__ Attr attr_of(const FuseArgs &A, unsigned e) {
+  const int NK = A.S.NK, kk = (int)(e / (unsigned)NK), f = (int)(e - (unsigned)kk * (unsigned)NK);
+  Attr a;
+  const double *P = kf_sec<double>(A.S, kk, A.S.o_points) + 3 * (size_t)f, *N = A.normals + ((size_t)kk * NK + f) * 3;
+  for (int c = 0; c < 3; c++) a.p[c] = P[c], a.n[c] = N[c];
+  a.mind = kf_sec<float>(A.S, kk, A.S.o_mind)[f], a.maxd = kf_sec<float>(A.S, kk, A.S.o_maxd)[f];
+  a.ref = A.B.ref_kf[(size_t)kk * NK + f];
+  const uint4 *D = reinterpret_cast<const uint4 *>(record_of(A.S, kk) + A.S.o_pdesc) + 2 * (size_t)f;
+  a.d0 = D[0], a.d1 = D[1];
+  return a;
+}
+// feature e takes the id and its attributes (bit 0 is the caller's)
+__device__ __forceinline__ void take(const FuseArgs &A, unsigned e, int id, const Attr &a) {
+  const int NK = A.S.NK, kk = (int)(e / (unsigned)NK), f = (int)(e - (unsigned)kk * (unsigned)NK);
+  uint8_t *r = record_of(A.S, kk);
+  *id_word(A.S, e) = id;
+  double *P = reinterpret_cast<double *>(r + A.S.o_points) + 3 * (size_t)f, *N = A.normals + ((size_t)kk * NK + f) * 3;
+  for (int c = 0; c < 3; c++) P[c] = a.p[c], N[c] = a.n[c];
+  reinterpret_cast<float *>(r + A.S.o_mind)[f] = a.mind, reinterpret_cast<float *>(r + A.S.o_maxd)[f] = a.maxd;
+  A.B.ref_kf[(size_t)kk * NK + f] = a.ref;
+  uint4 *D = reinterpret_cast<uint4 *>(r + A.S.o_pdesc) + 2 * (size_t)f;
+  D[0] = a.d0, D[1] = a.d1;
+}
+__device__ __forceinline__ unsigned lowest_of(const unsigned *L, int n) {
+  unsigned lo = ~0u;
+  for (int c = threadIdx.x & 63; c < min(n, kMaxC); c += 64) lo = min(lo, L[c]);
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) lo = min(lo, (unsigned)__shfl_xor((int)lo, o));
+  return lo;
+}
+
+struct MutateLds {
+  unsigned a[kMaxC], b[kMaxC], h[kMaxC], t[kMaxC];
+  uint8_t ca[kMaxC], cb[kMaxC];
+  uint32_t d[kMaxC * 9];
+};
+
+// MapPoint::computeDescriptor of B (mappoint.cpp:118-179) from the carriers the replace leaves: B's own (L.b, L.cb) and the
+// converted ones of A (L.ca == 3); k_up_desc_over's selection by one wavefront
+__device__ void descriptor_of(const FuseArgs &A, MutateLds &L, int na, int nb) {
+  const int lane = threadIdx.x & 63;
+  const unsigned NK = (unsigned)A.S.NK;
+  int N = 0;
+  for (int pass = 0; pass < 2; pass++) {
+    const unsigned *src = pass ? L.a : L.b;
+    const uint8_t *cl = pass ? L.ca : L.cb;
+    const int want = pass ? 3 : 1, n = pass ? na : nb;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+      const int c = c0 + lane;
+      const bool hold = c < n && cl[c] == want && !kf_bad(A.S, (int)(src[c] / NK));  // (:138)
+      const unsigned long long m = __ballot(hold);
+      const int r = N + __popcll(m & ((1ull << lane) - 1ull));
+      if (hold && r < kMaxC) L.h[r] = src[c];
+      N += __popcll(m);
+    }
+  }
+  __syncthreads();
+  if (N == 0) return;  // `if (desp.empty()) return;`
+  if (N > kMaxC) {     // the point keeps its descriptor (section 4l's capacity)
+    if (lane == 0) atomicOr(A.status, (int)VO_KFSTORE_UPKEEP_CAPACITY);
+    return;
+  }
+  for (int c = lane; c < N; c += 64) {  // ascending key-frame number: the entries are distinct
+    const unsigned e = L.h[c];
+    int r = 0;
+    for (int o = 0; o < N; o++) r += L.h[o] < e;
+    L.t[r] = e;
+  }
+  __syncthreads();
+  for (int i = lane; i < N * 8; i += 64) {
+    const unsigned e = L.t[i >> 3], kk = e / NK;
+    L.d[(i >> 3) * 9 + (i & 7)] = (kf_sec<uint32_t>(A.S, (int)kk, A.S.o_desc) + 8 * (size_t)(e - kk * NK))[i & 7];
+  }
+  __syncthreads();
+  const int k = (N - 1) / 2;
+  constexpr int NC = kMaxC / 64;
+  int best_mid = 256, best = 0;
+  for (int row = 0; row < N; row++) {
+    uint32_t a[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) a[j] = L.d[row * 9 + j];
+    int d[NC];
+#pragma unroll
+    for (int c = 0; c < NC; c++) {
+      d[c] = 0x7fff;
+      const int col = lane + 64 * c;
+      if (col < N) {
+        int sum = 0;
+#pragma unroll
+        for (int j = 0; j < 8; j++) sum += __popc(a[j] ^ L.d[col * 9 + j]);
+        d[c] = sum;
+      }
+    }
+    int lo = 0, hi = 256;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      int cnt = 0;
+#pragma unroll
+      for (int c = 0; c < NC; c++)
+        if (64 * c < N) cnt += __popcll(__ballot(d[c] <= mid));
+      if (cnt >= k + 1) hi = mid;
+      else lo = mid + 1;
+    }
+    if (lo < best_mid) best_mid = lo, best = row;  // strict: the first row wins (:168)
+  }
+  const uint32_t *win = L.d + best * 9;
+  for (int pass = 0; pass < 2; pass++) {  // every feature that carries B, bad key-frames included
+    const unsigned *src = pass ? L.a : L.b;
+    const uint8_t *cl = pass ? L.ca : L.cb;
+    const int n = pass ? na : nb;
+    for (int c = lane; c < n; c += 64) {
+      if (pass ? cl[c] != 3 : cl[c] == 0) continue;
+      const unsigned e = src[c], kk = e / NK;
+      uint32_t *dst = reinterpret_cast<uint32_t *>(record_of(A.S, (int)kk) + A.S.o_pdesc) + 8 * (size_t)(e - kk * NK);
+#pragma unroll
+      for (int j = 0; j < 8; j++) dst[j] = win[j];
+    }
+  }
+}
+
+// ---- the mutation (:1109-1127) of one chain per wavefront
+__global__ __launch_bounds__(64) void k_fuse_mutate(FuseArgs A, int step) {
+  __shared__ MutateLds L;
+  const int T = A.F.targets[step];
+  if (T < 0 || !target_ready(A, T)) return;
+  const int lane = threadIdx.x, NK = A.S.NK;
+  const int base = min(max(A.F.base[step], 0), A.F.M), end = A.F.head[1];
+  int *rec = A.F.rec + step * kFuseRecInts;
+  // more candidates passed the gates than a step takes, or the call's matches do not fit: the step is left undone
+  if (rec[kFuPassed] > A.F.M || end > A.F.M) {
+    if (blockIdx.x == 0 && lane == 0) atomicOr(A.status, (int)VO_KFSTORE_FUSE_CAPACITY), rec[kFuUndone] = 1;
+    return;
+  }
+  const KfOverlay &V = A.F.V;
+  for (int m0 = base + (int)blockIdx.x; m0 < end; m0 += (int)gridDim.x) {
+    const int key = A.F.key[m0], pos0 = A.F.mt[m0].x;
+    bool later = false;  // the chain's leader is its first match in list order
+    for (int o = base + lane; o < end; o += 64) later |= A.F.key[o] == key && A.F.mt[o].x < pos0;
+    if (__ballot(later) != 0ull) continue;
+    int cur = m0;
+    for (int guard = base; cur >= 0 && guard < end; guard++) {
+      const int4 mt = A.F.mt[cur];
+      const int mp = mt.y, p_mp = mt.z, f = mt.w;
+      if (p_mp >= 0 && p_mp < V.n_slots && f >= 0 && f < NK) {
+        const unsigned eT = (unsigned)T * (unsigned)NK + (unsigned)f;
+        const int nb0 = collect(A, mp, p_mp, L.b);
+        bool held = false;
+        for (int c = lane; c < min(nb0, kMaxC); c += 64) held |= (int)(L.b[c] / (unsigned)NK) == T;
+        const int org = *id_word(A.S, eT);
+        const bool occupied = (*flag_byte(A.S, eT) & 1) && org >= 0;
+        if (nb0 == 0 || __ballot(held) != 0ull) {
+          // (a candidate that passed is not held by the target and has a holder: nothing to do here)
+        } else if (!occupied) {  // addObservation + addMapPoint (:1124-1125)
+          const unsigned src = lowest_of(L.b, nb0);
+          if (lane == 0) {
+            const Attr a = attr_of(A, src);
+            take(A, eT, mp, a);
+            uint8_t *fb = flag_byte(A.S, eT);
+            *fb = (uint8_t)(*fb | 1);
+            V.node_entry[cur] = (int)eT, V.node_next[cur] = V.a_head[p_mp], V.a_head[p_mp] = cur + 1;
+            atomicAdd(rec + kFuAdds, 1);
+          }
+        } else {
+          const int p_org = slot_of(A.O, org);
+          const int na0 = p_org >= 0 && p_org < V.n_slots ? collect(A, org, p_org, L.a) : 0;
+          if (na0 > kMaxC || nb0 > kMaxC || p_org < 0 || p_org >= V.n_slots) {
+            if (lane == 0) atomicOr(A.status, (int)VO_KFSTORE_FUSE_CAPACITY);
+          } else {
+            const int obs_org = classify(A, L.a, na0, L.ca), obs_mp = classify(A, L.b, nb0, L.cb);
+            const bool keep_org = obs_org > obs_mp;  // (:1116)
+            if (keep_org) {  // the point that goes is the candidate: its carriers change places with org's, so that A sits in L.a
+              for (int c = lane; c < max(na0, nb0); c += 64) {
+                const unsigned x = L.a[c];
+                const uint8_t y = L.ca[c];
+                L.a[c] = L.b[c], L.ca[c] = L.cb[c], L.b[c] = x, L.cb[c] = y;
+              }
+              __syncthreads();
+            }
+            const int idA = keep_org ? mp : org, idB = keep_org ? org : mp, pA = keep_org ? p_mp : p_org, pB = keep_org ? p_org : p_mp;
+            const int na = keep_org ? nb0 : na0, nb = keep_org ? na0 : nb0;
+            const Attr a = attr_of(A, lowest_of(L.b, nb));
+            int cleared = 0;
+            for (int c = lane; c < na; c += 64) {  // replaceMapPoint (mappoint.cpp:235-246)
+              if (L.ca[c] == 0) continue;
+              const unsigned e = L.a[c], kk = e / (unsigned)NK;
+              bool holds_b = false;
+              for (int o = 0; o < nb && !holds_b; o++) holds_b = L.b[o] / (unsigned)NK == kk;
+              if (L.ca[c] == 1 && !holds_b) {
+                take(A, e, idB, a);
+                L.ca[c] = 3;
+              } else {  // the holder has B already, or a second feature of a holder
+                uint8_t *fb = flag_byte(A.S, e);
+                *fb = (uint8_t)(*fb & ~1);
+                cleared++;
+              }
+            }
+            cleared = wave_sum_int(cleared);
+            // addFound / addVisible (:248-249) when both are listed
+            int ia = -1, ib = -1;
+            const int n_rec = min(max(A.U.head[0], 0), A.U.R);
+            for (int j = lane; j < n_rec; j += 64) {
+              const int v = A.U.id[j];
+              if (v == idA) ia = j;
+              if (v == idB) ib = j;
+            }
+#pragma unroll
+            for (int o = 32; o >= 1; o >>= 1) ia = max(ia, __shfl_xor(ia, o)), ib = max(ib, __shfl_xor(ib, o));
+            if (lane == 0) {
+              if (ia >= 0 && ib >= 0) A.U.found[ib] += A.U.found[ia], A.U.visible[ib] += A.U.visible[ia];
+              // A's runs and added entries go behind B's
+              const int tail_b = V.m_tail[pB] > 0 ? V.m_tail[pB] - 1 : pB;
+              if (tail_b >= 0 && tail_b < V.n_slots) V.m_next[tail_b] = pA + 1;
+              V.m_tail[pB] = V.m_tail[pA] > 0 ? V.m_tail[pA] : pA + 1;
+              atomicAdd(rec + (keep_org ? kFuKeptOrg : kFuKeptCand), 1);
+              if (cleared) atomicAdd(rec + kFuCleared, cleared);
+            }
+            __threadfence_block();
+            __syncthreads();
+            descriptor_of(A, L, na, nb);
+          }
+        }
+      }
+      __threadfence_block();
+      __syncthreads();
+      // the chain's next match in list order
+      unsigned long long nxt = ~0ull;
+      const int pos_cur = mt.x;
+      for (int o = base + lane; o < end; o += 64) {
+        const int po = A.F.mt[o].x;
+        if (A.F.key[o] == key && po > pos_cur) {
+          const unsigned long long k2 = ((unsigned long long)(unsigned)po << 32) | (unsigned)o;
+          nxt = k2 < nxt ? k2 : nxt;
+        }
+      }
+      nxt = wave_min_u64(nxt);
+      cur = nxt == ~0ull ? -1 : (int)(nxt & 0xffffffffu);
+    }
+  }
+}
+
+// ---- the closing step's candidates (:397-416): the targets' ids, first occurrences decided by k_fuse_mark
+__global__ __launch_bounds__(256) void k_fuse_gather(FuseArgs A) {
+  const int i = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK;
+  const int n_t = min(max(A.F.head[0], 0), kFuseFinal);
+  if (i == 0) A.F.head[3] = n_t * NK;
+  if (i >= n_t * NK) return;
+  const int t = i / NK, f = i - t * NK, T = A.F.targets[t];
+  int id = -1;
+  if (T >= 0 && T < A.S.size && !A.X.erased[T] && f < n_features(A.S, T) && (kf_sec<uint8_t>(A.S, T, A.S.o_flags)[f] & 1))
+    id = kf_sec<int>(A.S, T, A.S.o_ids)[f];
+  A.F.list[i] = id;
+}
+
+// ---- current's live points (:420-429), each id once
+__global__ __launch_bounds__(256) void k_fuse_live(FuseArgs A, int current) {
+  const int i = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK;
+  if (i == 0) A.F.head[2] = current;
+  if (i >= NK) return;
+  int id = -1;
+  if (target_ready(A, current) && i < n_features(A.S, current)) {
+    const uint8_t *fl = kf_sec<uint8_t>(A.S, current, A.S.o_flags);
+    const int *ids = kf_sec<int>(A.S, current, A.S.o_ids);
+    if ((fl[i] & 1) && ids[i] >= 0) {
+      id = ids[i];
+      for (int o = 0; o < i; o++)
+        if ((fl[o] & 1) && ids[o] == id) {
+          id = -1;
+          break;
+        }
+    }
+  }
+  A.F.snap[i] = id;
+}
+
+size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+struct Layout {
+  uint8_t *block;
+  size_t at = 0;
+  template <class T>
+  void take(T *&field, size_t count) {
+    field = block ? reinterpret_cast<T *>(block + at) : nullptr;
+    at += up16(count * sizeof(T));
+  }
+};
+
+void fuse_lay(Layout &L, KfFuseView &F, int NK, int M, int n_slots) {
+  const size_t s = (size_t)n_slots, m = (size_t)M;
+  L.take(F.head, 4), L.take(F.base, 64), L.take(F.targets, 64), L.take(F.rec, 64 * kFuseRecInts);
+  L.take(F.first, s), L.take(F.V.m_next, s), L.take(F.V.m_tail, s), L.take(F.V.a_head, s);
+  F.reset_bytes = L.at;
+  L.take(F.V.node_entry, m), L.take(F.V.node_next, m), L.take(F.key, m), L.take(F.mt, m);
+  L.take(F.snap, (size_t)NK), L.take(F.list, (size_t)kFuseFinal * NK);
+  F.NK = NK, F.M = M, F.list_cap = kFuseFinal * NK, F.V.n_slots = n_slots, F.V.n_nodes = M;
+}
+
+int step_enqueue(const FuseArgs &A, int step, const int *list, int n_max, const int *n_dev, float threshold, hipStream_t st) {
+  // (an empty list still gets the step's record and the sticky word of a target that is erased or has no pose)
+  hipLaunchKernelGGL(k_fuse_mark, dim3((unsigned)std::max((n_max + 255) / 256, 1)), dim3(256), 0, st, A, step, list, std::max(n_max, 0), n_dev);
+  if (n_max <= 0) {
+    VO_HIP_CHECK(hipGetLastError());
+    return VO_OK;
+  }
+  const int blocks = std::min((n_max + 3) / 4, kSearchGrid);
+  hipLaunchKernelGGL(k_fuse_search, dim3((unsigned)blocks), dim3(256), (size_t)A.S.NK * sizeof(float4), st, A, step, list, n_max, n_dev,
+                     threshold);
+  hipLaunchKernelGGL(k_fuse_mutate, dim3(kMutateGrid), dim3(64), 0, st, A, step);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+}  // namespace
+
+namespace vo {
+
+size_t fuse_bytes(int NK, int max_matches, int n_slots) {
+  Layout L{nullptr};
+  KfFuseView F{};
+  fuse_lay(L, F, NK, max_matches, n_slots);
+  return L.at;
+}
+
+KfFuseView fuse_layout(void *block, int NK, int max_matches, int n_slots, const float bounds[4]) {
+  Layout L{reinterpret_cast<uint8_t *>(block)};
+  KfFuseView F{};
+  fuse_lay(L, F, NK, max_matches, n_slots);
+  F.xmin = bounds[0], F.xmax = bounds[1], F.ymin = bounds[2], F.ymax = bounds[3];
+  F.gpw = (float)kGridCols / (F.xmax - F.xmin), F.gph = (float)kGridRows / (F.ymax - F.ymin);  // (camera.cpp:47-48)
+  return F;
+}
+
+int fuse_single_enqueue(const FuseArgs &A, int target, int n, const int *dev_ids, float threshold, hipStream_t st) {
+  VO_HIP_CHECK(hipMemsetAsync(A.F.head, 0, A.F.reset_bytes, st));
+  hipLaunchKernelGGL(k_fuse_begin_single, dim3(1), dim3(64), 0, st, A.F, target);
+  return step_enqueue(A, 0, dev_ids, n, nullptr, threshold, st);
+}
+
+int fuse_neighbors_enqueue(const FuseArgs &A, int current, hipStream_t st) {
+  const int NK = A.S.NK;
+  VO_HIP_CHECK(hipMemsetAsync(A.F.head, 0, A.F.reset_bytes, st));
+  hipLaunchKernelGGL(k_fuse_begin, dim3((unsigned)((NK + 255) / 256)), dim3(256), 0, st, A, current);
+  for (int step = 0; step < kFuseFinal; step++) VO_CHECK(step_enqueue(A, step, A.F.snap, NK, nullptr, 3.0f, st));  // (:389-395)
+  hipLaunchKernelGGL(k_fuse_gather, dim3((unsigned)((kFuseFinal * NK + 255) / 256)), dim3(256), 0, st, A);
+  return step_enqueue(A, kFuseFinal, A.F.list, kFuseFinal * NK, A.F.head + 3, 3.0f, st);  // (:418)
+}
+
+int fuse_live_list_enqueue(const FuseArgs &A, int current, hipStream_t st) {
+  hipLaunchKernelGGL(k_fuse_live, dim3((unsigned)((A.S.NK + 255) / 256)), dim3(256), 0, st, A, current);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+}  // namespace vo

@@ -118,6 +118,9 @@ struct vo_kfstore {
   vo::OwnedPinnedBuf up_stage;        // a host form's lists going up: one copy
   vo::KfUpkeepView U{};
   bool upkeep = false;
+  vo::OwnedDevBuf fu;                 // vo_kfstore_enable_fuse: the block of section 4m
+  vo::KfFuseView F{};
+  bool fuse = false;
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -233,6 +236,12 @@ int need_local_ba(const vo_kfstore *s, const char *call) {
 int need_upkeep(const vo_kfstore *s, const char *call) {
   if (s && s->upkeep) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_point_upkeep has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_fuse(const vo_kfstore *s, const char *call) {
+  if (s && s->fuse) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_fuse has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -1215,6 +1224,109 @@ int vo_kfstore_upkeep_result(vo_kfstore *s, int32_t *record, int32_t *erased_ids
     std::sort(er.begin(), er.begin() + ne);
     memcpy(erased_ids, er.data(), (size_t)ne * 4);
   }
+  return VO_OK;
+}
+
+int vo_kfstore_enable_fuse(vo_kfstore *s, const float bounds[4], int max_candidates) {
+  const char *W = "vo_kfstore_enable_fuse";
+  VO_CHECK(need_upkeep(s, W));
+  if (!bounds || max_candidates < 1 || !(bounds[1] > bounds[0]) || !(bounds[3] > bounds[2])) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->NK > 4096) {
+    vo::set_error("%s: %d features per key-frame, the search stages at most 4096", W, s->NK);
+    return VO_ERR_CAPACITY;
+  }
+  if (s->fuse) return VO_OK;
+  const size_t bytes = vo::fuse_bytes(s->NK, max_candidates, s->okeys_cap);
+  VO_CHECK(s->fu.reserve(bytes));
+  s->F = vo::fuse_layout(s->fu.p, s->NK, max_candidates, s->okeys_cap, bounds);
+  VO_CHECK(s->up_stage.reserve((size_t)s->F.list_cap * 4));
+  VO_HIP_CHECK(hipMemsetAsync(s->fu.p, 0, bytes, s->st));
+  VO_HIP_CHECK(hipMemsetAsync(s->F.targets, 0xff, 64 * 4, s->st));  // (no call yet: no step)
+  VO_CHECK(vo::stream_sync(s->st, W));
+  s->fuse = true;
+  return VO_OK;
+}
+
+static vo::FuseArgs fuse_args(vo_kfstore *s, const vo::KfObsView &O) {
+  const vo::KfConnView C = vo::connections_view(s->conn);
+  return vo::FuseArgs{vo::kfstore_view(s), O, C, s->X, s->M, s->B, s->U, s->F, s->normals.as<double>(), C.status};
+}
+
+int vo_kfstore_fuse_map_points_dev(vo_kfstore *s, int target, int n, const int32_t *dev_ids, float threshold) {
+  const char *W = "vo_kfstore_fuse_map_points_dev";
+  VO_CHECK(need_fuse(s, W));
+  VO_CHECK(need_keyframe(s, W, target));
+  if (n < 0 || (n > 0 && !dev_ids) || !(threshold > 0.f)) return VO_ERR_INVALID;
+  if (n > s->F.list_cap) {
+    vo::set_error("%s: %d ids, the store takes %d (60 * max_features)", W, n, s->F.list_cap);
+    return VO_ERR_CAPACITY;
+  }
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  VO_CHECK(vo::fuse_single_enqueue(fuse_args(s, O), target, n, dev_ids, threshold, s->st));
+  s->obs_dirty = true, s->gen++;  // (whether anything matched only the device knows)
+  return VO_OK;
+}
+
+int vo_kfstore_fuse_map_points(vo_kfstore *s, int target, int n, const int32_t *ids, float threshold) {
+  const char *W = "vo_kfstore_fuse_map_points";
+  VO_CHECK(need_fuse(s, W));
+  VO_CHECK(need_keyframe(s, W, target));
+  if (n < 0 || (n > 0 && !ids) || !(threshold > 0.f)) return VO_ERR_INVALID;
+  if (n > s->F.list_cap) {
+    vo::set_error("%s: %d ids, the store takes %d (60 * max_features)", W, n, s->F.list_cap);
+    return VO_ERR_CAPACITY;
+  }
+  if (n > 0) {
+    memcpy(s->up_stage.data(), ids, (size_t)n * 4);
+    VO_CHECK(vo::copy_h2d(s->F.list, s->up_stage.data(), (size_t)n * 4, s->st, W));
+  }
+  VO_CHECK(vo_kfstore_fuse_map_points_dev(s, target, n, s->F.list, threshold));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_search_in_neighbors(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_search_in_neighbors";
+  VO_CHECK(need_fuse(s, W));
+  VO_CHECK(need_keyframe(s, W, current));
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));  // the index the overlay stands on
+  VO_CHECK(vo::fuse_neighbors_enqueue(fuse_args(s, O), current, s->st));
+  s->obs_dirty = true, s->gen++;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));  // the one rebuild behind the fuses, whatever their number
+  const vo::FuseArgs A = fuse_args(s, O);
+  VO_CHECK(vo::fuse_live_list_enqueue(A, current, s->st));
+  VO_CHECK(vo::upkeep_descriptors_enqueue(A.S, O, s->U, A.status, s->NK, s->F.snap, s->st));             // computeDescriptor (:426)
+  VO_CHECK(vo::ba_refresh_list_enqueue(A.S, O, s->X, s->M, s->B, A.normals, A.status, s->NK, s->F.snap, s->st));  // (:427)
+  return vo::connections_update(s->conn, A.S, O, 1, s->F.head + 2, s->st);  // keyframe_curr_->updateConnections() (:431)
+}
+
+int vo_kfstore_fuse_result(vo_kfstore *s, int32_t *record, int32_t *targets, int32_t *per_target) {
+  const char *W = "vo_kfstore_fuse_result";
+  VO_CHECK(need_fuse(s, W));
+  int32_t head[4], tg[64], rec[64 * vo::kFuseRecInts];
+  VO_CHECK(vo::copy_d2h(head, s->F.head, sizeof(head), s->st, W));
+  VO_CHECK(vo::copy_d2h(tg, s->F.targets, sizeof(tg), s->st, W));
+  VO_CHECK(vo::copy_d2h(rec, s->F.rec, sizeof(rec), s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  int32_t out_rec[8] = {0}, out_t[VO_KFSTORE_FUSE_MAX_STEPS], out_p[VO_KFSTORE_FUSE_MAX_STEPS * 6];
+  memset(out_t, 0xff, sizeof(out_t)), memset(out_p, 0, sizeof(out_p));
+  const int n_t = std::min(std::max(head[0], 0), vo::kFuseFinal);
+  int n = 0;
+  for (int step = 0; step <= vo::kFuseFinal; step++) {
+    if (step < vo::kFuseFinal ? step >= n_t : tg[step] < 0) continue;
+    out_t[n] = tg[step];
+    for (int c = 0; c < 6; c++) out_p[n * 6 + c] = rec[step * vo::kFuseRecInts + 1 + c], out_rec[1 + c] += out_p[n * 6 + c];
+    n++;
+  }
+  out_rec[0] = n;
+  if (record) memcpy(record, out_rec, sizeof(out_rec));
+  if (targets) memcpy(targets, out_t, sizeof(out_t));
+  if (per_target) memcpy(per_target, out_p, sizeof(out_p));
   return VO_OK;
 }
 

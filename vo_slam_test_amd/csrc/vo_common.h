@@ -484,6 +484,51 @@ int upkeep_created_enqueue(const KfMapView &M, const KfUpkeepView &U, int *statu
 int upkeep_stats_enqueue(const KfUpkeepView &U, int n, const int *dev_ids, const int *dev_visible, const int *dev_found, hipStream_t st);
 int upkeep_cull_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfUpkeepView &U, int current, hipStream_t st);
 
+// Map-point fusion on the device (fuse.hip): LocalMapping::searchInNeighbors, Matcher::fuseMapPoints
+// and MapPoint::replaceMapPoint from the store.  What vo_kfstore_enable_fuse allocates, one block.  The OVERLAY on the
+// observation index as it stood at the start of a call (n_slots = the index's capacity; a slot is addressed by the start of
+// an id's run, values are stored + 1 so that a memset resets them): m_next / m_tail, per root the chain of the runs of the ids
+// a replace has merged into it; a_head with node_entry / node_next [M], per id the entries a call has added to it (a match
+// reserves the node of its own number).  first [n_slots]: the first occurrence of an id in a step's list.  head [4]: targets
+// in the list, matches reserved by the call, `current`, the length of the closing step's list; base [64]: head[1] at the
+// start of a step; targets [64]; rec [64][8]: (target, passed, matches, adds, kept_org, kept_candidate, cleared, undone) per
+// step; snap [NK], `current`'s ids at the start; list [60 NK], a step's candidates; mt [M], the matches (list position, id,
+// slot, feature) and key [M], their chain keys.
+constexpr int kFuseSteps = 61, kFuseRecInts = 8, kFuseFinal = 60, kFuseMaxCarriers = VO_KFSTORE_FUSE_MAX_CARRIERS;
+enum { kFuTarget = 0, kFuPassed, kFuMatches, kFuAdds, kFuKeptOrg, kFuKeptCand, kFuCleared, kFuUndone };
+struct KfOverlay {
+  int n_slots, n_nodes;
+  int *m_next, *m_tail, *a_head, *node_entry, *node_next;
+};
+struct KfFuseView {
+  int NK, M, list_cap;
+  float xmin, xmax, ymin, ymax, gpw, gph;
+  KfOverlay V;
+  int *first, *head, *base, *targets, *rec, *snap, *list, *key;
+  int4 *mt;
+  size_t reset_bytes;  // from the block's start: everything a call resets
+};
+size_t fuse_bytes(int NK, int max_matches, int n_slots);
+KfFuseView fuse_layout(void *block, int NK, int max_matches, int n_slots, const float bounds[4]);
+struct FuseArgs {
+  KfStoreView S;
+  KfObsView O;
+  KfConnView C;
+  KfCullView X;
+  KfMapView M;
+  KfBaView B;
+  KfUpkeepView U;
+  KfFuseView F;
+  double *normals;
+  int *status;
+};
+// one fuse call on its own: reset, then mark / search / mutate for step 0 over the n ids of a device list
+int fuse_single_enqueue(const FuseArgs &A, int target, int n, const int *dev_ids, float threshold, hipStream_t st);
+// the composed call up to the closing rebuild: reset, target list and snapshot, 60 target steps, the gather, the closing step
+int fuse_neighbors_enqueue(const FuseArgs &A, int current, hipStream_t st);
+// current's live ids, each once, into F.snap (behind the rebuild: the list of the closing descriptors and refresh)
+int fuse_live_list_enqueue(const FuseArgs &A, int current, hipStream_t st);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
