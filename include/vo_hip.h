@@ -1351,6 +1351,84 @@ int vo_kfstore_fuse_map_points(vo_kfstore *s, int target, int n, const int32_t *
 int vo_kfstore_fuse_map_points_dev(vo_kfstore *s, int target, int n, const int32_t *dev_ids, float threshold);
 int vo_kfstore_search_in_neighbors(vo_kfstore *s, int current);
 int vo_kfstore_fuse_result(vo_kfstore *s, int32_t *record /*[8]*/, int32_t *targets /*[61]*/, int32_t *per_target /*[61][6]*/);
+/* Loop Sim3 on the device: LoopClosing::computeSim3 (loopClosing.cpp:178-348) from the store, behind
+ * vo_kfdb_query_loop[_dev] and the host's consistency groups.  Opt-in and additive: a store without it allocates and behaves
+ * as before.  The definitions are section 4i's (HOLDS, OBSERVATION, bad(j)); a map point's position, descriptor, normal and
+ * min / max distance are read at the feature through which the walk meets it.  A Sim3 is 13 doubles as vo_sim3_ransac_eval
+ * writes them: R row-major, t, s.  The CONTRACT is the reference's sequential result.
+ * enable_loop(max_candidates, max_loop_points, max_rand): valid on an EMPTY store on which vo_kfstore_enable_fuse has succeeded
+ * (which implies connections, culling, mapping, local BA, point upkeep: poses, key-point xy / octave, bounds, normals);
+ * max_candidates in [1, VO_KFSTORE_LOOP_MAX_CANDIDATES], max_loop_points >= 1, max_rand >= 3.  One device block of
+ * 129 * max_candidates * max_features + 127 * max_features + 5 * index capacity + 21 * max_loop_points + 4 * max_rand bytes and
+ * a little (alignment, one k_node_replay argument block per candidate); the table ransacMaxIters(N), N <= max_features, is
+ * evaluated here with the host's C library (sim3Solver.cpp:86-93), so the device computes no log.  Synchronises once.
+ * compute_sim3(current, cand[n_cand], fix_scale, rand_values[n_rand], rand_max, max_rounds): current and every candidate in
+ * [0, size) (VO_ERR_INVALID), n_cand <= max_candidates and n_rand <= max_rand (VO_ERR_CAPACITY), rand_max >= 1 (the caller's
+ * RAND_MAX); ONE copy up, the call enqueued, ONE synchronisation at the end.  compute_sim3_dev: cand and rand_values in device
+ * memory, ENQUEUED only -- no host synchronisation, no device-to-host copy, no allocation; the key-frame numbers are checked
+ * on the device (a number outside the store is a bad candidate).  current erased or without a pose: no walk, every result
+ * zero, VO_KFSTORE_CONNECTIONS_INVALID.  Neither form touches an erase lock (vo_kfstore_set_erase_lock): the caller locks the
+ * candidates and current beforehand and releases, by the final state, ACCEPTED: every candidate but the matched one (:331-339);
+ * NO MATCH and REJECTED: every candidate and current (:290-296, :341-346); UNDECIDED: none yet.
+ * 1. Front, all candidates at once: candidate i is discarded when bad(cand[i]) or erased (:210); else
+ *    Matcher(0.75).searchByBoW(current, cand[i], checkRot = true) (matcher.cpp:561-677) over the store's FeatureVectors; fewer
+ *    than 20 matches discard it (:218).
+ * 2. Sim3Solver (sim3Solver.cpp:8-96) per live candidate, in feature order of current: a match at feature i is kept when
+ *    feature i has bit 0 and an id >= 0 that current holds, and the matched feature's id >= 0 is held by the candidate (ids are
+ *    validated where they enter and one call changes nothing, so only a store filled through the device forms can fail this;
+ *    a candidate without a pose keeps no match and its solver stops at once); idx1 / idx2 are the OBSERVATIONS, which need not be i; pcam = Tcw * p in double;
+ *    pixels = Camera::camera2pixel in double with the float intrinsics; maxError = (int)(9.210 * sigma * sigma);
+ *    ransacMaxIters = max(1, min(ceil(log(0.01) / log(1 - pow((float)20 / N, 3))), 300)), 1 at N == 20.
+ * 3. The walk (:234-288): while (candidates > 0 && !matchFlag) for i: iterate(5) on candidate i's solver, whose state persists
+ *    (iterations_global_, inliers_best_, the >= against the best, the > 20 return, the N < 20 exit).  Every trip consumes
+ *    three of rand_values in order, as randomInt does: int(((double)r / ((double)rand_max + 1.0)) * d) over the shrinking
+ *    index list (:125-141).  A non-empty return is VERIFIED: inlierMappoints, searchBySim3(current, cand, ., Scm, 7.5)
+ *    (matcher.cpp:679-865; z < 0 one way, z <= 0 the other), solveLoopSim3 (vo_sim3_solve's contract: Scm is written only when
+ *    both problems ran); >= 20 inliers end the walk with Scw = Scm * Smw, otherwise it resumes behind candidate i.  The record
+ *    reports rand_used.  A trip that would draw past n_rand leaves the call UNDECIDED for good and raises
+ *    VO_KFSTORE_LOOP_RAND_SHORT; 3 * 300 * n_cand values always suffice.  A caller who shares rand() with others pre-draws,
+ *    and afterwards re-seeds and discards rand_used values, so that its generator stands where the reference's would.
+ * 4. Rounds.  A round is "walk to the next verification or to the end, then verify".  max_rounds rounds are enqueued
+ *    unconditionally (five launches each); nothing synchronises in between, and a round whose predecessor finished returns
+ *    at once.  Not finished after max_rounds: UNDECIDED, which is no error and raises nothing;
+ *    compute_sim3_continue(max_rounds) enqueues more rounds on the state as left.  Results do not depend on the split.
+ * 5. After a match (:298-347): the loop points are the ids of ALL of the matched key-frame's ordered list (section 4h) in its
+ *    order, then the matched key-frame itself: bit 0 set, feature order, first occurrence.  The mark is per call, which differs
+ *    from loopPointIdxOfKF_ only for a point marked by an earlier call on the same current.  More than max_loop_points:
+ *    UNDECIDED for good, VO_KFSTORE_LOOP_CAPACITY.  Then searchByProjection(current, Scw, loopPoints, matchMapPoints, 10)
+ *    (matcher.cpp:356-447) with its ordered claims and the :422 index quirk as vo_match_sim3_projection reproduces them;
+ *    match_cnt >= 40 is ACCEPTED, else REJECTED.
+ * loop_result: synchronises; any pointer may be NULL.  record [16] = state (0 UNDECIDED, 1 NO MATCH, 2 REJECTED, 3 ACCEPTED),
+ * matched position in cand and key-frame (-1: none), rounds run, verifications, rand_used, the inlier count of the last
+ * refinement, match_cnt, number of loop points, 0 ...; per_cand [max_candidates][8] = key-frame, discard reason (0 live, 1
+ * bad, 2 below 20 BoW matches, 3 solver stopped), BoW matches, N, ransacMaxIters, iterations_global_, inliers_best_,
+ * verifications; Scm / Scw [13] (Scw behind a match only); match_ids [features of current] = matchMapPoints_ as map-point ids,
+ * -1 for null (behind a match; -1 otherwise); loop_point_ids [max_loop_points] = loopConnectKFMapPoints_ with
+ * *n_loop_points entries (states 2 and 3).  Both lists stay on the device.
+ * loop_solver_inputs(position): Sim3Solver's arrays of candidate `position` of the last call as its constructor left them
+ * (*n = N; pcams1_ / pcams2_ [N][3], pixels1_ / pixels2_ [N][2], maxError1_ / maxError2_ [N], matchedIndexs_ [N]); synchronises;
+ * any array may be NULL. */
+#define VO_KFSTORE_LOOP_MAX_CANDIDATES 16
+#define VO_KFSTORE_LOOP_RAND_SHORT 32
+#define VO_KFSTORE_LOOP_CAPACITY 64
+#define VO_KFSTORE_LOOP_UNDECIDED 0
+#define VO_KFSTORE_LOOP_NO_MATCH 1
+#define VO_KFSTORE_LOOP_REJECTED 2
+#define VO_KFSTORE_LOOP_ACCEPTED 3
+int vo_kfstore_enable_loop(vo_kfstore *s, int max_candidates, int max_loop_points, int max_rand);
+int vo_kfstore_compute_sim3(vo_kfstore *s, int current, int n_cand, const int32_t *cand, int fix_scale, int n_rand,
+                            const int32_t *rand_values, int32_t rand_max, int max_rounds);
+int vo_kfstore_compute_sim3_dev(vo_kfstore *s, int current, int n_cand, const int32_t *dev_cand, int fix_scale, int n_rand,
+                                const int32_t *dev_rand_values, int32_t rand_max, int max_rounds);
+int vo_kfstore_compute_sim3_continue(vo_kfstore *s, int max_rounds);
+int vo_kfstore_loop_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *per_cand /*[max_candidates][8]*/, double *Scm /*[13]*/,
+                           double *Scw /*[13]*/, int32_t *match_ids /*[n of current]*/, int32_t *n_loop_points,
+                           int32_t *loop_point_ids /*[max_loop_points]*/);
+/* Sim3Solver::setRansacParameters(0.99, 20, 300) for n correspondences (sim3Solver.cpp:76-96), on the host: the entry of the
+ * table enable_loop uploads.  1 for n <= 20. */
+int vo_kfstore_loop_ransac_max_iters(int n);
+int vo_kfstore_loop_solver_inputs(vo_kfstore *s, int position, int32_t *n, double *cam1_points, double *cam2_points, double *pixels1,
+                                  double *pixels2, int32_t *max_err1, int32_t *max_err2, int32_t *matched_index);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

@@ -69,6 +69,8 @@ SYMBOLS = [
     "vo_kfstore_recent_points", "vo_kfstore_upkeep_result",
     "vo_kfstore_enable_fuse", "vo_kfstore_fuse_map_points", "vo_kfstore_fuse_map_points_dev", "vo_kfstore_search_in_neighbors",
     "vo_kfstore_fuse_result",
+    "vo_kfstore_enable_loop", "vo_kfstore_compute_sim3", "vo_kfstore_compute_sim3_dev", "vo_kfstore_compute_sim3_continue",
+    "vo_kfstore_loop_result", "vo_kfstore_loop_solver_inputs", "vo_kfstore_loop_ransac_max_iters",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1949,6 +1951,61 @@ class KeyFrameStore:
         n = int(rec[0])
         return dict(targets=[int(t) for t in tg[:n]], per_target=[tuple(int(x) for x in row) for row in per[:n]],
                     totals=tuple(int(x) for x in rec[1:7]))
+
+    LOOP_MAX_CANDIDATES, CONNECTIONS_LOOP_RAND_SHORT, CONNECTIONS_LOOP_CAPACITY = 16, 32, 64
+    LOOP_UNDECIDED, LOOP_NO_MATCH, LOOP_REJECTED, LOOP_ACCEPTED = 0, 1, 2, 3
+    LOOP_RECORD = ("state", "match_pos", "match_kf", "rounds", "verifications", "rand_used", "refine_inliers", "match_cnt", "n_loop_points")
+    LOOP_PER_CANDIDATE = ("kf", "reason", "bow_matches", "n", "max_iters", "iterations", "inliers_best", "verifications")
+
+    def enable_loop(self, max_candidates, max_loop_points, max_rand):
+        """LoopClosing::computeSim3 on the device from now on (DESIGN.md section 4n); valid on an empty store after enable_fuse
+        only.  max_candidates <= LOOP_MAX_CANDIDATES; max_loop_points: the loop points a match may collect; max_rand: the
+        rand() values a call may bring (3 * 300 * candidates always suffice)"""
+        check(lib().vo_kfstore_enable_loop(self._h, int(max_candidates), int(max_loop_points), int(max_rand)), "vo_kfstore_enable_loop")
+        self._loop_caps = (int(max_candidates), int(max_loop_points))
+
+    def compute_sim3(self, current, candidates, rand_values, rand_max, fix_scale=True, max_rounds=8):
+        """computeSim3 for the current key-frame over the candidates in their order, drawing from rand_values.  Lists / numpy
+        arrays are copied and the call synchronises once; device tensors (int32, both) are enqueued only"""
+        if hasattr(candidates, "data_ptr"):
+            _need_tensor(candidates, "int32", None, "compute_sim3")
+            _need_tensor(rand_values, "int32", None, "compute_sim3")
+            check(lib().vo_kfstore_compute_sim3_dev(self._h, int(current), int(candidates.numel()), _p(candidates), int(bool(fix_scale)),
+                                                    int(rand_values.numel()), _p(rand_values), int(rand_max), int(max_rounds)),
+                  "vo_kfstore_compute_sim3_dev")
+            return
+        c, r = np.ascontiguousarray(candidates, np.int32).reshape(-1), np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+        check(lib().vo_kfstore_compute_sim3(self._h, int(current), len(c), _p(c), int(bool(fix_scale)), len(r), _p(r), int(rand_max),
+                                            int(max_rounds)), "vo_kfstore_compute_sim3")
+
+    def compute_sim3_continue(self, max_rounds):
+        """more rounds on the state the last compute_sim3 left; enqueued only"""
+        check(lib().vo_kfstore_compute_sim3_continue(self._h, int(max_rounds)), "vo_kfstore_compute_sim3_continue")
+
+    def loop_result(self, n_current=None):
+        """the last compute_sim3 -> dict over LOOP_RECORD plus per_candidate (dicts over LOOP_PER_CANDIDATE), Scm, Scw [13],
+        match_ids [n_current] and loop_point_ids; synchronises"""
+        C_, P = getattr(self, "_loop_caps", (1, 1))
+        rec, per = np.zeros(16, np.int32), np.zeros((C_, 8), np.int32)
+        Scm, Scw = np.zeros(13), np.zeros(13)
+        mids = np.full(self.max_features, -1, np.int32)
+        nlp, lids = C.c_int32(0), np.zeros(P, np.int32)
+        check(lib().vo_kfstore_loop_result(self._h, _p(rec), _p(per), _p(Scm), _p(Scw), _p(mids), C.byref(nlp), _p(lids)), "vo_kfstore_loop_result")
+        out = {k: int(rec[i]) for i, k in enumerate(self.LOOP_RECORD)}
+        out["per_candidate"] = [{k: int(row[i]) for i, k in enumerate(self.LOOP_PER_CANDIDATE)} for row in per]
+        out.update(Scm=Scm, Scw=Scw, match_ids=mids if n_current is None else mids[:n_current], loop_point_ids=lids[:nlp.value].copy())
+        return out
+
+    def loop_solver_inputs(self, position):
+        """Sim3Solver's arrays of candidate `position` of the last compute_sim3 -> dict(pc1, pc2 [N, 3], px1, px2 [N, 2], me1, me2,
+        index [N]); synchronises"""
+        n, NK = C.c_int32(0), self.max_features
+        pc1, pc2, px1, px2 = np.zeros((NK, 3)), np.zeros((NK, 3)), np.zeros((NK, 2)), np.zeros((NK, 2))
+        me1, me2, idx = np.zeros(NK, np.int32), np.zeros(NK, np.int32), np.zeros(NK, np.int32)
+        check(lib().vo_kfstore_loop_solver_inputs(self._h, int(position), C.byref(n), _p(pc1), _p(pc2), _p(px1), _p(px2), _p(me1), _p(me2),
+                                                  _p(idx)), "vo_kfstore_loop_solver_inputs")
+        N = n.value
+        return dict(pc1=pc1[:N], pc2=pc2[:N], px1=px1[:N], px2=px2[:N], me1=me1[:N], me2=me2[:N], index=idx[:N])
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -18,6 +18,7 @@
 // write disjoint ids and disjoint features, so every byte has one writer per launch.
 #include "vo_common.h"
 
+#include "kf_area.h"
 #include "new_points_geom.h"
 #include "obs_walk.h"
 
@@ -28,7 +29,7 @@ using namespace vo;
 constexpr int kMaxC = kFuseMaxCarriers;
 constexpr int kMutateGrid = 256, kSearchGrid = 1024;
 constexpr int kThLow = 50;
-constexpr int kGridCols = 64, kGridRows = 48;
+constexpr int kGridCols = kAreaCols, kGridRows = kAreaRows;
 
 __device__ __forceinline__ int n_features(const KfStoreView &S, int k) { return min(max(kf_head(S, k)[0], 0), S.NK); }
 __device__ __forceinline__ bool kf_bad(const KfStoreView &S, int k) { return kf_head(S, k)[1] != 0; }
@@ -187,28 +188,18 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, int step, const
     if (dist < __fmul_rn(0.8f, mind) || dist > __fmul_rn(1.2f, maxd)) continue;  // (:1055, mappoint.cpp:391-401)
     const double *pn = A.O.normals + ((size_t)kk * NK + ff) * 3;
     if (np_dot3(line[0], pn[0], line[1], pn[1], line[2], pn[2]) < __dmul_rn(0.5, (double)dist)) continue;  // (:1059)
-    const float ratio = __fdiv_rn(maxd, dist);  // predictScale (mappoint.cpp:198-212), as reloc.hip does it
-    const float lg = (float)log((double)ratio);
-    const int sc = (int)ceilf(__fdiv_rn(lg, log_sf1));
-    const int level = sc < 0 ? 0 : (sc >= n_levels ? n_levels - 1 : sc);
+    const int level = predict_level(maxd, dist, log_sf1, n_levels);  // predictScale (mappoint.cpp:198-212)
     const float radius = __fmul_rn(threshold, A.M.sf[level]);
     if (lane == 0) atomicAdd(rec + kFuPassed, 1);
-    // getFeaturesInArea (keyframe.cpp:268-309): the floor-computed cell range
-    const float gpw = A.F.gpw, gph = A.F.gph;
-    const int x0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(u, A.F.xmin), radius), gpw)));
-    const int x1 = min(kGridCols - 1, (int)floorf(__fmul_rn(__fadd_rn(__fsub_rn(u, A.F.xmin), radius), gpw)));
-    const int y0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(v, A.F.ymin), radius), gph)));
-    const int y1 = min(kGridRows - 1, (int)floorf(__fmul_rn(__fadd_rn(__fsub_rn(v, A.F.ymin), radius), gph)));
-    if (x0 >= kGridCols || x1 < 0 || y0 >= kGridRows || y1 < 0) continue;
+    const AreaWindow W = area_window(A.F, u, v, radius);  // getFeaturesInArea (keyframe.cpp:268-309), kf_area.h
+    if (!W.any) continue;
     const uint4 *qd = reinterpret_cast<const uint4 *>(record_of(S, kk) + S.o_pdesc) + 2 * (size_t)ff;
     const uint4 qa = qd[0], qb = qd[1];
     unsigned long long best = ~0ull;
     for (int f = lane; f < nT; f += 64) {
       const float4 t = s_feat[f];
-      // the feature's own cell is ROUNDED (frame.cpp:83-86); outside the grid it is in no cell
-      const int gx = (int)roundf(__fmul_rn(__fsub_rn(t.x, A.F.xmin), gpw)), gy = (int)roundf(__fmul_rn(__fsub_rn(t.y, A.F.ymin), gph));
-      if (gx < 0 || gx >= kGridCols || gy < 0 || gy >= kGridRows || gx < x0 || gx > x1 || gy < y0 || gy > y1) continue;
-      if (!(fabsf(__fsub_rn(t.x, u)) < radius && fabsf(__fsub_rn(t.y, v)) < radius)) continue;
+      int gx, gy;
+      if (!area_holds(A.F, W, t.x, t.y, u, v, radius, gx, gy)) continue;
       const int oct = __float_as_int(t.w);
       if (oct < level - 1 || oct > level) continue;  // (:1077)
       const float ex = __fsub_rn(u, t.x), ey = __fsub_rn(v, t.y);
@@ -221,10 +212,7 @@ __global__ __launch_bounds__(256) void k_fuse_search(FuseArgs A, int step, const
       if (__fmul_rn(__fmul_rn(e2, inv), inv) > th) continue;  // (:1090, :1097)
       const uint4 *dd = reinterpret_cast<const uint4 *>(kf_sec<uint8_t>(S, T, S.o_desc)) + 2 * (size_t)f;
       const uint4 da = dd[0], db = dd[1];
-      const int d = __popc(qa.x ^ da.x) + __popc(qa.y ^ da.y) + __popc(qa.z ^ da.z) + __popc(qa.w ^ da.w) + __popc(qb.x ^ db.x) +
-                    __popc(qb.y ^ db.y) + __popc(qb.z ^ db.z) + __popc(qb.w ^ db.w);
-      // the strictly smallest distance in the visiting order: cell column, cell row, feature
-      const unsigned long long key = ((unsigned long long)d << 44) | ((unsigned long long)gx << 38) | ((unsigned long long)gy << 32) | (unsigned)f;
+      const unsigned long long key = area_key(hamming256(qa, qb, da, db), gx, gy, f);
       best = key < best ? key : best;
     }
     best = wave_min_u64(best);

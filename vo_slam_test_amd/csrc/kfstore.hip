@@ -121,6 +121,11 @@ struct vo_kfstore {
   vo::OwnedDevBuf fu;                 // vo_kfstore_enable_fuse: the block of section 4m
   vo::KfFuseView F{};
   bool fuse = false;
+  vo::OwnedDevBuf lp;                 // vo_kfstore_enable_loop: the block of section 4n
+  vo::OwnedPinnedBuf lp_stage;        // a host form's candidates and rand() values going up, the results coming down: one copy each
+  vo::KfLoopView L{};
+  bool loop = false, loop_called = false;
+  int loop_fix_scale = 1;             // of the last compute_sim3: what compute_sim3_continue refines with
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -242,6 +247,12 @@ int need_upkeep(const vo_kfstore *s, const char *call) {
 int need_fuse(const vo_kfstore *s, const char *call) {
   if (s && s->fuse) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_fuse has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_loop(const vo_kfstore *s, const char *call) {
+  if (s && s->loop) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_loop has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -1328,6 +1339,138 @@ int vo_kfstore_fuse_result(vo_kfstore *s, int32_t *record, int32_t *targets, int
   if (targets) memcpy(targets, out_t, sizeof(out_t));
   if (per_target) memcpy(per_target, out_p, sizeof(out_p));
   return VO_OK;
+}
+
+int vo_kfstore_enable_loop(vo_kfstore *s, int max_candidates, int max_loop_points, int max_rand) {
+  const char *W = "vo_kfstore_enable_loop";
+  VO_CHECK(need_fuse(s, W));
+  if (max_candidates < 1 || max_candidates > VO_KFSTORE_LOOP_MAX_CANDIDATES || max_loop_points < 1 || max_rand < 3) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->loop) return VO_OK;
+  const size_t bytes = vo::loop_bytes(s->NK, max_candidates, max_loop_points, max_rand, s->okeys_cap);
+  VO_CHECK(s->lp.reserve(bytes));
+  s->L = vo::loop_layout(s->lp.p, s->NK, max_candidates, max_loop_points, max_rand, s->okeys_cap);
+  const size_t down = (size_t)(vo::kLoopStateInts + VO_KFSTORE_LOOP_MAX_CANDIDATES * vo::kLoopPerInts + s->NK + max_loop_points) * 4 + 26 * 8;
+  VO_CHECK(s->lp_stage.reserve(std::max(((size_t)VO_KFSTORE_LOOP_MAX_CANDIDATES + (size_t)max_rand) * 4, down)));
+  VO_CHECK(vo::loop_init(s->L, s->M, bytes, s->st));  // (synchronises: its tables are host temporaries)
+  s->loop = true;
+  return VO_OK;
+}
+
+static vo::LoopArgs loop_args(vo_kfstore *s, const vo::KfObsView &O) {
+  const vo::KfConnView C = vo::connections_view(s->conn);
+  return vo::LoopArgs{vo::kfstore_view(s), O, C, s->X, s->M, s->F, s->L, C.status};
+}
+
+// the candidates and the rand() values are in the block already (L.cand, L.rand)
+static int loop_compute_enqueue(vo_kfstore *s, int current, int n_cand, int fix_scale, int n_rand, int32_t rand_max, int max_rounds) {
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));  // "who observes p in key-frame j" (launches only, and only when the index is stale)
+  const vo::LoopArgs A = loop_args(s, O);
+  VO_CHECK(vo::loop_begin_enqueue(A, current, n_cand, fix_scale ? 1 : 0, n_rand, rand_max, s->st));
+  s->loop_fix_scale = fix_scale ? 1 : 0, s->loop_called = true;
+  return vo::loop_rounds_enqueue(A, max_rounds, s->loop_fix_scale, s->st);
+}
+
+static int loop_check(vo_kfstore *s, const char *W, int n_cand, const void *cand, int n_rand, const void *rand_values, int32_t rand_max,
+                      int max_rounds) {
+  VO_CHECK(need_loop(s, W));
+  if (n_cand < 1 || !cand || n_rand < 0 || (n_rand > 0 && !rand_values) || rand_max < 1 || max_rounds < 0) return VO_ERR_INVALID;
+  if (n_cand > s->L.C || n_rand > s->L.max_rand) {
+    vo::set_error("%s: %d candidates / %d rand() values, the block was enabled for %d / %d", W, n_cand, n_rand, s->L.C, s->L.max_rand);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+int vo_kfstore_compute_sim3_dev(vo_kfstore *s, int current, int n_cand, const int32_t *dev_cand, int fix_scale, int n_rand,
+                                const int32_t *dev_rand_values, int32_t rand_max, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3_dev";
+  VO_CHECK(loop_check(s, W, n_cand, dev_cand, n_rand, dev_rand_values, rand_max, max_rounds));
+  VO_HIP_CHECK(hipMemcpyAsync(s->L.cand, dev_cand, (size_t)n_cand * 4, hipMemcpyDeviceToDevice, s->st));
+  if (n_rand > 0) VO_HIP_CHECK(hipMemcpyAsync(s->L.rand, dev_rand_values, (size_t)n_rand * 4, hipMemcpyDeviceToDevice, s->st));
+  return loop_compute_enqueue(s, current, n_cand, fix_scale, n_rand, rand_max, max_rounds);
+}
+
+int vo_kfstore_compute_sim3(vo_kfstore *s, int current, int n_cand, const int32_t *cand, int fix_scale, int n_rand,
+                            const int32_t *rand_values, int32_t rand_max, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3";
+  VO_CHECK(loop_check(s, W, n_cand, cand, n_rand, rand_values, rand_max, max_rounds));
+  VO_CHECK(need_keyframe(s, W, current));
+  for (int i = 0; i < n_cand; i++) VO_CHECK(need_keyframe(s, W, cand[i]));
+  // one copy: [16 candidates | rand() values] lands on L.cand .. L.rand, which the block keeps side by side
+  int32_t *up = reinterpret_cast<int32_t *>(s->lp_stage.data());
+  memset(up, 0xff, VO_KFSTORE_LOOP_MAX_CANDIDATES * 4);
+  memcpy(up, cand, (size_t)n_cand * 4);
+  if (n_rand > 0) memcpy(up + VO_KFSTORE_LOOP_MAX_CANDIDATES, rand_values, (size_t)n_rand * 4);
+  VO_CHECK(vo::copy_h2d(s->L.cand, up, ((size_t)VO_KFSTORE_LOOP_MAX_CANDIDATES + (size_t)n_rand) * 4, s->st, W));
+  VO_CHECK(loop_compute_enqueue(s, current, n_cand, fix_scale, n_rand, rand_max, max_rounds));
+  return vo::stream_sync(s->st, W);
+}
+
+int vo_kfstore_compute_sim3_continue(vo_kfstore *s, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3_continue";
+  VO_CHECK(need_loop(s, W));
+  if (max_rounds < 0) return VO_ERR_INVALID;
+  if (!s->loop_called) {
+    vo::set_error("%s: no vo_kfstore_compute_sim3 has been enqueued on this store", W);
+    return VO_ERR_INVALID;
+  }
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));
+  return vo::loop_rounds_enqueue(loop_args(s, O), max_rounds, s->loop_fix_scale, s->st);
+}
+
+int vo_kfstore_loop_result(vo_kfstore *s, int32_t *record, int32_t *per_cand, double *Scm, double *Scw, int32_t *match_ids,
+                           int32_t *n_loop_points, int32_t *loop_point_ids) {
+  const char *W = "vo_kfstore_loop_result";
+  VO_CHECK(need_loop(s, W));
+  const vo::KfLoopView &L = s->L;
+  int32_t st[vo::kLoopStateInts], per[VO_KFSTORE_LOOP_MAX_CANDIDATES * vo::kLoopPerInts];
+  double sims[26];
+  VO_CHECK(vo::copy_d2h(st, L.st, sizeof(st), s->st, W));
+  VO_CHECK(vo::copy_d2h(per, L.per, sizeof(per), s->st, W));
+  VO_CHECK(vo::copy_d2h(sims, L.Scm, 13 * 8, s->st, W));
+  VO_CHECK(vo::copy_d2h(sims + 13, L.Scw, 13 * 8, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  const int n_cur = std::min(std::max(st[vo::kLsNCur], 0), s->NK), n_lp = st[vo::kLsState] >= 2 ? std::min(std::max(st[vo::kLsNLoop], 0), L.P) : 0;
+  if (match_ids && n_cur > 0) VO_CHECK(vo::copy_d2h(match_ids, L.match_ids, (size_t)n_cur * 4, s->st, W));
+  if (loop_point_ids && n_lp > 0) VO_CHECK(vo::copy_d2h(loop_point_ids, L.loop_ids, (size_t)n_lp * 4, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  if (record) {
+    memset(record, 0, 16 * 4);
+    memcpy(record, st, 9 * 4);
+  }
+  if (per_cand) memcpy(per_cand, per, (size_t)L.C * vo::kLoopPerInts * 4);
+  if (Scm) memcpy(Scm, sims, 13 * 8);
+  if (Scw) memcpy(Scw, sims + 13, 13 * 8);
+  if (n_loop_points) *n_loop_points = n_lp;
+  return VO_OK;
+}
+
+int vo_kfstore_loop_solver_inputs(vo_kfstore *s, int position, int32_t *n, double *cam1_points, double *cam2_points, double *pixels1,
+                                  double *pixels2, int32_t *max_err1, int32_t *max_err2, int32_t *matched_index) {
+  const char *W = "vo_kfstore_loop_solver_inputs";
+  VO_CHECK(need_loop(s, W));
+  const vo::KfLoopView &L = s->L;
+  if (position < 0 || position >= L.C || !n) return VO_ERR_INVALID;
+  int32_t per[vo::kLoopPerInts];
+  VO_CHECK(vo::copy_d2h(per, L.per + position * vo::kLoopPerInts, sizeof(per), s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  const size_t N = (size_t)std::min(std::max(per[vo::kLpN], 0), s->NK), o = (size_t)position * s->NK;
+  *n = (int32_t)N;
+  if (N == 0) return VO_OK;
+  if (cam1_points) VO_CHECK(vo::copy_d2h(cam1_points, L.pc1 + o * 3, N * 24, s->st, W));
+  if (cam2_points) VO_CHECK(vo::copy_d2h(cam2_points, L.pc2 + o * 3, N * 24, s->st, W));
+  if (pixels1) VO_CHECK(vo::copy_d2h(pixels1, L.px1 + o * 2, N * 16, s->st, W));
+  if (pixels2) VO_CHECK(vo::copy_d2h(pixels2, L.px2 + o * 2, N * 16, s->st, W));
+  if (max_err1) VO_CHECK(vo::copy_d2h(max_err1, L.me1 + o, N * 4, s->st, W));
+  if (max_err2) VO_CHECK(vo::copy_d2h(max_err2, L.me2 + o, N * 4, s->st, W));
+  if (matched_index) VO_CHECK(vo::copy_d2h(matched_index, L.midx + o, N * 4, s->st, W));
+  return vo::stream_sync(s->st, W);
 }
 
 }  // extern "C"

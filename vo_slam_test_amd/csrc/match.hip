@@ -1355,6 +1355,89 @@ __global__ __launch_bounds__(64) void k_tri_walk(TriWalkArgs A) {
   }
 }
 
+// The store-to-store walk of the loop front: pair c = (`current`, cand[c]), a wavefront per candidate,
+// searchByBoW(KeyFrame*, KeyFrame*) (matcher.cpp:561-677).  A feature of `current` is a query when its node is shared and it
+// has a map point (flags bit 0, :591-593); a feature of the candidate may be claimed when it has one (:606-609) -- bok.  A
+// candidate that is no key-frame of the store, is erased or flagged bad (loopClosing.cpp:210), or `current` erased or without a
+// pose, leaves nq = nA = 0: k_node_replay then writes nothing but a match count of 0.
+struct LoopWalkArgs {
+  vo::KfStoreView S;
+  vo::KfCullView X;
+  vo::KfMapView M;
+  vo::KfLoopView L;
+  int current;
+};
+__global__ __launch_bounds__(64) void k_loop_bow_walk(LoopWalkArgs A) {
+  const int c = blockIdx.x, lane = threadIdx.x, cur = A.current, NK = A.S.NK;
+  const vo::KfLoopView &L = A.L;
+  const int kf = L.cand[c];
+  const bool cur_ok = cur >= 0 && cur < A.S.size && !A.X.erased[cur] && *vo::np_pose_set(A.M, cur) != 0;
+  const bool go = cur_ok && kf >= 0 && kf < A.S.size && !A.X.erased[kf] && !vo::kf_head(A.S, kf)[1];
+  int4 *Q = L.queries + (size_t)c * NK;
+  uint8_t *bok = L.bok + (size_t)c * NK;
+  int nq = 0, nA = 0, nB = 0;
+  if (go) {
+    const int *headA = vo::kf_head(A.S, cur), *headB = vo::kf_head(A.S, kf);
+    nA = min(max(headA[0], 0), NK), nB = min(max(headB[0], 0), NK);
+    const int nnA = min(max(headA[2], 0), NK), nnB = min(max(headB[2], 0), NK);
+    const uint8_t *flagsA = vo::kf_sec<uint8_t>(A.S, cur, A.S.o_flags), *flagsB = vo::kf_sec<uint8_t>(A.S, kf, A.S.o_flags);
+    for (int i = lane; i < nB; i += 64) bok[i] = (flagsB[i] & 1) ? 1 : 0;
+    if (nA > 0 && nB > 0 && nnA > 0 && nnB > 0) {
+      const int *nodeA = vo::kf_sec<int>(A.S, cur, A.S.o_node), *startA = vo::kf_sec<int>(A.S, cur, A.S.o_start);
+      const int *featA = vo::kf_sec<int>(A.S, cur, A.S.o_feat);
+      const int *nodeB = vo::kf_sec<int>(A.S, kf, A.S.o_node), *startB = vo::kf_sec<int>(A.S, kf, A.S.o_start);
+      const int total = min(max(startA[nnA], 0), NK);
+      for (int b = 0; b < total; b += 64) {
+        const int t = b + lane;
+        bool emit = false;
+        int4 q = make_int4(0, 0, 0, 0);
+        if (t < total) {
+          int lo = 0, hi = nnA;  // first node whose start is beyond t; the entry belongs to the node before it
+          while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (startA[mid] <= t) lo = mid + 1;
+            else hi = mid;
+          }
+          const int nd = nodeA[max(lo - 1, 0)];
+          int l2 = 0, h2 = nnB;  // first node of B >= nd
+          while (l2 < h2) {
+            const int mid = (l2 + h2) >> 1;
+            if (nodeB[mid] < nd) l2 = mid + 1;
+            else h2 = mid;
+          }
+          if (l2 < nnB && nodeB[l2] == nd) {
+            const int i1 = featA[t];
+            const int s0 = min(max(startB[l2], 0), NK), s1 = min(max(startB[l2 + 1], s0), NK);
+            if (i1 >= 0 && i1 < nA && (flagsA[i1] & 1)) {
+              emit = true;
+              q = make_int4(i1, s0, s1, 0);
+            }
+          }
+        }
+        const unsigned long long mk = __builtin_amdgcn_ballot_w64(emit);
+        const int within = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(mk >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)mk, 0u));
+        if (emit) Q[nq + within] = q;
+        nq += (int)__popcll(mk);
+      }
+    }
+  }
+  if (lane == 0) {
+    NodeArgs &P = reinterpret_cast<NodeArgs *>(L.args)[c];
+    P.mode = kNodeBow1, P.nq = nq, P.nA = nA, P.nB = nB, P.check_rot = 1;
+    P.ratio = 0.75f, P.ex = 0.f, P.ey = 0.f;  // Matcher matcher(0.75) (loopClosing.cpp:182)
+    for (int i = 0; i < 9; i++) P.F[i] = 0.0;
+    for (int i = 0; i < 16; i++) P.sf[i] = 1.f;
+    const int a = cur_ok ? cur : 0, b = go ? kf : a;
+    P.queries = Q, P.bfeat = vo::kf_sec<uint32_t>(A.S, b, A.S.o_feat);
+    P.descA = vo::kf_sec<uint4>(A.S, a, A.S.o_desc), P.descB = vo::kf_sec<uint4>(A.S, b, A.S.o_desc);
+    P.angA = vo::kf_sec<float>(A.S, a, A.S.o_angle), P.angB = vo::kf_sec<float>(A.S, b, A.S.o_angle);
+    P.xA = P.yA = P.urA = P.xB = P.yB = P.urB = nullptr, P.octB = nullptr;
+    P.b_ok = bok;
+    P.claims = L.claims + (size_t)c * NK;
+    P.match = L.match12 + (size_t)c * NK, P.n_matches = L.nm + c;
+  }
+}
+
 __global__ __launch_bounds__(256) void k_fill_u8(uint8_t *p, int n, uint8_t v) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) p[i] = v;
@@ -1455,6 +1538,18 @@ int vo::tri_walk_replay(const vo::KfStoreView &S, const vo::KfCullView &X, const
   const size_t lds = (((size_t)S.NK + 15) & ~(size_t)15) * 5;  // taken[] / tmpb[] for the store's capacity
   if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
   hipLaunchKernelGGL(k_node_replay, dim3(1), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(M.args));
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+int vo::loop_bow_replay(const vo::LoopArgs &A, int current, int n_cand, hipStream_t st) {
+  if (A.S.NK > kNodeMaxB || n_cand < 1 || n_cand > A.L.C) return VO_ERR_INVALID;
+  LoopWalkArgs W{A.S, A.X, A.M, A.L, current};
+  hipLaunchKernelGGL(k_loop_bow_walk, dim3((unsigned)n_cand), dim3(64), 0, st, W);
+  VO_HIP_CHECK(hipGetLastError());
+  const size_t lds = (((size_t)A.S.NK + 15) & ~(size_t)15) * 5;  // taken[] / tmpb[] for the store's capacity
+  if (lds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_node_replay, hipFuncAttributeMaxDynamicSharedMemorySize, kNodeMaxB * 5);
+  hipLaunchKernelGGL(k_node_replay, dim3((unsigned)n_cand), dim3(64), lds, st, reinterpret_cast<const NodeArgs *>(A.L.args));
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }

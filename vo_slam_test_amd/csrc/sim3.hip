@@ -301,6 +301,20 @@ __global__ __launch_bounds__(256) void k_sim3(const int *offsets, const double *
 
 }  // namespace
 
+int vo::sim3_solve_dev(int n_problems, int fix_scale, const int *off, const double *Pm, const double *pxc, const double *isc,
+                       const double *Pc, const double *pxm, const double *ism, const double *cam4, double *poses, double *scales,
+                       uint8_t *outlier, int *n_inliers, vo_lm_summary *sums, hipStream_t st) {
+  if (n_problems < 1) return VO_ERR_INVALID;
+  if (fix_scale)
+    hipLaunchKernelGGL(k_sim3<6>, dim3(n_problems), dim3(256), 0, st, off, Pm, pxc, isc, Pc, pxm, ism, cam4, poses, scales, outlier, n_inliers,
+                       sums);
+  else
+    hipLaunchKernelGGL(k_sim3<7>, dim3(n_problems), dim3(256), 0, st, off, Pm, pxc, isc, Pc, pxm, ism, cam4, poses, scales, outlier, n_inliers,
+                       sums);
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
 extern "C" {
 
 int vo_sim3_solve(int n_problems, const int32_t *offsets, const double *cam_match, const double *pix_curr,

@@ -529,6 +529,66 @@ int fuse_neighbors_enqueue(const FuseArgs &A, int current, hipStream_t st);
 // current's live ids, each once, into F.snap (behind the rebuild: the list of the closing descriptors and refresh)
 int fuse_live_list_enqueue(const FuseArgs &A, int current, hipStream_t st);
 
+// Loop Sim3 on the device (loop_sim3.hip, match.hip, sim3.hip): LoopClosing::computeSim3 from the
+// store.  What vo_kfstore_enable_loop allocates, one block (C = max_candidates, P = max_loop_points, n_slots = the observation
+// index's capacity).  st [kLoopStateInts]: the record (entries 0 .. 8, include/vo_hip.h) and the walk's own words (enum below);
+// cand [16]; rand [max_rand]; iters [NK + 1], ransacMaxIters by N, tabulated on the host; per [16][8]; the FRONT, per
+// candidate: queries / claims [NK], k_node_replay's argument block, bok [NK] (features of the candidate that may be claimed),
+// match12 [NK] (searchByBoW's result: feature of the candidate per feature of `current`), nm; the SOLVERS, per candidate:
+// pc1 / pc2 [NK][3], px1 / px2 [NK][2], me1 / me2 / midx [NK] (Sim3Solver's pcams, pixels, maxError and matchedIndexs_);
+// tflags [5][NK], the inlier flags of the up-to-five trips of one iterate call; a VERIFICATION: inl [NK] (inlierMappoints as
+// features of the candidate, -1: null), m2on [NK] (matched2), m1 / m2 [NK] (searchBySim3's two directions), the refinement's
+// inputs Pm Pc [NK][3], pxc pxm [NK][2], isc ism [NK], sidx [NK], off [2], pose [6], scale, outl [NK], ninl, sums [2]; Scm,
+// Scw [13]; AFTER a match: mark [n_slots] (the first list position of an id), fnd [n_slots] bytes (the id is in
+// matchMapPoints_), loop_ids [P] with their list positions qg [P] and the projection's qu qv qlv qok [P], and match_ids [NK].
+constexpr int kLoopStateInts = 32, kLoopPerInts = 8, kLoopTrips = 5;
+enum { kLsState = 0, kLsMatchPos, kLsMatchKf, kLsRounds, kLsVerifs, kLsRandUsed, kLsRefine, kLsMatchCnt, kLsNLoop,
+       kLsCurrent = 16, kLsNCand, kLsFixScale, kLsNRand, kLsRandMax, kLsCursor, kLsLive, kLsPhase, kLsPending, kLsNCur };
+enum { kLoopWalk = 0, kLoopVerify, kLoopAfter, kLoopDone, kLoopHalt };  // st[kLsPhase]
+enum { kLpKf = 0, kLpReason, kLpBow, kLpN, kLpMaxIters, kLpIters, kLpBest, kLpVerifs };
+struct KfLoopView {
+  int NK, C, P, max_rand, n_slots;
+  int *st, *cand, *rand, *iters, *per;
+  int4 *queries, *claims;
+  uint8_t *args, *bok;
+  int *match12, *nm;
+  double *pc1, *pc2, *px1, *px2;
+  int *me1, *me2, *midx;
+  uint8_t *tflags;
+  int *inl, *m1, *m2, *sidx, *off, *ninl;
+  uint8_t *m2on, *outl;
+  double *Pm, *Pc, *pxc, *pxm, *isc, *ism, *pose, *scale, *Scm, *Scw, *cam4;
+  vo_lm_summary *sums;
+  unsigned *mark;
+  uint8_t *fnd, *qok;
+  int *loop_ids, *qlv, *qg, *match_ids;
+  float *qu, *qv;
+};
+size_t loop_bytes(int NK, int max_cand, int max_pts, int max_rand, int n_slots);
+KfLoopView loop_layout(void *block, int NK, int max_cand, int max_pts, int max_rand, int n_slots);
+struct LoopArgs {
+  KfStoreView S;
+  KfObsView O;
+  KfConnView C;
+  KfCullView X;
+  KfMapView M;
+  KfFuseView F;  // the image bounds and the grid pitch
+  KfLoopView L;
+  int *status;
+};
+// the tables and constants of the block, once (ransacMaxIters by N from the host's libm; the camera as doubles)
+int loop_init(const KfLoopView &L, const KfMapView &M, size_t bytes, hipStream_t st);
+// a new call: the state reset, `current` checked, the front (match.hip: loop_bow_replay) and the solvers' construction
+int loop_begin_enqueue(const LoopArgs &A, int current, int n_cand, int fix_scale, int n_rand, int rand_max, hipStream_t st);
+// `rounds` rounds (walk to the next verification or to the end, then verify), then the steps behind a match; launches only
+int loop_rounds_enqueue(const LoopArgs &A, int rounds, int fix_scale, hipStream_t st);
+// the front's searchByBoW(current, cand[c], mode 1, checkRot) for c < n_cand in ONE k_node_replay launch (match.hip)
+int loop_bow_replay(const LoopArgs &A, int current, int n_cand, hipStream_t st);
+// k_sim3 (sim3.hip) on device-resident inputs: problem p owns off[p] .. off[p + 1]; nothing is copied or synchronised
+int sim3_solve_dev(int n_problems, int fix_scale, const int *off, const double *Pm, const double *pxc, const double *isc, const double *Pc,
+                   const double *pxm, const double *ism, const double *cam4, double *poses, double *scales, uint8_t *outlier, int *n_inliers,
+                   vo_lm_summary *sums, hipStream_t st);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
