@@ -967,7 +967,7 @@ int vo_kfstore_set_normals(vo_kfstore *s, int keyframe, const double *normals /*
  * n_ordered: -1 / 0); parent = getParent() or -1; n_children, children [VO_KFSTORE_MAX_CHILDREN] = the graph row's
  * (entries beyond n_children: -1).
  * A store with culling (below) skips a listed key-frame that has been erased like a number outside the store.
- * Not covered: loop edges. */
+ * Loop edges: vo_kfstore_add_loop_edge below, on a store with that block. */
 #define VO_KFSTORE_CONNECTIONS_MAX_KEYFRAMES 4096
 #define VO_KFSTORE_CONNECTIONS_INVALID 1
 #define VO_KFSTORE_CONNECTIONS_CAPACITY 2
@@ -1429,6 +1429,93 @@ int vo_kfstore_loop_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *per
 int vo_kfstore_loop_ransac_max_iters(int n);
 int vo_kfstore_loop_solver_inputs(vo_kfstore *s, int position, int32_t *n, double *cam1_points, double *cam2_points, double *pixels1,
                                   double *pixels2, int32_t *max_err1, int32_t *max_err2, int32_t *matched_index);
+/* The loop pose graph from the store: Optimizer::solvePoseGraphLoop (optimizer_ceres.cpp:1036-1305) with
+ * the pose collection (:1062-1083) and the four edge families (:1094-1236) gathered on the device, and the write-back of
+ * every key-frame pose (:1264-1278) and every map point (:1281-1301) done there; the solve in between is
+ * vo_pose_graph_solve's, unchanged.  It takes LoopClosing::correctLoop's outputs as plain arrays, so a host correctLoop can
+ * drive it.  Opt-in and additive: a store without it allocates and behaves as before, and every entry point of this block
+ * returns VO_ERR_INVALID on it.  bad(j) and "erased" are section 4i's; pointer-keyed containers are walked in ascending
+ * key-frame number.  A Sim3 is 8 doubles as vo_sim3_reanchor_points takes them: quaternion x y z w, translation, scale; every
+ * Sim3 an entry point receives has its quaternion normalised when it is read.  All Sim3 arithmetic is csrc/sim3_compose.h's:
+ * double, a fixed operation order, every operation rounded on its own (DESIGN.md section 4o writes the order down).
+ * enable_pose_graph(max_edges, max_corrected, max_corrected_points): valid only on an EMPTY store on which
+ * vo_kfstore_enable_local_ba has succeeded, else VO_ERR_INVALID; capacities below 1 are VO_ERR_INVALID.  Allocates, with K =
+ * max_keyframes, N = max_features, Nn = min(K, 683) (the solver's 6 (nodes - 1) <= 4096), E / C / P the capacities and every
+ * array rounded up to 16 bytes: the loop-edge rows and counts (36 K); node index, edge counts and the refresh list
+ * (4 K N + 8 K + 4 C + 4); S_wr (64 Nn); a window's inputs (136 C + 4 E + 8 P + 4); the window -- the record (64), nodes
+ * (68 Nn), edges (72 E); a solver's result (56 Nn): 4 K N + 44 K + 188 Nn + 76 E + 140 C + 8 P + 72 bytes as listed,
+ * 2 813 160 at 500 key-frames of 1000 features with 8192 edges, 64 corrected key-frames and 8192 corrected points; and ONE
+ * page-locked staging block of the largest of the window, the inputs and the result (host memory, 623 888 bytes there, before
+ * the allocator's headroom).  Synchronises once.
+ * add_loop_edge(a, b): KeyFrame::addLoopEdge both ways (loopClosing.cpp:484-485, keyframe.cpp:528-533): b joins a's loop
+ * edges and a joins b's, and both get the erase lock of vo_kfstore_set_erase_lock(.., 1).  A repeat changes nothing.  At
+ * most VO_KFSTORE_MAX_LOOP_EDGES per key-frame: VO_ERR_CAPACITY beyond, with nothing written.  a, b in [0, size), a != b, else
+ * VO_ERR_INVALID.  Enqueues only.  get_loop_edges: synchronises; *n and edges [VO_KFSTORE_MAX_LOOP_EDGES] ascending.
+ * pose_graph_window(curr, match, ...): corr_kf [n_corr] strictly ascending = the key set of both correctSim3 and
+ * uncorrectSim3 (currConnectKFs_ with curr, loopClosing.cpp:367-398), S_corr / S_uncorr [n_corr][8]; lc_start [n_corr + 1]
+ * (lc_start[0] == 0) and lc_kf = loopConnections as CSR over the same keys, each row strictly ascending; cp_id [n_cp] strictly
+ * ascending with cp_ref = the points with loopCorrectByKF_ == curr and their correctReference_.  The host form validates all
+ * of that, every number against [0, size) (ids: >= 0) and the counts against the capacities (VO_ERR_CAPACITY) before anything
+ * is enqueued (VO_ERR_INVALID, nothing changes); ONE copy, four launches, synchronises once.  pose_graph_window_dev: the same
+ * arrays in device memory with n_lc given; curr, match and the counts are validated, the arrays are copied device to device
+ * and everything is ENQUEUED only -- no host synchronisation, no device-to-host copy, no allocation; what the host form
+ * validates is checked on the device: a violation gives status EMPTY and the sticky VO_KFSTORE_CONNECTIONS_INVALID.  The
+ * window is that of the reference called once:
+ *  1 nodes: the key-frames that are not erased, ascending and compacted; node_kf[i] = the key-frame of node i.  More than Nn
+ *    nodes or more than max_edges edges: status OVERFLOW, the record holds the TRUE counts, no array is valid, the sticky
+ *    VO_KFSTORE_POSE_GRAPH_CAPACITY is raised.  curr or match erased, or any node without a pose: status EMPTY and the sticky
+ *    VO_KFSTORE_CONNECTIONS_INVALID (vo_kfstore_connections_status reads and clears both).
+ *  2 node Sim3 (:1062-1083): S_corr where the key-frame is in corr_kf, else (unit_quaternion(R), t, 1) from the pose column
+ *    (Eigen's four branches); quats / trans / scales hold it with the quaternion normalised, and it is these values every
+ *    later step reads.
+ *  3 family A (:1094-1125): keys ascending, each row ascending; k -> j is emitted when W[k][j] >= 100 (quirk Q-B5: the curr /
+ *    match exemption never acts) and both are nodes and j != k; the measurement is S[j] * S[k]^-1 on the node Sim3s; the pair
+ *    joins `inserted`.
+ *  4 per node key-frame k ascending, with Swi = (S_uncorr[k] if listed, else k's node Sim3)^-1 and the other end resolved
+ *    the same way, measurement S[other] * Swi (:1128-1236): B the parent, when k has one and it is a node; C k's loop edges l
+ *    ascending with l < curr (:1174) that are nodes; D the prefix of k's ordered list (section 4h) with weight >= 100
+ *    (getCovisiblesByWeight, keyframe.cpp:341-356) in list order, skipping an entry w that is the parent, a child of k (a
+ *    non-erased key-frame whose parent is k), a loop edge of k, bad(w), w >= k, or with (w, k) in `inserted`.
+ *  5 edge_i / edge_j are node indices in exactly this order (the solver's sums follow it): per-row and per-key-frame counts, a
+ *    scan, an emit at the offsets; no atomics decide an order.
+ * pose_graph_window_result: synchronises (one copy into the staging block); record [16] = n_nodes, n_edges, the counts of
+ * families A, B, C, D, status (VO_KFSTORE_BA_WINDOW_*), curr, match, fixed_node (match's node), and of the last apply
+ * n_points_moved and n_unanchored (feature rows, not distinct points); four zeros.  Arrays filled to the counts when the status
+ * is OK: node_kf, quats [n][4], trans [n][3], scales, edge_i, edge_j, q_meas [e][4], t_meas [e][3], s_meas (the caller sizes
+ * them by Nn and max_edges).  Any pointer may be NULL.
+ * pose_graph_apply(quats, trans): a solver's result for the LAST window, host arrays in node order; one copy, three launches,
+ * one synchronisation at the end.  VO_ERR_INVALID when there is no window, the last one is empty or overflowed, or the store
+ * has been changed since (the generation word of local_ba_apply; add_loop_edge advances it).  In the reference's order:
+ *  a every node, the fixed one included, gets Tiw = SE3(normalised uq, t / s) as Tcw12 in the pose column, and
+ *    Swr = Sim3(s, R(Tiw), t)^-1, with s the window's scale of the node.
+ *  b every feature with bit 0 set of every non-erased key-frame: idm = cp_ref where its id is in cp_id, else its ref_kf as
+ *    stored; its row becomes Swr[idm] * (Srw[idm] * p), Srw being the window's node Sim3 (step 2).  The row is the feature's own,
+ *    so the carriers of a point with equal rows and equal ref_kf end with equal rows.  idm == -1 or not a node: the row keeps
+ *    its bytes and counts in n_unanchored (the reference reads a default-constructed Sim3 there).
+ *  c every live point is refreshed as by vo_kfstore_refresh_points (updateNormalAndDepth, :1299).
+ *  d the observation index is marked stale and the generation word advances.
+ * pose_graph(curr, match, ..., max_iterations, summary): the window, ONE device-to-host copy into the staging block,
+ * vo_pose_graph_solve(n_nodes, ..., fixed_node, ..., fix_scale = 1, max_iterations, summary) on those bytes, the apply.
+ * Whatever the solver refuses is returned and NOTHING is written back (the rule of the C++ shim's solvePoseGraphLoop);
+ * VO_ERR_CAPACITY for an overflowed window, VO_ERR_INVALID for an empty one.  summary may be NULL.  Running the solver on the
+ * window's device arrays in place is not covered. */
+#define VO_KFSTORE_MAX_LOOP_EDGES 8
+#define VO_KFSTORE_POSE_GRAPH_CAPACITY 128
+int vo_kfstore_enable_pose_graph(vo_kfstore *s, int max_edges, int max_corrected, int max_corrected_points);
+int vo_kfstore_add_loop_edge(vo_kfstore *s, int a, int b);
+int vo_kfstore_get_loop_edges(vo_kfstore *s, int keyframe, int32_t *n, int32_t *edges /*[VO_KFSTORE_MAX_LOOP_EDGES]*/);
+int vo_kfstore_pose_graph_window(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
+                                 const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
+                                 const int32_t *cp_ref);
+int vo_kfstore_pose_graph_window_dev(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr,
+                                     const double *dev_S_uncorr, const int32_t *dev_lc_start, int n_lc, const int32_t *dev_lc_kf, int n_cp,
+                                     const int32_t *dev_cp_id, const int32_t *dev_cp_ref);
+int vo_kfstore_pose_graph_window_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *node_kf, double *quats, double *trans,
+                                        double *scales, int32_t *edge_i, int32_t *edge_j, double *q_meas, double *t_meas, double *s_meas);
+int vo_kfstore_pose_graph_apply(vo_kfstore *s, const double *quats, const double *trans);
+int vo_kfstore_pose_graph(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
+                          const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
+                          const int32_t *cp_ref, int max_iterations, vo_lm_summary *summary);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

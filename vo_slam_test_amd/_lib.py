@@ -71,6 +71,8 @@ SYMBOLS = [
     "vo_kfstore_fuse_result",
     "vo_kfstore_enable_loop", "vo_kfstore_compute_sim3", "vo_kfstore_compute_sim3_dev", "vo_kfstore_compute_sim3_continue",
     "vo_kfstore_loop_result", "vo_kfstore_loop_solver_inputs", "vo_kfstore_loop_ransac_max_iters",
+    "vo_kfstore_enable_pose_graph", "vo_kfstore_add_loop_edge", "vo_kfstore_get_loop_edges", "vo_kfstore_pose_graph_window",
+    "vo_kfstore_pose_graph_window_dev", "vo_kfstore_pose_graph_window_result", "vo_kfstore_pose_graph_apply", "vo_kfstore_pose_graph",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -2006,6 +2008,84 @@ class KeyFrameStore:
                                                   _p(idx)), "vo_kfstore_loop_solver_inputs")
         N = n.value
         return dict(pc1=pc1[:N], pc2=pc2[:N], px1=px1[:N], px2=px2[:N], me1=me1[:N], me2=me2[:N], index=idx[:N])
+
+    MAX_LOOP_EDGES = 8
+    CONNECTIONS_POSE_GRAPH_CAPACITY = 128
+    POSE_GRAPH_MAX_NODES = 683
+    PG_RECORD = ("n_nodes", "n_edges", "n_a", "n_b", "n_c", "n_d", "status", "curr", "match", "fixed_node", "n_points_moved", "n_unanchored")
+
+    def enable_pose_graph(self, max_edges, max_corrected, max_corrected_points):
+        """solvePoseGraphLoop's gather and write-back on the device from now on; valid on an empty store
+        after enable_local_ba only"""
+        check(lib().vo_kfstore_enable_pose_graph(self._h, int(max_edges), int(max_corrected), int(max_corrected_points)),
+              "vo_kfstore_enable_pose_graph")
+        self._pg_edges = int(max_edges)
+
+    def add_loop_edge(self, a, b):
+        """KeyFrame::addLoopEdge both ways, with both erase locks; enqueued only"""
+        check(lib().vo_kfstore_add_loop_edge(self._h, int(a), int(b)), "vo_kfstore_add_loop_edge")
+
+    def loop_edges(self, keyframe):
+        """-> the loop edges of a key-frame, ascending"""
+        n, e = C.c_int32(0), np.zeros(self.MAX_LOOP_EDGES, np.int32)
+        check(lib().vo_kfstore_get_loop_edges(self._h, int(keyframe), C.byref(n), _p(e)), "vo_kfstore_get_loop_edges")
+        return [int(x) for x in e[:n.value]]
+
+    @staticmethod
+    def _pg_inputs(inp, dev):
+        """inp: dict(corr_kf, S_corr, S_uncorr, lc_start, lc_kf, cp_id, cp_ref) -> the seven arrays as the entry points take them"""
+        if dev:
+            for k, dt in (("corr_kf", "int32"), ("S_corr", "float64"), ("S_uncorr", "float64"), ("lc_start", "int32"), ("lc_kf", "int32"),
+                          ("cp_id", "int32"), ("cp_ref", "int32")):
+                _need_tensor(inp[k], dt, None, "pose_graph_window")
+            return [inp[k] for k in ("corr_kf", "S_corr", "S_uncorr", "lc_start", "lc_kf", "cp_id", "cp_ref")]
+        i32, f64 = (lambda x: np.ascontiguousarray(x, np.int32).reshape(-1)), (lambda x: np.ascontiguousarray(x, np.float64).reshape(-1, 8))
+        return [i32(inp["corr_kf"]), f64(inp["S_corr"]), f64(inp["S_uncorr"]), i32(inp["lc_start"]), i32(inp["lc_kf"]), i32(inp["cp_id"]),
+                i32(inp["cp_ref"])]
+
+    def pose_graph_window(self, curr, match, inp):
+        """the pose graph of a loop closure curr - match from correctLoop's outputs (inp: see _pg_inputs).  numpy arrays / lists
+        are validated, copied once and the call synchronises once; device tensors (all seven) are enqueued only"""
+        dev = hasattr(inp["corr_kf"], "data_ptr")
+        ck, sc, su, ls, lk, ci, cr = self._pg_inputs(inp, dev)   # (named: the arrays must outlive the call)
+        if dev:
+            check(lib().vo_kfstore_pose_graph_window_dev(self._h, int(curr), int(match), int(ck.numel()), _p(ck), _p(sc), _p(su), _p(ls),
+                                                         int(lk.numel()), _p(lk), int(ci.numel()), _p(ci), _p(cr)),
+                  "vo_kfstore_pose_graph_window_dev")
+            return
+        if len(ls) != len(ck) + 1 or len(sc) != len(ck) or len(su) != len(ck) or len(cr) != len(ci) or len(lk) < (int(ls[-1]) if len(ls) else 0):
+            raise VoError("vo_kfstore_pose_graph_window failed with status -1: the arrays' lengths do not fit each other")
+        check(lib().vo_kfstore_pose_graph_window(self._h, int(curr), int(match), len(ck), _p(ck), _p(sc), _p(su), _p(ls), _p(lk), len(ci),
+                                                 _p(ci), _p(cr)), "vo_kfstore_pose_graph_window")
+
+    def pose_graph_window_result(self):
+        """the last window -> dict(record (dict over PG_RECORD), node_kf, quats, trans, scales, e_i, e_j, q_meas, t_meas, s_meas) cut
+        to the record's counts; with fixed = record['fixed_node'] it is a graph Optimizer.solvePoseGraphLoop takes"""
+        nn, ne = self.POSE_GRAPH_MAX_NODES, getattr(self, "_pg_edges", 1)
+        rec = np.zeros(16, np.int32)
+        a = dict(node_kf=np.zeros(nn, np.int32), quats=np.zeros((nn, 4)), trans=np.zeros((nn, 3)), scales=np.zeros(nn), e_i=np.zeros(ne, np.int32),
+                 e_j=np.zeros(ne, np.int32), q_meas=np.zeros((ne, 4)), t_meas=np.zeros((ne, 3)), s_meas=np.zeros(ne))
+        check(lib().vo_kfstore_pose_graph_window_result(self._h, _p(rec), *(_p(v) for v in a.values())), "vo_kfstore_pose_graph_window_result")
+        r = {k: int(rec[i]) for i, k in enumerate(self.PG_RECORD)}
+        ok = r["status"] == self.BA_WINDOW_OK
+        cut = dict(node_kf="n_nodes", quats="n_nodes", trans="n_nodes", scales="n_nodes")
+        return dict({k: v[:r[cut.get(k, "n_edges")] if ok else 0].copy() for k, v in a.items()}, record=r, fixed=r["fixed_node"])
+
+    def pose_graph_apply(self, quats, trans):
+        """a solver's result for the last window written back (host arrays in node order)"""
+        q, t = np.ascontiguousarray(quats, np.float64), np.ascontiguousarray(trans, np.float64)
+        check(lib().vo_kfstore_pose_graph_apply(self._h, _p(q), _p(t)), "vo_kfstore_pose_graph_apply")
+
+    def pose_graph(self, curr, match, inp, max_iterations=20):
+        """window, vo_pose_graph_solve with match's node fixed, write-back -> summary; a refusal of the solver raises and nothing
+        has been written back"""
+        ck, sc, su, ls, lk, ci, cr = self._pg_inputs(inp, False)   # (named: the arrays must outlive the call)
+        if len(ls) != len(ck) + 1 or len(sc) != len(ck) or len(su) != len(ck) or len(cr) != len(ci) or len(lk) < (int(ls[-1]) if len(ls) else 0):
+            raise VoError("vo_kfstore_pose_graph failed with status -1: the arrays' lengths do not fit each other")
+        s = LmSummary()
+        check(lib().vo_kfstore_pose_graph(self._h, int(curr), int(match), len(ck), _p(ck), _p(sc), _p(su), _p(ls), _p(lk), len(ci), _p(ci),
+                                          _p(cr), int(max_iterations), C.byref(s)), "vo_kfstore_pose_graph")
+        return s
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -126,6 +126,15 @@ struct vo_kfstore {
   vo::KfLoopView L{};
   bool loop = false, loop_called = false;
   int loop_fix_scale = 1;             // of the last compute_sim3: what compute_sim3_continue refines with
+  vo::OwnedDevBuf pg;                 // vo_kfstore_enable_pose_graph: the block of section 4o
+  vo::OwnedPinnedBuf pg_stage;        // a window's inputs or a solver's result going up, the window coming down: one copy each
+  vo::KfPgView P{};
+  bool pose_graph = false, pg_window = false, pg_rec_known = false;
+  unsigned long long pg_gen = 0;
+  int32_t pg_rec[vo::kPgRecInts] = {0};
+  int pg_counts[3] = {0, 0, 0};       // n_corr, n_lc, n_cp of the last window: where its inputs lie in P.in
+  std::vector<int32_t> pg_ledge;      // the loop edges as the host knows them: [max_kf][1 + VO_KFSTORE_MAX_LOOP_EDGES], count first
+  std::vector<double> pg_q, pg_t;     // the composed call's solver state (sized by the capacities: no allocation per call)
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
@@ -253,6 +262,12 @@ int need_fuse(const vo_kfstore *s, const char *call) {
 int need_loop(const vo_kfstore *s, const char *call) {
   if (s && s->loop) return VO_OK;
   if (s) vo::set_error("%s: vo_kfstore_enable_loop has not been called on this store", call);
+  return VO_ERR_INVALID;
+}
+
+int need_pose_graph(const vo_kfstore *s, const char *call) {
+  if (s && s->pose_graph) return VO_OK;
+  if (s) vo::set_error("%s: vo_kfstore_enable_pose_graph has not been called on this store", call);
   return VO_ERR_INVALID;
 }
 
@@ -1041,6 +1056,248 @@ int vo_kfstore_local_ba(vo_kfstore *s, vo_ba *ba, int current, const volatile un
   VO_CHECK(vo_ba_local_ba(ba, stop, s->ba_erase.data(), summaries));  // (VO_ERR_STOPPED: the return at :594, no write-back)
   VO_CHECK(vo_ba_get_state(ba, s->ba_poses.data(), s->ba_points.data()));
   return vo_kfstore_local_ba_apply(s, s->ba_poses.data(), s->ba_points.data(), s->ba_erase.data());
+}
+
+// ---- the loop pose graph from the store
+int vo_kfstore_enable_pose_graph(vo_kfstore *s, int max_edges, int max_corrected, int max_corrected_points) {
+  const char *W = "vo_kfstore_enable_pose_graph";
+  VO_CHECK(need_local_ba(s, W));
+  if (max_edges < 1 || max_corrected < 1 || max_corrected_points < 1) return VO_ERR_INVALID;
+  if (s->size != 0) {
+    vo::set_error("%s: the store holds %d key-frames, the call is valid on an empty store only", W, s->size);
+    return VO_ERR_INVALID;
+  }
+  if (s->pose_graph) return VO_OK;
+  VO_CHECK(s->pg.reserve(vo::pg_store_bytes(s->max_kf, s->NK, max_edges, max_corrected, max_corrected_points)));
+  s->P = vo::pg_store_layout(s->pg.p, s->max_kf, s->NK, max_edges, max_corrected, max_corrected_points);
+  VO_CHECK(s->pg_stage.reserve(std::max(s->P.win_bytes, std::max(s->P.in_bytes, s->P.sol_bytes))));
+  s->pg_ledge.assign((size_t)s->max_kf * (1 + VO_KFSTORE_MAX_LOOP_EDGES), 0);
+  s->pg_q.resize((size_t)s->P.max_nodes * 4), s->pg_t.resize((size_t)s->P.max_nodes * 3);
+  VO_CHECK(vo::pg_store_init(s->P, s->st));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  s->pose_graph = true;
+  return VO_OK;
+}
+
+int vo_kfstore_add_loop_edge(vo_kfstore *s, int a, int b) {
+  const char *W = "vo_kfstore_add_loop_edge";
+  VO_CHECK(need_pose_graph(s, W));
+  VO_CHECK(need_keyframe(s, W, a));
+  VO_CHECK(need_keyframe(s, W, b));
+  if (a == b) {
+    vo::set_error("%s: key-frame %d cannot be its own loop edge", W, a);
+    return VO_ERR_INVALID;
+  }
+  const int stride = 1 + VO_KFSTORE_MAX_LOOP_EDGES;
+  int32_t *ra = s->pg_ledge.data() + (size_t)a * stride, *rb = s->pg_ledge.data() + (size_t)b * stride;
+  const bool a_has = std::find(ra + 1, ra + 1 + ra[0], b) != ra + 1 + ra[0], b_has = std::find(rb + 1, rb + 1 + rb[0], a) != rb + 1 + rb[0];
+  if ((!a_has && ra[0] >= VO_KFSTORE_MAX_LOOP_EDGES) || (!b_has && rb[0] >= VO_KFSTORE_MAX_LOOP_EDGES)) {
+    vo::set_error("%s: key-frame %d or %d holds %d loop edges already", W, a, b, VO_KFSTORE_MAX_LOOP_EDGES);
+    return VO_ERR_CAPACITY;
+  }
+  if (!a_has) ra[1 + ra[0]++] = b;
+  if (!b_has) rb[1 + rb[0]++] = a;
+  s->gen++;
+  return vo::pg_add_loop_edge(s->P, s->X, a, b, s->st);  // (a repeat still sets both locks, as addLoopEdge does)
+}
+
+int vo_kfstore_get_loop_edges(vo_kfstore *s, int keyframe, int32_t *n, int32_t *edges) {
+  const char *W = "vo_kfstore_get_loop_edges";
+  VO_CHECK(need_pose_graph(s, W));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  int32_t h[1 + VO_KFSTORE_MAX_LOOP_EDGES];
+  VO_CHECK(vo::copy_d2h(h, s->P.n_ledge + keyframe, 4, s->st, W));
+  VO_CHECK(vo::copy_d2h(h + 1, s->P.ledge + (size_t)keyframe * VO_KFSTORE_MAX_LOOP_EDGES, VO_KFSTORE_MAX_LOOP_EDGES * 4, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  const int cnt = std::min(std::max(h[0], 0), VO_KFSTORE_MAX_LOOP_EDGES);
+  if (n) *n = cnt;
+  if (edges) memcpy(edges, h + 1, (size_t)cnt * 4);
+  return VO_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+int pg_check_counts(const vo_kfstore *s, const char *W, int curr, int match, int n_corr, int n_lc, int n_cp) {
+  VO_CHECK(need_keyframe(s, W, curr));
+  VO_CHECK(need_keyframe(s, W, match));
+  if (n_corr < 0 || n_lc < 0 || n_cp < 0) return VO_ERR_INVALID;
+  if (n_corr > s->P.max_corr || n_lc > s->P.max_edges || n_cp > s->P.max_cp) {
+    vo::set_error("%s: %d corrected key-frames, %d loop connections, %d corrected points; the store was enabled for %d, %d, %d", W, n_corr,
+                  n_lc, n_cp, s->P.max_corr, s->P.max_edges, s->P.max_cp);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+int pg_enqueue_window(vo_kfstore *s, int curr, int match, int n_corr, int n_lc, int n_cp) {
+  const vo::PgInputs I = vo::pg_inputs(s->P.in, n_corr, n_lc, n_cp);
+  VO_CHECK(vo::pg_window_enqueue(vo::kfstore_view(s), vo::connections_view(s->conn), s->X, s->M, s->P, I, curr, match, s->st));
+  s->pg_counts[0] = n_corr, s->pg_counts[1] = n_lc, s->pg_counts[2] = n_cp;
+  s->pg_window = true, s->pg_rec_known = false, s->pg_gen = s->gen;
+  return VO_OK;
+}
+
+// the window as one copy into the staging block; the record is then known on the host
+int pg_fetch_window(vo_kfstore *s, const char *W, bool record_only) {
+  VO_CHECK(vo::copy_d2h(s->pg_stage.data(), s->P.win, record_only ? sizeof(s->pg_rec) : s->P.win_bytes, s->st, W));
+  VO_CHECK(vo::stream_sync(s->st, W));
+  memcpy(s->pg_rec, s->pg_stage.data(), sizeof(s->pg_rec));
+  s->pg_rec_known = true;
+  return VO_OK;
+}
+
+template <class T>
+T *pg_staged(const vo_kfstore *s, const T *dev) {
+  return reinterpret_cast<T *>(s->pg_stage.data() + (reinterpret_cast<const uint8_t *>(dev) - s->P.win));
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_pose_graph_window(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
+                                 const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
+                                 const int32_t *cp_ref) {
+  const char *W = "vo_kfstore_pose_graph_window";
+  VO_CHECK(need_pose_graph(s, W));
+  if (n_corr < 0 || n_cp < 0 || !lc_start || (n_corr > 0 && (!corr_kf || !S_corr || !S_uncorr)) || (n_cp > 0 && (!cp_id || !cp_ref)))
+    return VO_ERR_INVALID;
+  if (lc_start[0] != 0 || lc_start[n_corr] < 0 || (lc_start[n_corr] > 0 && !lc_kf)) {
+    vo::set_error("%s: the loop connections do not start at 0, or end at %d without a list", W, lc_start[n_corr]);
+    return VO_ERR_INVALID;
+  }
+  const int n_lc = lc_start[n_corr];
+  VO_CHECK(pg_check_counts(s, W, curr, match, n_corr, n_lc, n_cp));
+  for (int r = 0; r < n_corr; r++) {
+    if (corr_kf[r] < 0 || corr_kf[r] >= s->size || (r > 0 && corr_kf[r - 1] >= corr_kf[r])) {
+      vo::set_error("%s: corrected key-frame %d (entry %d) outside [0, %d) or not in ascending order", W, corr_kf[r], r, s->size);
+      return VO_ERR_INVALID;
+    }
+    if (lc_start[r + 1] < lc_start[r] || lc_start[r + 1] > n_lc) {
+      vo::set_error("%s: the loop connections of entry %d run from %d to %d of %d", W, r, lc_start[r], lc_start[r + 1], n_lc);
+      return VO_ERR_INVALID;
+    }
+    for (int e = lc_start[r]; e < lc_start[r + 1]; e++)
+      if (lc_kf[e] < 0 || lc_kf[e] >= s->size || (e > lc_start[r] && lc_kf[e - 1] >= lc_kf[e])) {
+        vo::set_error("%s: loop connection %d of key-frame %d outside [0, %d) or not in ascending order", W, lc_kf[e], corr_kf[r], s->size);
+        return VO_ERR_INVALID;
+      }
+  }
+  for (int e = 0; e < n_cp; e++)
+    if (cp_id[e] < 0 || (e > 0 && cp_id[e - 1] >= cp_id[e]) || cp_ref[e] < 0 || cp_ref[e] >= s->size) {
+      vo::set_error("%s: corrected point %d (entry %d) negative or not in ascending order, or its reference %d outside [0, %d)", W, cp_id[e],
+                    e, cp_ref[e], s->size);
+      return VO_ERR_INVALID;
+    }
+  const vo::PgInputs H = vo::pg_inputs(s->pg_stage.data(), n_corr, n_lc, n_cp);
+  memcpy(H.S_corr, S_corr, (size_t)n_corr * 64), memcpy(H.S_unc, S_uncorr, (size_t)n_corr * 64);
+  memcpy(H.corr_kf, corr_kf, (size_t)n_corr * 4), memcpy(H.lc_start, lc_start, ((size_t)n_corr + 1) * 4);
+  memcpy(H.lc_kf, lc_kf, (size_t)n_lc * 4), memcpy(H.cp_id, cp_id, (size_t)n_cp * 4), memcpy(H.cp_ref, cp_ref, (size_t)n_cp * 4);
+  VO_CHECK(vo::copy_h2d(s->P.in, s->pg_stage.data(), H.bytes, s->st, W));  // the one copy
+  VO_CHECK(pg_enqueue_window(s, curr, match, n_corr, n_lc, n_cp));
+  return vo::stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_pose_graph_window_dev(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr,
+                                     const double *dev_S_uncorr, const int32_t *dev_lc_start, int n_lc, const int32_t *dev_lc_kf, int n_cp,
+                                     const int32_t *dev_cp_id, const int32_t *dev_cp_ref) {
+  const char *W = "vo_kfstore_pose_graph_window_dev";
+  VO_CHECK(need_pose_graph(s, W));
+  if (!dev_lc_start || (n_corr > 0 && (!dev_corr_kf || !dev_S_corr || !dev_S_uncorr)) || (n_lc > 0 && !dev_lc_kf) ||
+      (n_cp > 0 && (!dev_cp_id || !dev_cp_ref)))
+    return VO_ERR_INVALID;
+  VO_CHECK(pg_check_counts(s, W, curr, match, n_corr, n_lc, n_cp));
+  const vo::PgInputs I = vo::pg_inputs(s->P.in, n_corr, n_lc, n_cp);
+  auto d2d = [&](void *dst, const void *src, size_t bytes) {
+    return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->st) == hipSuccess;
+  };
+  if (!d2d(I.S_corr, dev_S_corr, (size_t)n_corr * 64) || !d2d(I.S_unc, dev_S_uncorr, (size_t)n_corr * 64) ||
+      !d2d(I.corr_kf, dev_corr_kf, (size_t)n_corr * 4) || !d2d(I.lc_start, dev_lc_start, ((size_t)n_corr + 1) * 4) ||
+      !d2d(I.lc_kf, dev_lc_kf, (size_t)n_lc * 4) || !d2d(I.cp_id, dev_cp_id, (size_t)n_cp * 4) || !d2d(I.cp_ref, dev_cp_ref, (size_t)n_cp * 4)) {
+    vo::set_error("%s: hipMemcpyAsync failed", W);
+    return VO_ERR_HIP;
+  }
+  return pg_enqueue_window(s, curr, match, n_corr, n_lc, n_cp);
+}
+
+int vo_kfstore_pose_graph_window_result(vo_kfstore *s, int32_t *record, int32_t *node_kf, double *quats, double *trans, double *scales,
+                                        int32_t *edge_i, int32_t *edge_j, double *q_meas, double *t_meas, double *s_meas) {
+  const char *W = "vo_kfstore_pose_graph_window_result";
+  VO_CHECK(need_pose_graph(s, W));
+  VO_CHECK(pg_fetch_window(s, W, false));
+  const int32_t *r = s->pg_rec;
+  if (record) memcpy(record, r, sizeof(s->pg_rec));
+  if (r[vo::kPgStatus] != VO_KFSTORE_BA_WINDOW_OK) return VO_OK;
+  const size_t nn = (size_t)r[vo::kPgNNodes], ne = (size_t)r[vo::kPgNEdges];
+  const vo::KfPgView &P = s->P;
+  if (node_kf) memcpy(node_kf, pg_staged(s, P.node_kf), nn * 4);
+  if (quats) memcpy(quats, pg_staged(s, P.quats), nn * 32);
+  if (trans) memcpy(trans, pg_staged(s, P.trans), nn * 24);
+  if (scales) memcpy(scales, pg_staged(s, P.scales), nn * 8);
+  if (edge_i) memcpy(edge_i, pg_staged(s, P.e_i), ne * 4);
+  if (edge_j) memcpy(edge_j, pg_staged(s, P.e_j), ne * 4);
+  if (q_meas) memcpy(q_meas, pg_staged(s, P.q_meas), ne * 32);
+  if (t_meas) memcpy(t_meas, pg_staged(s, P.t_meas), ne * 24);
+  if (s_meas) memcpy(s_meas, pg_staged(s, P.s_meas), ne * 8);
+  return VO_OK;
+}
+
+int vo_kfstore_pose_graph_apply(vo_kfstore *s, const double *quats, const double *trans) {
+  const char *W = "vo_kfstore_pose_graph_apply";
+  VO_CHECK(need_pose_graph(s, W));
+  if (!s->pg_window || s->pg_gen != s->gen) {
+    vo::set_error("%s: no window, or the store has been changed since the last one", W);
+    return VO_ERR_INVALID;
+  }
+  if (!s->pg_rec_known) VO_CHECK(pg_fetch_window(s, W, true));
+  const int32_t *r = s->pg_rec;
+  if (r[vo::kPgStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    vo::set_error("%s: the last window is %s", W, r[vo::kPgStatus] == VO_KFSTORE_BA_WINDOW_EMPTY ? "empty" : "overflowed");
+    return VO_ERR_INVALID;
+  }
+  if (!quats || !trans) return VO_ERR_INVALID;
+  const size_t nn = (size_t)r[vo::kPgNNodes];
+  uint8_t *h = s->pg_stage.data();
+  memcpy(h, quats, nn * 32), memcpy(h + nn * 32, trans, nn * 24);  // staged as k_pg_poses reads it: quats | trans
+  vo::KfObsView O;
+  VO_CHECK(vo::kfstore_obs_view(s, &O));  // (rebuilt when stale: the refresh list is read off it)
+  VO_CHECK(vo::copy_h2d(s->P.sol, h, nn * 56, s->st, W));
+  const vo::PgInputs I = vo::pg_inputs(s->P.in, s->pg_counts[0], s->pg_counts[1], s->pg_counts[2]);
+  const vo::KfStoreView V = vo::kfstore_view(s);
+  VO_CHECK(vo::pg_apply_enqueue(V, O, s->X, s->M, s->B, s->P, I, (int)nn, s->st));
+  VO_CHECK(vo::ba_refresh_list_enqueue(V, O, s->X, s->M, s->B, s->normals.as<double>(), vo::connections_view(s->conn).status,
+                                       s->size * s->NK, s->P.rl, s->st));  // updateNormalAndDepth of every live point (:1299)
+  s->obs_dirty = true, s->gen++, s->pg_rec_known = false;
+  return vo::stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_pose_graph(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr, const double *S_uncorr,
+                          const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id, const int32_t *cp_ref,
+                          int max_iterations, vo_lm_summary *summary) {
+  const char *W = "vo_kfstore_pose_graph";
+  VO_CHECK(need_pose_graph(s, W));
+  VO_CHECK(vo_kfstore_pose_graph_window(s, curr, match, n_corr, corr_kf, S_corr, S_uncorr, lc_start, lc_kf, n_cp, cp_id, cp_ref));
+  VO_CHECK(pg_fetch_window(s, W, false));  // the ONE device-to-host copy
+  const int32_t *r = s->pg_rec;
+  if (r[vo::kPgStatus] == VO_KFSTORE_BA_WINDOW_OVERFLOW) {
+    vo::set_error("%s: %d nodes, %d edges; the solver takes %d nodes and the store was enabled for %d edges", W, r[vo::kPgNNodes],
+                  r[vo::kPgNEdges], s->P.max_nodes, s->P.max_edges);
+    return VO_ERR_CAPACITY;
+  }
+  if (r[vo::kPgStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    vo::set_error("%s: the window is empty (curr or match erased, a key-frame without a pose, or lists only the device could refuse)", W);
+    return VO_ERR_INVALID;
+  }
+  const vo::KfPgView &P = s->P;
+  const size_t nn = (size_t)r[vo::kPgNNodes];
+  memcpy(s->pg_q.data(), pg_staged(s, P.quats), nn * 32), memcpy(s->pg_t.data(), pg_staged(s, P.trans), nn * 24);
+  // whatever the solver refuses is returned and nothing is written back (the shim's rule, optimizer_hip.inl:280-287)
+  VO_CHECK(vo_pose_graph_solve((int)nn, s->pg_q.data(), s->pg_t.data(), pg_staged(s, P.scales), r[vo::kPgFixed], r[vo::kPgNEdges],
+                               pg_staged(s, P.e_i), pg_staged(s, P.e_j), pg_staged(s, P.q_meas), pg_staged(s, P.t_meas),
+                               pg_staged(s, P.s_meas), 1, max_iterations, summary));
+  return vo_kfstore_pose_graph_apply(s, s->pg_q.data(), s->pg_t.data());
 }
 
 int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {

@@ -589,6 +589,52 @@ int sim3_solve_dev(int n_problems, int fix_scale, const int *off, const double *
                    const double *pxm, const double *ism, const double *cam4, double *poses, double *scales, uint8_t *outlier, int *n_inliers,
                    vo_lm_summary *sums, hipStream_t st);
 
+// The loop pose graph from the store (pose_graph_store.hip): the pose collection and the four edge
+// families of Optimizer::solvePoseGraphLoop (optimizer_ceres.cpp:1062-1236) gathered on the device, and its write-back
+// (:1264-1301).  What vo_kfstore_enable_pose_graph allocates, one block: ledge [max_kf][kPgMaxLoopEdges] ascending (-1 beyond
+// n_ledge [max_kf]); node_of [max_kf] (node index or -1); cnt [max_corr + max_kf + 1], the edges of every family-A row and
+// then of every key-frame, then their exclusive offsets; rl [max_kf][NK], the apply's refresh list (a point's id at its first
+// live key, -1 elsewhere); swr [max_nodes][8]; `in`, a window's inputs packed by their counts (PgInputs); the WINDOW,
+// contiguous so that one copy fetches it: rec, node_kf, quats, trans, scales, e_i, e_j, q_meas, t_meas, s_meas; and `sol`, a
+// solver's quats | trans as the apply's one copy brings them.
+constexpr int kPgRecInts = 16, kPgMaxLoopEdges = VO_KFSTORE_MAX_LOOP_EDGES, kPgMaxNodes = 4096 / 6 + 1, kPgMinWeight = 100;
+enum { kPgNNodes = 0, kPgNEdges, kPgNA, kPgNB, kPgNC, kPgND, kPgStatus, kPgCurr, kPgMatch, kPgFixed, kPgNMoved, kPgNUnanchored };
+struct KfPgView {
+  int max_kf, NK, max_nodes, max_edges, max_corr, max_cp;
+  int *ledge, *n_ledge, *node_of, *cnt, *rl;
+  double *swr;
+  uint8_t *in;
+  size_t in_bytes;
+  uint8_t *win;
+  size_t win_bytes;
+  int *rec, *node_kf;
+  double *quats, *trans, *scales;
+  int *e_i, *e_j;
+  double *q_meas, *t_meas, *s_meas;
+  uint8_t *sol;
+  size_t sol_bytes;
+};
+// a window's inputs inside `in` (or a staging block laid out like it): S_corr | S_uncorr [n_corr][8], corr_kf [n_corr],
+// lc_start [n_corr + 1], lc_kf [n_lc], cp_id | cp_ref [n_cp], every array rounded up to 16 bytes
+struct PgInputs {
+  int n_corr, n_lc, n_cp;
+  double *S_corr, *S_unc;
+  int *corr_kf, *lc_start, *lc_kf, *cp_id, *cp_ref;
+  size_t bytes;
+};
+PgInputs pg_inputs(void *block, int n_corr, int n_lc, int n_cp);
+size_t pg_store_bytes(int max_kf, int NK, int max_edges, int max_corr, int max_cp);
+KfPgView pg_store_layout(void *block, int max_kf, int NK, int max_edges, int max_corr, int max_cp);
+int pg_store_init(const KfPgView &P, hipStream_t st);
+// addLoopEdge both ways and both erase locks; one launch
+int pg_add_loop_edge(const KfPgView &P, const KfCullView &X, int a, int b, hipStream_t st);
+// four launches: nodes (with the inputs' checks and the node Sim3s), counts, layout, emit
+int pg_window_enqueue(const KfStoreView &S, const KfConnView &C, const KfCullView &X, const KfMapView &M, const KfPgView &P,
+                      const PgInputs &I, int curr, int match, hipStream_t st);
+// two launches on the solver's result in P.sol: poses and S_wr, then the re-anchoring with the refresh list
+int pg_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
+                     const KfPgView &P, const PgInputs &I, int n_nodes, hipStream_t st);
+
 // vo_kfdb_query_reloc_dev on a stream of the caller's (kfdb.hip): the database's own stream and `st` are ordered around the
 // query by events.  Nothing is validated beyond what vo_kfdb_query_reloc_dev checks.
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
