@@ -11,7 +11,7 @@
 //                 its children from the parent column, its graph row for k_lm_keyframes.
 // As in local_map.hip nothing depends on which thread runs when: the counts are integer sums, a step of the sequence
 // writes every word from one thread, and the order comes from a fixed sorting network over distinct keys.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "block_sort.h"
 #include "obs_walk.h"
@@ -238,7 +238,7 @@ __global__ void k_conn_init(int max_kf, int *n_ordered, int *mode, int *first, i
 
 }  // namespace
 
-namespace vo {
+namespace {
 
 size_t connections_bytes(int max_kf) { return ((size_t)2 * max_kf * max_kf + (size_t)5 * max_kf + 4) * 4; }
 
@@ -272,6 +272,10 @@ int connections_create(KfConnections **out, int max_kf, int *graph, hipStream_t 
   *out = c;
   return VO_OK;
 }
+
+}  // namespace
+
+namespace vo {
 
 void connections_destroy(KfConnections *c) { delete c; }
 
@@ -310,6 +314,10 @@ KfConnView connections_view(const KfConnections *c) {
 
 void connections_set_erased(KfConnections *c, const int *erased) { c->erased = erased; }
 
+}  // namespace vo
+
+namespace {
+
 int connections_status(KfConnections *c, hipStream_t st, int *word) {
   const char *W = "vo_kfstore_connections_status";
   int w = 0;
@@ -347,4 +355,60 @@ int connections_get(KfConnections *c, int size, int k, hipStream_t st, int32_t *
   return VO_OK;
 }
 
-}  // namespace vo
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_connections(vo_kfstore *s) {
+  if (const int rc = enable_begin(s, "vo_kfstore_enable_connections", 0, kLayerConnections)) return rc < 0 ? rc : VO_OK;
+  VO_CHECK(connections_create(&s->conn, s->max_kf, s->graph.as<int>(), s->st));
+  s->layers |= kLayerConnections;
+  return VO_OK;
+}
+
+int vo_kfstore_update_connections_dev(vo_kfstore *s, int n, const int32_t *dev_keyframes) {
+  VO_CHECK(need(s, "vo_kfstore_update_connections_dev", kLayerConnections));
+  if (n < 0 || (n > 0 && !dev_keyframes)) return VO_ERR_INVALID;
+  if (n == 0 || s->size == 0) return VO_OK;
+  VO_CHECK(connections_reserve(s->conn, n, nullptr));  // (before the index: nothing is enqueued when it fails)
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  s->gen++;  // (the ordered lists are what a window starts from)
+  return connections_update(s->conn, kfstore_view(s), O, n, dev_keyframes, s->st);
+}
+
+int vo_kfstore_update_connections(vo_kfstore *s, int n, const int32_t *keyframes) {
+  const char *W = "vo_kfstore_update_connections";
+  VO_CHECK(need(s, W, kLayerConnections));
+  if (n < 0 || (n > 0 && !keyframes)) return VO_ERR_INVALID;
+  for (int i = 0; i < n; i++)
+    if (keyframes[i] < 0 || keyframes[i] >= s->size) {
+      set_error("%s: entry %d: key-frame %d outside [0, %d)", W, i, keyframes[i], s->size);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  int *dev_list = nullptr;
+  VO_CHECK(connections_reserve(s->conn, n, &dev_list));
+  VO_CHECK(copy_h2d(dev_list, keyframes, (size_t)n * 4, s->st, W));
+  VO_CHECK(vo_kfstore_update_connections_dev(s, n, dev_list));
+  return stream_sync(s->st, W);  // (the caller's list is free on return)
+}
+
+int vo_kfstore_connections_status(vo_kfstore *s, int32_t *word) {
+  VO_CHECK(need(s, "vo_kfstore_connections_status", kLayerConnections));
+  if (!word) return VO_ERR_INVALID;
+  int w = 0;
+  VO_CHECK(connections_status(s->conn, s->st, &w));
+  *word = w;
+  return VO_OK;
+}
+
+int vo_kfstore_get_connections(vo_kfstore *s, int keyframe, int32_t *n_connected, int32_t *weights, int32_t *n_ordered,
+                               int32_t *ordered, int32_t *ordered_weights, int32_t *parent, int32_t *n_children, int32_t *children) {
+  VO_CHECK(need(s, "vo_kfstore_get_connections", kLayerConnections));
+  if (keyframe < 0 || keyframe >= s->size) return VO_ERR_INVALID;
+  return connections_get(s->conn, s->size, keyframe, s->st, n_connected, weights, n_ordered, ordered, ordered_weights, parent,
+                         n_children, children);
+}
+
+}  // extern "C"

@@ -11,9 +11,11 @@
 //   (the caller follows with connections.hip's ordering pass over the touched key-frames)
 // As in connections.hip nothing depends on which thread runs when: the counts are integer sums, a step of the sequence
 // writes every word or byte from one thread, and the re-parenting choice is the maximum of distinct keys.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "obs_walk.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -308,8 +310,10 @@ __global__ void k_cull_lock(KfCullView X, int k, int on) {
 
 }  // namespace
 
-namespace vo {
+namespace {
 
+// cull_bytes is what cull_layout hands out of one block; cull_init writes the defaults; cull_enqueue is k_cull_count +
+// k_cull_apply, erase_enqueue the erase alone, both without the ordering pass.  Launches only.
 size_t cull_bytes(int max_kf, int NK) { return ((size_t)3 * max_kf * NK + (size_t)7 * max_kf + 4) * 4; }
 
 KfCullView cull_layout(void *block, int max_kf, int NK) {
@@ -352,4 +356,118 @@ int erase_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C,
   return VO_OK;
 }
 
-}  // namespace vo
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_culling(vo_kfstore *s) {
+  const char *W = "vo_kfstore_enable_culling";
+  if (const int rc = enable_begin(s, W, kLayerConnections, kLayerCulling)) return rc < 0 ? rc : VO_OK;
+  VO_CHECK(s->cull.reserve(cull_bytes(s->max_kf, s->NK)));
+  s->X = cull_layout(s->cull.p, s->max_kf, s->NK);
+  VO_CHECK(cull_init(s->X, s->max_kf, s->st));
+  VO_CHECK(stream_sync(s->st, W));
+  connections_set_erased(s->conn, s->X.erased);
+  s->layers |= kLayerCulling;
+  return VO_OK;
+}
+
+int vo_kfstore_set_keypoints(vo_kfstore *s, int keyframe, const int32_t *octave, const float *depth, const float *u_right) {
+  const char *W = "vo_kfstore_set_keypoints";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
+  if (n == 0) return VO_OK;
+  if (!octave || !depth || !u_right) return VO_ERR_INVALID;
+  s->gen++;
+  // the three columns of a key-frame lie side by side: staged whole (the defaults beyond n), one copy
+  uint8_t *h = s->stage.data();  // (a record is longer than 12 bytes a feature)
+  int32_t *ho = reinterpret_cast<int32_t *>(h);
+  float *hd = reinterpret_cast<float *>(h) + NK, *hu = hd + NK;
+  for (size_t i = 0; i < NK; i++) ho[i] = i < n ? octave[i] : 0, hd[i] = i < n ? depth[i] : -1.f, hu[i] = i < n ? u_right[i] : -1.f;
+  VO_CHECK(copy_h2d(cull_octave(s->X, keyframe), h, NK * 12, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_keypoints_dev(vo_kfstore *s, int keyframe, const int32_t *dev_octave, const float *dev_depth, const float *dev_u_right) {
+  const char *W = "vo_kfstore_set_keypoints_dev";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_octave || !dev_depth || !dev_u_right) return VO_ERR_INVALID;
+  s->gen++;
+  VO_HIP_CHECK(hipMemcpyAsync(cull_octave(s->X, keyframe), dev_octave, n * 4, hipMemcpyDeviceToDevice, s->st));
+  VO_HIP_CHECK(hipMemcpyAsync(cull_depth(s->X, keyframe), dev_depth, n * 4, hipMemcpyDeviceToDevice, s->st));
+  VO_HIP_CHECK(hipMemcpyAsync(cull_uright(s->X, keyframe), dev_u_right, n * 4, hipMemcpyDeviceToDevice, s->st));
+  return VO_OK;
+}
+
+int vo_kfstore_set_erase_lock(vo_kfstore *s, int keyframe, int on) {
+  const char *W = "vo_kfstore_set_erase_lock";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  s->gen++;
+  return cull_set_lock(s->X, keyframe, on, s->st);
+}
+
+int vo_kfstore_cull_keyframes(vo_kfstore *s, int current, float th_depth) {
+  const char *W = "vo_kfstore_cull_keyframes";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has not been erased only the device knows: the kernels then walk no candidate and raise the sticky
+  //  VO_KFSTORE_CONNECTIONS_INVALID)
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(cull_enqueue(kfstore_view(s), O, connections_view(s->conn), s->X, current, th_depth, s->st));
+  s->obs_dirty = true, s->gen++;  // (whether anything was erased only the device knows)
+  return connections_order(s->conn, s->size, s->st);
+}
+
+int vo_kfstore_erase_keyframe(vo_kfstore *s, int keyframe) {
+  const char *W = "vo_kfstore_erase_keyframe";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(erase_enqueue(kfstore_view(s), O, connections_view(s->conn), s->X, keyframe, s->st));
+  s->obs_dirty = true, s->gen++;
+  return connections_order(s->conn, s->size, s->st);
+}
+
+int vo_kfstore_cull_result(vo_kfstore *s, int32_t *n_candidates, int32_t *keyframes, int32_t *mp_cnt, int32_t *re_obs, int32_t *decision) {
+  const char *W = "vo_kfstore_cull_result";
+  VO_CHECK(need(s, W, kLayerCulling));
+  if (!n_candidates) return VO_ERR_INVALID;
+  std::vector<int32_t> rec((size_t)s->size * 4 + 4);
+  int32_t n = 0;
+  VO_CHECK(copy_d2h(&n, s->X.n_rec, 4, s->st, W));
+  if (s->size > 0) VO_CHECK(copy_d2h(rec.data(), s->X.rec, (size_t)s->size * 16, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  n = std::min(std::max(n, 0), s->size);
+  *n_candidates = n;
+  for (int t = 0; t < n; t++) {
+    if (keyframes) keyframes[t] = rec[(size_t)t * 4];
+    if (mp_cnt) mp_cnt[t] = rec[(size_t)t * 4 + 1];
+    if (re_obs) re_obs[t] = rec[(size_t)t * 4 + 2];
+    if (decision) decision[t] = rec[(size_t)t * 4 + 3];
+  }
+  return VO_OK;
+}
+
+int vo_kfstore_cull_state(vo_kfstore *s, int keyframe, int32_t *erased, int32_t *locked, int32_t *pending) {
+  const char *W = "vo_kfstore_cull_state";
+  VO_CHECK(need(s, W, kLayerCulling));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  int32_t w[3] = {0, 0, 0};
+  VO_CHECK(copy_d2h(w, s->X.erased + keyframe, 4, s->st, W));
+  VO_CHECK(copy_d2h(w + 1, s->X.locked + keyframe, 4, s->st, W));
+  VO_CHECK(copy_d2h(w + 2, s->X.pending + keyframe, 4, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  if (erased) *erased = w[0];
+  if (locked) *locked = w[1];
+  if (pending) *pending = w[2];
+  return VO_OK;
+}
+
+}  // extern "C"

@@ -1,7 +1,7 @@
 // fuse.hip -- map-point fusion on the device: LocalMapping::searchInNeighbors
 // (localMapping.cpp:363-432), Matcher::fuseMapPoints (matcher.cpp:1012-1133) and MapPoint::replaceMapPoint
 // (mappoint.cpp:214-253) over the key-frame store's observation index AS IT STOOD AT THE START OF THE CALL plus an overlay
-// (vo_common.h: KfOverlay; obs_walk.h: obs_overlay_wave), so that a call of up to 61 fuse steps never rebuilds the index.
+// (kfstore.h: KfOverlay; obs_walk.h: obs_overlay_wave), so that a call of up to 61 fuse steps never rebuilds the index.
 //   k_fuse_begin    the target list from section 4h's ordered lists (one thread) and `current`'s ids (a thread per feature)
 //   k_fuse_mark     a thread per list entry: the id's slot (the start of its run), an atomic maximum there decides the first
 //                   occurrence of the id in the list without a sort
@@ -16,7 +16,7 @@
 //   k_fuse_live     `current`'s live ids, each once, for the closing descriptors and refresh
 // No kernel waits on another workgroup; every loop is bounded by a count read once or by an array's size; chains read and
 // write disjoint ids and disjoint features, so every byte has one writer per launch.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "kf_area.h"
 #include "new_points_geom.h"
@@ -556,8 +556,6 @@ __global__ __launch_bounds__(256) void k_fuse_live(FuseArgs A, int current) {
   A.F.snap[i] = id;
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct Layout {
   uint8_t *block;
   size_t at = 0;
@@ -593,10 +591,6 @@ int step_enqueue(const FuseArgs &A, int step, const int *list, int n_max, const 
   return VO_OK;
 }
 
-}  // namespace
-
-namespace vo {
-
 size_t fuse_bytes(int NK, int max_matches, int n_slots) {
   Layout L{nullptr};
   KfFuseView F{};
@@ -613,12 +607,14 @@ KfFuseView fuse_layout(void *block, int NK, int max_matches, int n_slots, const 
   return F;
 }
 
+// one fuse call on its own: reset, then mark / search / mutate for step 0 over the n ids of a device list
 int fuse_single_enqueue(const FuseArgs &A, int target, int n, const int *dev_ids, float threshold, hipStream_t st) {
   VO_HIP_CHECK(hipMemsetAsync(A.F.head, 0, A.F.reset_bytes, st));
   hipLaunchKernelGGL(k_fuse_begin_single, dim3(1), dim3(64), 0, st, A.F, target);
   return step_enqueue(A, 0, dev_ids, n, nullptr, threshold, st);
 }
 
+// the composed call up to the closing rebuild: reset, target list and snapshot, 60 target steps, the gather, the closing step
 int fuse_neighbors_enqueue(const FuseArgs &A, int current, hipStream_t st) {
   const int NK = A.S.NK;
   VO_HIP_CHECK(hipMemsetAsync(A.F.head, 0, A.F.reset_bytes, st));
@@ -628,10 +624,113 @@ int fuse_neighbors_enqueue(const FuseArgs &A, int current, hipStream_t st) {
   return step_enqueue(A, kFuseFinal, A.F.list, kFuseFinal * NK, A.F.head + 3, 3.0f, st);  // (:418)
 }
 
+// current's live ids, each once, into F.snap (behind the rebuild: the list of the closing descriptors and refresh)
 int fuse_live_list_enqueue(const FuseArgs &A, int current, hipStream_t st) {
   hipLaunchKernelGGL(k_fuse_live, dim3((unsigned)((A.S.NK + 255) / 256)), dim3(256), 0, st, A, current);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
 
-}  // namespace vo
+FuseArgs fuse_args(vo_kfstore *s, const KfObsView &O) {
+  const KfConnView C = connections_view(s->conn);
+  return FuseArgs{kfstore_view(s), O, C, s->X, s->M, s->B, s->U, s->F, s->normals.as<double>(), C.status};
+}
+
+// a fuse call's head: the layer, the target, the list (at most F.list_cap ids) and the threshold
+int fuse_check(const vo_kfstore *s, const char *W, int target, int n, const int32_t *ids, float threshold) {
+  VO_CHECK(need(s, W, kLayerFuse));
+  VO_CHECK(need_keyframe(s, W, target));
+  if (n < 0 || (n > 0 && !ids) || !(threshold > 0.f)) return VO_ERR_INVALID;
+  if (n > s->F.list_cap) {
+    set_error("%s: %d ids, the store takes %d (60 * max_features)", W, n, s->F.list_cap);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_fuse(vo_kfstore *s, const float bounds[4], int max_candidates) {
+  const char *W = "vo_kfstore_enable_fuse";
+  const bool args_ok = bounds && max_candidates >= 1 && bounds[1] > bounds[0] && bounds[3] > bounds[2];
+  if (const int rc = enable_begin(s, W, kLayerUpkeep, kLayerFuse, args_ok)) return rc < 0 ? rc : VO_OK;
+  if (s->NK > 4096) {
+    set_error("%s: %d features per key-frame, the search stages at most 4096", W, s->NK);
+    return VO_ERR_CAPACITY;
+  }
+  const size_t bytes = fuse_bytes(s->NK, max_candidates, s->okeys_cap);
+  VO_CHECK(s->fu.reserve(bytes));
+  s->F = fuse_layout(s->fu.p, s->NK, max_candidates, s->okeys_cap, bounds);
+  VO_CHECK(s->up_stage.reserve((size_t)s->F.list_cap * 4));
+  VO_HIP_CHECK(hipMemsetAsync(s->fu.p, 0, bytes, s->st));
+  VO_HIP_CHECK(hipMemsetAsync(s->F.targets, 0xff, 64 * 4, s->st));  // (no call yet: no step)
+  VO_CHECK(stream_sync(s->st, W));
+  s->layers |= kLayerFuse;
+  return VO_OK;
+}
+
+int vo_kfstore_fuse_map_points_dev(vo_kfstore *s, int target, int n, const int32_t *dev_ids, float threshold) {
+  const char *W = "vo_kfstore_fuse_map_points_dev";
+  VO_CHECK(fuse_check(s, W, target, n, dev_ids, threshold));
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(fuse_single_enqueue(fuse_args(s, O), target, n, dev_ids, threshold, s->st));
+  s->obs_dirty = true, s->gen++;  // (whether anything matched only the device knows)
+  return VO_OK;
+}
+
+int vo_kfstore_fuse_map_points(vo_kfstore *s, int target, int n, const int32_t *ids, float threshold) {
+  const char *W = "vo_kfstore_fuse_map_points";
+  VO_CHECK(fuse_check(s, W, target, n, ids, threshold));
+  if (n > 0) {
+    memcpy(s->up_stage.data(), ids, (size_t)n * 4);
+    VO_CHECK(copy_h2d(s->F.list, s->up_stage.data(), (size_t)n * 4, s->st, W));
+  }
+  VO_CHECK(vo_kfstore_fuse_map_points_dev(s, target, n, s->F.list, threshold));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_search_in_neighbors(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_search_in_neighbors";
+  VO_CHECK(need(s, W, kLayerFuse));
+  VO_CHECK(need_keyframe(s, W, current));
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));  // the index the overlay stands on
+  VO_CHECK(fuse_neighbors_enqueue(fuse_args(s, O), current, s->st));
+  s->obs_dirty = true, s->gen++;
+  VO_CHECK(kfstore_obs_view(s, &O));  // the one rebuild behind the fuses, whatever their number
+  const FuseArgs A = fuse_args(s, O);
+  VO_CHECK(fuse_live_list_enqueue(A, current, s->st));
+  VO_CHECK(upkeep_descriptors_enqueue(A.S, O, s->U, A.status, s->NK, s->F.snap, s->st));             // computeDescriptor (:426)
+  VO_CHECK(ba_refresh_list_enqueue(A.S, O, s->X, s->M, s->B, A.normals, A.status, s->NK, s->F.snap, s->st));  // (:427)
+  return connections_update(s->conn, A.S, O, 1, s->F.head + 2, s->st);  // keyframe_curr_->updateConnections() (:431)
+}
+
+int vo_kfstore_fuse_result(vo_kfstore *s, int32_t *record, int32_t *targets, int32_t *per_target) {
+  const char *W = "vo_kfstore_fuse_result";
+  VO_CHECK(need(s, W, kLayerFuse));
+  int32_t head[4], tg[64], rec[64 * kFuseRecInts];
+  VO_CHECK(copy_d2h(head, s->F.head, sizeof(head), s->st, W));
+  VO_CHECK(copy_d2h(tg, s->F.targets, sizeof(tg), s->st, W));
+  VO_CHECK(copy_d2h(rec, s->F.rec, sizeof(rec), s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  int32_t out_rec[8] = {0}, out_t[VO_KFSTORE_FUSE_MAX_STEPS], out_p[VO_KFSTORE_FUSE_MAX_STEPS * 6];
+  memset(out_t, 0xff, sizeof(out_t)), memset(out_p, 0, sizeof(out_p));
+  const int n_t = std::min(std::max(head[0], 0), kFuseFinal);
+  int n = 0;
+  for (int step = 0; step <= kFuseFinal; step++) {
+    if (step < kFuseFinal ? step >= n_t : tg[step] < 0) continue;
+    out_t[n] = tg[step];
+    for (int c = 0; c < 6; c++) out_p[n * 6 + c] = rec[step * kFuseRecInts + 1 + c], out_rec[1 + c] += out_p[n * 6 + c];
+    n++;
+  }
+  out_rec[0] = n;
+  if (record) memcpy(record, out_rec, sizeof(out_rec));
+  if (targets) memcpy(targets, out_t, sizeof(out_t));
+  if (per_target) memcpy(per_target, out_p, sizeof(out_p));
+  return VO_OK;
+}
+
+}  // extern "C"

@@ -16,19 +16,19 @@
 // Nothing depends on which thread runs when: positions come from counts and scans, the atomics are integer sums, and every
 // byte and word of the store has one writer per launch (an entry of the index carries one id, a point has one lane).
 // Compiled with -ffp-contract=off: the refresh rounds every double operation on its own, in the order section 4k writes down.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "ba_math.h"
 #include "new_points_geom.h"
 #include "obs_walk.h"
+
+#include <algorithm>
 
 namespace {
 
 using namespace vo;
 
 enum { kOk = VO_KFSTORE_BA_WINDOW_OK, kEmpty = VO_KFSTORE_BA_WINDOW_EMPTY, kOverflow = VO_KFSTORE_BA_WINDOW_OVERFLOW };
-
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 struct BaLayout {
   uint8_t *block;
@@ -426,7 +426,7 @@ __global__ void k_ba_init(KfBaView B) {
 
 }  // namespace
 
-namespace vo {
+namespace {
 
 size_t ba_store_bytes(int max_kf, int NK, int max_cams, int max_points, int max_edges) {
   BaLayout L{nullptr};
@@ -450,6 +450,8 @@ int ba_store_init(const KfBaView &B, int max_kf, hipStream_t st) {
   return VO_OK;
 }
 
+// five launches: local cameras, first-occurrence counts, points (with their edge counts and the fixed marks), layout (fixed
+// cameras, capacities, poses, edge offsets), edges
 int ba_window_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView &C, const KfCullView &X, const KfMapView &M,
                       const KfBaView &B, int current, hipStream_t st) {
   WinArgs A{S, O, C, X, M, B, current};
@@ -463,6 +465,7 @@ int ba_window_enqueue(const KfStoreView &S, const KfObsView &O, const KfConnView
   return VO_OK;
 }
 
+// two launches on the inputs in B.in: erase + death (and the poses), then write + refresh
 int ba_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                      double *normals, int *status, int n_cams, int n_points, int n_edges, hipStream_t st) {
   ApplyArgs A{S, O, X, M, B, normals, status, n_cams, n_points, n_edges};
@@ -475,6 +478,7 @@ int ba_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView 
   return VO_OK;
 }
 
+// the refresh alone for the n ids in B.ids_in
 int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                        double *normals, int *status, int n, hipStream_t st) {
   if (n <= 0) return VO_OK;
@@ -484,6 +488,10 @@ int ba_refresh_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullVie
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
+
+}  // namespace
+
+namespace vo {
 
 int ba_refresh_list_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                             double *normals, int *status, int n, const int *dev_ids, hipStream_t st) {
@@ -496,3 +504,170 @@ int ba_refresh_list_enqueue(const KfStoreView &S, const KfObsView &O, const KfCu
 }
 
 }  // namespace vo
+
+extern "C" {
+
+int vo_kfstore_enable_local_ba(vo_kfstore *s, int max_cams, int max_points, int max_edges) {
+  const char *W = "vo_kfstore_enable_local_ba";
+  const bool args_ok = max_cams >= 1 && max_points >= 1 && max_edges >= 1;
+  if (const int rc = enable_begin(s, W, kLayerMapping, kLayerLocalBa, args_ok)) return rc < 0 ? rc : VO_OK;
+  VO_CHECK(s->ba.reserve(ba_store_bytes(s->max_kf, s->NK, max_cams, max_points, max_edges)));
+  s->B = ba_store_layout(s->ba.p, s->max_kf, s->NK, max_cams, max_points, max_edges);
+  VO_CHECK(s->ba_win.stage.reserve(std::max(s->B.win_bytes, s->B.in_bytes)));
+  s->ba_poses.resize((size_t)max_cams * 6), s->ba_points.resize((size_t)max_points * 3), s->ba_erase.resize((size_t)max_edges + 1);
+  VO_CHECK(ba_store_init(s->B, s->max_kf, s->st));
+  VO_CHECK(stream_sync(s->st, W));
+  s->layers |= kLayerLocalBa;
+  return VO_OK;
+}
+
+int vo_kfstore_set_point_refs(vo_kfstore *s, int keyframe, const int32_t *ref_kf) {
+  const char *W = "vo_kfstore_set_point_refs";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!ref_kf) return VO_ERR_INVALID;
+  for (size_t i = 0; i < n; i++)
+    if (ref_kf[i] < -1 || ref_kf[i] >= s->size) {
+      set_error("%s: feature %zu: reference key-frame %d outside [-1, %d)", W, i, ref_kf[i], s->size);
+      return VO_ERR_INVALID;
+    }
+  s->gen++;
+  VO_CHECK(copy_h2d(s->B.ref_kf + (size_t)keyframe * s->NK, ref_kf, n * 4, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_point_refs_dev(vo_kfstore *s, int keyframe, const int32_t *dev_ref_kf) {
+  const char *W = "vo_kfstore_set_point_refs_dev";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_ref_kf) return VO_ERR_INVALID;
+  s->gen++;
+  VO_HIP_CHECK(hipMemcpyAsync(s->B.ref_kf + (size_t)keyframe * s->NK, dev_ref_kf, n * 4, hipMemcpyDeviceToDevice, s->st));
+  return VO_OK;
+}
+
+int vo_kfstore_get_point_refs(vo_kfstore *s, int keyframe, int32_t *ref_kf) {
+  const char *W = "vo_kfstore_get_point_refs";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!ref_kf) return VO_ERR_INVALID;
+  VO_CHECK(copy_d2h(ref_kf, s->B.ref_kf + (size_t)keyframe * s->NK, n * 4, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_local_ba_window(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_local_ba_window";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has been erased, or that a camera has no pose, only the device knows: the window is then empty)
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(ba_window_enqueue(kfstore_view(s), O, connections_view(s->conn), s->X, s->M, s->B, current, s->st));
+  s->ba_win.begin(s->gen);
+  return VO_OK;
+}
+
+int vo_kfstore_local_ba_window_result(vo_kfstore *s, int32_t *record, int32_t *cam_keyframe, uint8_t *cam_fixed, double *poses6,
+                                      int32_t *point_id, double *points, int32_t *edge_cam, int32_t *edge_point,
+                                      int32_t *edge_feature, double *edge_obs, double *edge_inv_sigma) {
+  const char *W = "vo_kfstore_local_ba_window_result";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  const KfBaView &B = s->B;
+  const KfWindow &win = s->ba_win;
+  VO_CHECK(s->ba_win.fetch(B.win, B.win_bytes, false, s->st, W));
+  const int32_t *r = win.rec;
+  if (record) memcpy(record, r, sizeof(win.rec));
+  if (r[kBaStatus] != VO_KFSTORE_BA_WINDOW_OK) return VO_OK;
+  const size_t nc = (size_t)r[kBaNCams], np = (size_t)r[kBaNPoints], ne = (size_t)r[kBaNEdges];
+  if (cam_keyframe) memcpy(cam_keyframe, win.staged(B.cam_kf, B.win), nc * 4);
+  if (cam_fixed) memcpy(cam_fixed, win.staged(B.cam_fixed, B.win), nc);
+  if (poses6) memcpy(poses6, win.staged(B.poses6, B.win), nc * 48);
+  if (point_id) memcpy(point_id, win.staged(B.pt_id, B.win), np * 4);
+  if (points) memcpy(points, win.staged(B.points, B.win), np * 24);
+  if (edge_cam) memcpy(edge_cam, win.staged(B.e_cam, B.win), ne * 4);
+  if (edge_point) memcpy(edge_point, win.staged(B.e_pt, B.win), ne * 4);
+  if (edge_feature) memcpy(edge_feature, win.staged(B.e_feat, B.win), ne * 4);
+  if (edge_obs) memcpy(edge_obs, win.staged(B.e_obs, B.win), ne * 24);
+  if (edge_inv_sigma) memcpy(edge_inv_sigma, win.staged(B.e_isg, B.win), ne * 8);
+  return VO_OK;
+}
+
+int vo_kfstore_local_ba_apply(vo_kfstore *s, const double *poses6, const double *points, const uint8_t *edge_erase) {
+  const char *W = "vo_kfstore_local_ba_apply";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  VO_CHECK(s->ba_win.check_apply(W, s->gen, s->B.win, s->st));
+  const int32_t *r = s->ba_win.rec;
+  const size_t nc = (size_t)r[kBaNCams], np = (size_t)r[kBaNPoints], ne = (size_t)r[kBaNEdges];
+  if (!poses6 || (np > 0 && !points) || (ne > 0 && !edge_erase)) return VO_ERR_INVALID;
+  // staged as the kernels read it: Tcw12 per camera (SE3::exp on the host, :786-788) | points | erase bytes
+  uint8_t *h = s->ba_win.stage.data();
+  double *T = reinterpret_cast<double *>(h);
+  for (size_t c = 0; c < nc; c++) VO_CHECK(vo_se3_exp(poses6 + 6 * c, T + 12 * c, T + 12 * c + 9));
+  if (np) memcpy(h + nc * 96, points, np * 24);
+  if (ne) memcpy(h + nc * 96 + np * 24, edge_erase, ne);
+  const size_t bytes = nc * 96 + np * 24 + ne;
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));  // (not stale: nothing has changed since the window)
+  VO_CHECK(copy_h2d(s->B.in, h, bytes, s->st, W));
+  VO_CHECK(ba_apply_enqueue(kfstore_view(s), O, s->X, s->M, s->B, s->normals.as<double>(), connections_view(s->conn).status, (int)nc,
+                            (int)np, (int)ne, s->st));
+  s->obs_dirty = true, s->gen++;
+  return stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_refresh_points(vo_kfstore *s, int n, const int32_t *ids) {
+  const char *W = "vo_kfstore_refresh_points";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  if (n < 0 || (n > 0 && !ids)) return VO_ERR_INVALID;
+  if (n > s->B.max_points) {
+    set_error("%s: %d ids, the store was enabled for %d points", W, n, s->B.max_points);
+    return VO_ERR_CAPACITY;
+  }
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0) {
+      set_error("%s: entry %d: id %d is negative", W, i, ids[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(copy_h2d(s->B.ids_in, ids, (size_t)n * 4, s->st, W));
+  VO_CHECK(ba_refresh_enqueue(kfstore_view(s), O, s->X, s->M, s->B, s->normals.as<double>(), connections_view(s->conn).status, n, s->st));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_local_ba(vo_kfstore *s, vo_ba *ba, int current, const volatile unsigned char *stop, vo_lm_summary *summaries) {
+  const char *W = "vo_kfstore_local_ba";
+  VO_CHECK(need(s, W, kLayerLocalBa));
+  if (!ba) return VO_ERR_INVALID;
+  VO_CHECK(vo_kfstore_local_ba_window(s, current));
+  const KfBaView &B = s->B;
+  const KfWindow &win = s->ba_win;
+  VO_CHECK(s->ba_win.fetch(B.win, B.win_bytes, false, s->st, W));  // the ONE device-to-host copy
+  const int32_t *r = win.rec;
+  if (r[kBaStatus] == VO_KFSTORE_BA_WINDOW_OVERFLOW) {
+    set_error("%s: %d cameras, %d points, %d edges; the store was enabled for %d, %d, %d", W, r[kBaNCams], r[kBaNPoints], r[kBaNEdges],
+              B.max_cams, B.max_points, B.max_edges);
+    return VO_ERR_CAPACITY;
+  }
+  if (r[kBaStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    set_error("%s: the window of key-frame %d is empty (erased, or a camera without a pose)", W, current);
+    return VO_ERR_INVALID;
+  }
+  const double cam[5] = {s->M.cam[0], s->M.cam[1], s->M.cam[2], s->M.cam[3], s->M.cam[4]};  // float members widened (:543-548)
+  VO_CHECK(vo_ba_reset(ba, r[kBaNCams], win.staged(B.poses6, B.win), win.staged(B.cam_fixed, B.win), r[kBaNPoints],
+                       win.staged(B.points, B.win), r[kBaNEdges], win.staged(B.e_cam, B.win), win.staged(B.e_pt, B.win),
+                       win.staged(B.e_obs, B.win), win.staged(B.e_isg, B.win), cam));
+  VO_CHECK(vo_ba_local_ba(ba, stop, s->ba_erase.data(), summaries));  // (VO_ERR_STOPPED: the return at :594, no write-back)
+  VO_CHECK(vo_ba_get_state(ba, s->ba_poses.data(), s->ba_points.data()));
+  return vo_kfstore_local_ba_apply(s, s->ba_poses.data(), s->ba_points.data(), s->ba_erase.data());
+}
+
+}  // extern "C"

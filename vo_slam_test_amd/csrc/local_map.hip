@@ -8,7 +8,7 @@
 //                   written straight into the tracker's local-map arrays
 // Nothing here depends on which thread runs when: the vote counts are integer sums, the list is built by one thread, and
 // "first occurrence" is a property of the sorted index, not of an atomic race.
-#include "vo_common.h"
+#include "kfstore.h"
 
 namespace {
 

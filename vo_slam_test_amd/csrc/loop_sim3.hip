@@ -22,7 +22,7 @@
 // Every kernel behind k_loop_construct starts by reading the phase word and returns at once when the step is not due, so
 // rounds can be enqueued without knowing how many the walk needs.  No kernel waits on another workgroup; every loop is
 // bounded by a count clamped to its array.  Compiled with -ffp-contract=off.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "ba_math.h"
 #include "kf_area.h"
@@ -654,8 +654,6 @@ __global__ __launch_bounds__(256) void k_loop_project(LoopArgs A) {
   }
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct Layout {
   uint8_t *block;
   size_t at = 0;
@@ -693,7 +691,7 @@ extern "C" int vo_kfstore_loop_ransac_max_iters(int n) {
   return std::max(1, std::min(iterations, kRansacMaxIterations));
 }
 
-namespace vo {
+namespace {
 
 size_t loop_bytes(int NK, int max_cand, int max_pts, int max_rand, int n_slots) {
   Layout Y{nullptr};
@@ -709,6 +707,7 @@ KfLoopView loop_layout(void *block, int NK, int max_cand, int max_pts, int max_r
   return L;
 }
 
+// the tables and constants of the block, once (ransacMaxIters by N from the host's libm; the camera as doubles)
 int loop_init(const KfLoopView &L, const KfMapView &M, size_t bytes, hipStream_t st) {
   VO_HIP_CHECK(hipMemsetAsync(L.st, 0, bytes, st));
   // Sim3Solver::setRansacParameters(0.99, 20, 300) (sim3Solver.cpp:76-96) for every N a key-frame can give, with the host's
@@ -722,6 +721,7 @@ int loop_init(const KfLoopView &L, const KfMapView &M, size_t bytes, hipStream_t
   return VO_OK;
 }
 
+// a new call: the state reset, `current` checked, the front (match.hip: loop_bow_replay) and the solvers' construction
 int loop_begin_enqueue(const LoopArgs &A, int current, int n_cand, int fix_scale, int n_rand, int rand_max, hipStream_t st) {
   VO_HIP_CHECK(hipMemsetAsync(A.L.match_ids, 0xff, (size_t)A.L.NK * 4, st));
   hipLaunchKernelGGL(k_loop_begin, dim3(1), dim3(64), 0, st, A, current, n_cand, fix_scale, n_rand, rand_max);
@@ -732,6 +732,7 @@ int loop_begin_enqueue(const LoopArgs &A, int current, int n_cand, int fix_scale
   return VO_OK;
 }
 
+// `rounds` rounds (walk to the next verification or to the end, then verify), then the steps behind a match; launches only
 int loop_rounds_enqueue(const LoopArgs &A, int rounds, int fix_scale, hipStream_t st) {
   const KfLoopView &L = A.L;
   const unsigned search_grid = (unsigned)std::min((2 * A.S.NK + 3) / 4, 512);
@@ -755,4 +756,135 @@ int loop_rounds_enqueue(const LoopArgs &A, int rounds, int fix_scale, hipStream_
   return VO_OK;
 }
 
-}  // namespace vo
+LoopArgs loop_args(vo_kfstore *s, const KfObsView &O) {
+  const KfConnView C = connections_view(s->conn);
+  return LoopArgs{kfstore_view(s), O, C, s->X, s->M, s->F, s->L, C.status};
+}
+
+// the candidates and the rand() values are in the block already (L.cand, L.rand)
+int loop_compute_enqueue(vo_kfstore *s, int current, int n_cand, int fix_scale, int n_rand, int32_t rand_max, int max_rounds) {
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));  // "who observes p in key-frame j" (launches only, and only when the index is stale)
+  const LoopArgs A = loop_args(s, O);
+  VO_CHECK(loop_begin_enqueue(A, current, n_cand, fix_scale ? 1 : 0, n_rand, rand_max, s->st));
+  s->loop_fix_scale = fix_scale ? 1 : 0, s->loop_called = true;
+  return loop_rounds_enqueue(A, max_rounds, s->loop_fix_scale, s->st);
+}
+
+int loop_check(vo_kfstore *s, const char *W, int n_cand, const void *cand, int n_rand, const void *rand_values, int32_t rand_max,
+               int max_rounds) {
+  VO_CHECK(need(s, W, kLayerLoop));
+  if (n_cand < 1 || !cand || n_rand < 0 || (n_rand > 0 && !rand_values) || rand_max < 1 || max_rounds < 0) return VO_ERR_INVALID;
+  if (n_cand > s->L.C || n_rand > s->L.max_rand) {
+    set_error("%s: %d candidates / %d rand() values, the block was enabled for %d / %d", W, n_cand, n_rand, s->L.C, s->L.max_rand);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_loop(vo_kfstore *s, int max_candidates, int max_loop_points, int max_rand) {
+  const char *W = "vo_kfstore_enable_loop";
+  const bool args_ok = max_candidates >= 1 && max_candidates <= VO_KFSTORE_LOOP_MAX_CANDIDATES && max_loop_points >= 1 && max_rand >= 3;
+  if (const int rc = enable_begin(s, W, kLayerFuse, kLayerLoop, args_ok)) return rc < 0 ? rc : VO_OK;
+  const size_t bytes = loop_bytes(s->NK, max_candidates, max_loop_points, max_rand, s->okeys_cap);
+  VO_CHECK(s->lp.reserve(bytes));
+  s->L = loop_layout(s->lp.p, s->NK, max_candidates, max_loop_points, max_rand, s->okeys_cap);
+  const size_t down = (size_t)(kLoopStateInts + VO_KFSTORE_LOOP_MAX_CANDIDATES * kLoopPerInts + s->NK + max_loop_points) * 4 + 26 * 8;
+  VO_CHECK(s->lp_stage.reserve(std::max(((size_t)VO_KFSTORE_LOOP_MAX_CANDIDATES + (size_t)max_rand) * 4, down)));
+  VO_CHECK(loop_init(s->L, s->M, bytes, s->st));  // (synchronises: its tables are host temporaries)
+  s->layers |= kLayerLoop;
+  return VO_OK;
+}
+
+int vo_kfstore_compute_sim3_dev(vo_kfstore *s, int current, int n_cand, const int32_t *dev_cand, int fix_scale, int n_rand,
+                                const int32_t *dev_rand_values, int32_t rand_max, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3_dev";
+  VO_CHECK(loop_check(s, W, n_cand, dev_cand, n_rand, dev_rand_values, rand_max, max_rounds));
+  VO_HIP_CHECK(hipMemcpyAsync(s->L.cand, dev_cand, (size_t)n_cand * 4, hipMemcpyDeviceToDevice, s->st));
+  if (n_rand > 0) VO_HIP_CHECK(hipMemcpyAsync(s->L.rand, dev_rand_values, (size_t)n_rand * 4, hipMemcpyDeviceToDevice, s->st));
+  return loop_compute_enqueue(s, current, n_cand, fix_scale, n_rand, rand_max, max_rounds);
+}
+
+int vo_kfstore_compute_sim3(vo_kfstore *s, int current, int n_cand, const int32_t *cand, int fix_scale, int n_rand,
+                            const int32_t *rand_values, int32_t rand_max, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3";
+  VO_CHECK(loop_check(s, W, n_cand, cand, n_rand, rand_values, rand_max, max_rounds));
+  VO_CHECK(need_keyframe(s, W, current));
+  for (int i = 0; i < n_cand; i++) VO_CHECK(need_keyframe(s, W, cand[i]));
+  // one copy: [16 candidates | rand() values] lands on L.cand .. L.rand, which the block keeps side by side
+  int32_t *up = reinterpret_cast<int32_t *>(s->lp_stage.data());
+  memset(up, 0xff, VO_KFSTORE_LOOP_MAX_CANDIDATES * 4);
+  memcpy(up, cand, (size_t)n_cand * 4);
+  if (n_rand > 0) memcpy(up + VO_KFSTORE_LOOP_MAX_CANDIDATES, rand_values, (size_t)n_rand * 4);
+  VO_CHECK(copy_h2d(s->L.cand, up, ((size_t)VO_KFSTORE_LOOP_MAX_CANDIDATES + (size_t)n_rand) * 4, s->st, W));
+  VO_CHECK(loop_compute_enqueue(s, current, n_cand, fix_scale, n_rand, rand_max, max_rounds));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_compute_sim3_continue(vo_kfstore *s, int max_rounds) {
+  const char *W = "vo_kfstore_compute_sim3_continue";
+  VO_CHECK(need(s, W, kLayerLoop));
+  if (max_rounds < 0) return VO_ERR_INVALID;
+  if (!s->loop_called) {
+    set_error("%s: no vo_kfstore_compute_sim3 has been enqueued on this store", W);
+    return VO_ERR_INVALID;
+  }
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  return loop_rounds_enqueue(loop_args(s, O), max_rounds, s->loop_fix_scale, s->st);
+}
+
+int vo_kfstore_loop_result(vo_kfstore *s, int32_t *record, int32_t *per_cand, double *Scm, double *Scw, int32_t *match_ids,
+                           int32_t *n_loop_points, int32_t *loop_point_ids) {
+  const char *W = "vo_kfstore_loop_result";
+  VO_CHECK(need(s, W, kLayerLoop));
+  const KfLoopView &L = s->L;
+  int32_t st[kLoopStateInts], per[VO_KFSTORE_LOOP_MAX_CANDIDATES * kLoopPerInts];
+  double sims[26];
+  VO_CHECK(copy_d2h(st, L.st, sizeof(st), s->st, W));
+  VO_CHECK(copy_d2h(per, L.per, sizeof(per), s->st, W));
+  VO_CHECK(copy_d2h(sims, L.Scm, 13 * 8, s->st, W));
+  VO_CHECK(copy_d2h(sims + 13, L.Scw, 13 * 8, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  const int n_cur = std::min(std::max(st[kLsNCur], 0), s->NK), n_lp = st[kLsState] >= 2 ? std::min(std::max(st[kLsNLoop], 0), L.P) : 0;
+  if (match_ids && n_cur > 0) VO_CHECK(copy_d2h(match_ids, L.match_ids, (size_t)n_cur * 4, s->st, W));
+  if (loop_point_ids && n_lp > 0) VO_CHECK(copy_d2h(loop_point_ids, L.loop_ids, (size_t)n_lp * 4, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  if (record) {
+    memset(record, 0, 16 * 4);
+    memcpy(record, st, 9 * 4);
+  }
+  if (per_cand) memcpy(per_cand, per, (size_t)L.C * kLoopPerInts * 4);
+  if (Scm) memcpy(Scm, sims, 13 * 8);
+  if (Scw) memcpy(Scw, sims + 13, 13 * 8);
+  if (n_loop_points) *n_loop_points = n_lp;
+  return VO_OK;
+}
+
+int vo_kfstore_loop_solver_inputs(vo_kfstore *s, int position, int32_t *n, double *cam1_points, double *cam2_points, double *pixels1,
+                                  double *pixels2, int32_t *max_err1, int32_t *max_err2, int32_t *matched_index) {
+  const char *W = "vo_kfstore_loop_solver_inputs";
+  VO_CHECK(need(s, W, kLayerLoop));
+  const KfLoopView &L = s->L;
+  if (position < 0 || position >= L.C || !n) return VO_ERR_INVALID;
+  int32_t per[kLoopPerInts];
+  VO_CHECK(copy_d2h(per, L.per + position * kLoopPerInts, sizeof(per), s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  const size_t N = (size_t)std::min(std::max(per[kLpN], 0), s->NK), o = (size_t)position * s->NK;
+  *n = (int32_t)N;
+  if (N == 0) return VO_OK;
+  if (cam1_points) VO_CHECK(copy_d2h(cam1_points, L.pc1 + o * 3, N * 24, s->st, W));
+  if (cam2_points) VO_CHECK(copy_d2h(cam2_points, L.pc2 + o * 3, N * 24, s->st, W));
+  if (pixels1) VO_CHECK(copy_d2h(pixels1, L.px1 + o * 2, N * 16, s->st, W));
+  if (pixels2) VO_CHECK(copy_d2h(pixels2, L.px2 + o * 2, N * 16, s->st, W));
+  if (max_err1) VO_CHECK(copy_d2h(max_err1, L.me1 + o, N * 4, s->st, W));
+  if (max_err2) VO_CHECK(copy_d2h(max_err2, L.me2 + o, N * 4, s->st, W));
+  if (matched_index) VO_CHECK(copy_d2h(matched_index, L.midx + o, N * 4, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+}  // extern "C"

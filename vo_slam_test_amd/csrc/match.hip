@@ -3,7 +3,7 @@
 // (:1240-1256) becomes one all-pairs kernel; the sequential, order-dependent assignment logic of
 // searchByProjection (:18-148, :274-353) is replayed on the host over the device-computed matrix
 // so that match pairs stay identical to the reference's visiting order.
-#include "vo_common.h"
+#include "kfstore.h"
 #include "block_sort.h"
 #include "new_points_geom.h"
 

@@ -4,13 +4,13 @@
 // searchForTriangulation (match.hip: k_tri_walk, k_node_replay) through the parallax test, the three-way choice of the
 // point, the depth, reprojection and scale gates (:197-341), then the commit of :344-355 in ascending idx1.
 // Compiled with -ffp-contract=off (float gates that must round like the x86-64 reference build).
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "triangulate.h"
 
-namespace {
+#include <algorithm>
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+namespace {
 
 // every array of the block once: measure (block == nullptr) or assign
 struct MapLayout {
@@ -19,7 +19,7 @@ struct MapLayout {
   template <class T>
   void take(T *&field, size_t bytes) {
     field = block ? reinterpret_cast<T *>(block + at) : nullptr;
-    at += up16(bytes);
+    at += vo::up16(bytes);
   }
 };
 
@@ -262,7 +262,9 @@ __global__ __launch_bounds__(256) void k_np_create(CreateArgs A) {
 
 }  // namespace
 
-namespace vo {
+namespace {
+
+using namespace vo;
 
 size_t mapping_bytes(int max_kf, int NK) {
   MapLayout L{nullptr};
@@ -299,6 +301,7 @@ int mapping_split_xy(const KfMapView &M, int k, int n, const float *dev_xy, hipS
   return VO_OK;
 }
 
+// (ref_kf: the column of a store with local BA, else NULL -- a created point's keyFrame_ref_ is `current`, mappoint.cpp:37)
 int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, double *normals, int *ref_kf, int current, int step,
               hipStream_t st) {
   CreateArgs A{S, X, M, normals, ref_kf, current, step};
@@ -307,4 +310,167 @@ int np_create(const KfStoreView &S, const KfCullView &X, const KfMapView &M, dou
   return VO_OK;
 }
 
-}  // namespace vo
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_mapping(vo_kfstore *s, const float cam[6], int n_levels, const float *scale_factors, int32_t first_point_id) {
+  const char *W = "vo_kfstore_enable_mapping";
+  const bool args_ok = cam && scale_factors && n_levels >= 1 && n_levels <= 16 && first_point_id >= 0;
+  if (const int rc = enable_begin(s, W, kLayerCulling, kLayerMapping, args_ok)) return rc < 0 ? rc : VO_OK;
+  if (s->NK > 16384) {
+    set_error("%s: %d features per key-frame, the search kernel handles 16384", W, s->NK);
+    return VO_ERR_CAPACITY;
+  }
+  s->map_bytes = mapping_bytes(s->max_kf, s->NK);
+  VO_CHECK(s->map.reserve(s->map_bytes));
+  s->M = mapping_layout(s->map.p, s->max_kf, s->NK);
+  s->M.n_levels = n_levels;
+  for (int i = 0; i < 6; i++) s->M.cam[i] = cam[i];
+  for (int i = 0; i < 16; i++) s->M.sf[i] = scale_factors[i < n_levels ? i : n_levels - 1];
+  VO_CHECK(mapping_init(s->M, s->map_bytes, first_point_id, s->st));
+  VO_CHECK(stream_sync(s->st, W));
+  s->layers |= kLayerMapping;
+  return VO_OK;
+}
+
+int vo_kfstore_set_pose(vo_kfstore *s, int keyframe, const double *Tcw12) {
+  const char *W = "vo_kfstore_set_pose";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  if (!Tcw12) return VO_ERR_INVALID;
+  s->gen++;
+  // the pose-set word lies behind the pose (the thirteenth slot): one copy
+  double *h = reinterpret_cast<double *>(s->stage.data());
+  memcpy(h, Tcw12, 96);
+  const int32_t one[2] = {1, 0};
+  memcpy(h + 12, one, 8);
+  VO_CHECK(copy_h2d(np_pose(s->M, keyframe), h, kNpPoseDoubles * 8, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_pose_dev(vo_kfstore *s, int keyframe, const double *dev_Tcw12) {
+  const char *W = "vo_kfstore_set_pose_dev";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  if (!dev_Tcw12) return VO_ERR_INVALID;
+  s->gen++;
+  return mapping_set_pose_dev(s->M, keyframe, dev_Tcw12, s->st);
+}
+
+int vo_kfstore_set_keypoint_xy(vo_kfstore *s, int keyframe, const float *xy) {
+  const char *W = "vo_kfstore_set_keypoint_xy";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe], NK = (size_t)s->NK;
+  if (n == 0) return VO_OK;
+  if (!xy) return VO_ERR_INVALID;
+  s->gen++;
+  // the two columns of a key-frame lie side by side: staged whole (zero beyond n), one copy
+  float *hx = reinterpret_cast<float *>(s->stage.data()), *hy = hx + NK;  // (a record is longer than 8 bytes a feature)
+  for (size_t i = 0; i < NK; i++) hx[i] = i < n ? xy[2 * i] : 0.f, hy[i] = i < n ? xy[2 * i + 1] : 0.f;
+  VO_CHECK(copy_h2d(np_x(s->M, keyframe), hx, NK * 8, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_set_keypoint_xy_dev(vo_kfstore *s, int keyframe, const float *dev_xy) {
+  const char *W = "vo_kfstore_set_keypoint_xy_dev";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const int n = s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  if (!dev_xy) return VO_ERR_INVALID;
+  s->gen++;
+  return mapping_split_xy(s->M, keyframe, n, dev_xy, s->st);
+}
+
+int vo_kfstore_next_point_id(vo_kfstore *s, int32_t *id) {
+  const char *W = "vo_kfstore_next_point_id";
+  VO_CHECK(need(s, W, kLayerMapping));
+  if (!id) return VO_ERR_INVALID;
+  VO_CHECK(copy_d2h(id, s->M.counter, 4, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_create_map_points(vo_kfstore *s, int current, int max_neighbors) {
+  const char *W = "vo_kfstore_create_map_points";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, current));
+  if (max_neighbors < 1 || max_neighbors > kKfGraphNb) {
+    set_error("%s: max_neighbors %d outside [1, %d]", W, max_neighbors, kKfGraphNb);
+    return VO_ERR_INVALID;
+  }
+  // (that `current` has been erased or has no pose only the device knows: k_tri_walk then reaches no neighbour and raises
+  //  the sticky VO_KFSTORE_CONNECTIONS_INVALID)
+  const KfStoreView V = kfstore_view(s);
+  const KfConnView C = connections_view(s->conn);
+  for (int i = 0; i < max_neighbors; i++) {  // step i + 1 reads the flags step i wrote: walk, replay, create per neighbour
+    VO_CHECK(tri_walk_replay(V, s->X, s->M, s->graph.as<int>(), C.status, current, i, s->st));
+    VO_CHECK(np_create(V, s->X, s->M, s->normals.as<double>(), (s->layers & kLayerLocalBa) ? s->B.ref_kf : nullptr, current, i, s->st));
+  }
+  s->obs_dirty = true, s->gen++;  // (whether anything was created only the device knows)
+  if (s->layers & kLayerUpkeep) VO_CHECK(upkeep_created_enqueue(s->M, s->U, C.status, current, s->st));  // addedMapPoints_.push_back (:355)
+  return VO_OK;
+}
+
+int vo_kfstore_new_points_result(vo_kfstore *s, int32_t *n_neighbors, int32_t *neighbor_kf, int32_t *status, int32_t *n_matches,
+                                 int32_t *n_created, int32_t *created, int created_capacity) {
+  const char *W = "vo_kfstore_new_points_result";
+  VO_CHECK(need(s, W, kLayerMapping));
+  if (!n_neighbors || created_capacity < 0 || (created_capacity > 0 && !created)) return VO_ERR_INVALID;
+  int32_t rec[kNpRecInts] = {0};
+  VO_CHECK(copy_d2h(rec, s->M.rec, sizeof(rec), s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  const int n = std::min(std::max(rec[0], 0), kKfGraphNb);
+  const int total = std::min(std::max(rec[1], 0), kKfGraphNb * s->NK);
+  *n_neighbors = n;
+  for (int i = 0; i < kKfGraphNb; i++) {
+    if (neighbor_kf) neighbor_kf[i] = i < n ? rec[4 + 4 * i] : -1;
+    if (status) status[i] = i < n ? rec[4 + 4 * i + 1] : VO_KFSTORE_NP_NOT_REACHED;
+    if (n_matches) n_matches[i] = i < n ? rec[4 + 4 * i + 2] : 0;
+    if (n_created) n_created[i] = i < n ? rec[4 + 4 * i + 3] : 0;
+  }
+  const int rows = std::min(total, created_capacity);
+  if (rows > 0) {
+    VO_CHECK(copy_d2h(created, s->M.created, (size_t)rows * 16, s->st, W));
+    VO_CHECK(stream_sync(s->st, W));
+  }
+  if (total > created_capacity) {
+    set_error("%s: the call created %d points, created_capacity is %d", W, total, created_capacity);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+int vo_kfstore_get_points(vo_kfstore *s, int keyframe, uint8_t *flags, int32_t *ids, double *points, uint8_t *point_desc,
+                          float *min_distance, float *max_distance, double *normals) {
+  const char *W = "vo_kfstore_get_points";
+  if (!s) return VO_ERR_INVALID;
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  const size_t n = (size_t)s->n[(size_t)keyframe];
+  if (n == 0) return VO_OK;
+  const KfStoreView &V = s->V;
+  const uint8_t *r = s->record(keyframe);
+  if (flags) VO_CHECK(copy_d2h(flags, r + V.o_flags, n, s->st, W));
+  if (ids) VO_CHECK(copy_d2h(ids, r + V.o_ids, n * 4, s->st, W));
+  if (points) VO_CHECK(copy_d2h(points, r + V.o_points, n * 24, s->st, W));
+  if (point_desc) VO_CHECK(copy_d2h(point_desc, r + V.o_pdesc, n * 32, s->st, W));
+  if (min_distance) VO_CHECK(copy_d2h(min_distance, r + V.o_mind, n * 4, s->st, W));
+  if (max_distance) VO_CHECK(copy_d2h(max_distance, r + V.o_maxd, n * 4, s->st, W));
+  if (normals) VO_CHECK(copy_d2h(normals, s->normals.as<double>() + (size_t)keyframe * s->NK * 3, n * 24, s->st, W));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_get_pose(vo_kfstore *s, int keyframe, double *Tcw12, int32_t *pose_set) {
+  const char *W = "vo_kfstore_get_pose";
+  VO_CHECK(need(s, W, kLayerMapping));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  double h[kNpPoseDoubles];
+  VO_CHECK(copy_d2h(h, np_pose(s->M, keyframe), sizeof(h), s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  if (Tcw12) memcpy(Tcw12, h, 96);
+  if (pose_set) memcpy(pose_set, h + 12, 4);
+  return VO_OK;
+}
+
+}  // extern "C"

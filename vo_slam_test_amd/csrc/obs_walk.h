@@ -1,4 +1,4 @@
-// obs_walk.h -- the walk over one id's run of the observation index (vo_common.h: KfObsView), shared
+// obs_walk.h -- the walk over one id's run of the observation index (kfstore.h: KfObsView), shared
 // by the kernels that read "who holds this id": k_conn_count (connections.hip), the culling kernels (cull.hip), the local-BA
 // window and write-back (local_ba_store.hip), the map-point upkeep (point_upkeep.hip) and the fusion (fuse.hip), which
 // walks it through an overlay.
@@ -43,7 +43,7 @@ __device__ __forceinline__ void obs_run_holders(const KfObsView &O, int NK, int 
   });
 }
 
-// ---- the walk through the overlay (vo_common.h: KfOverlay), by one WAVEFRONT: every entry that may
+// ---- the walk through the overlay (kfstore.h: KfOverlay), by one WAVEFRONT: every entry that may
 // carry the id whose run starts at slot p -- the frozen run of p, the frozen runs of the slots chained behind p, and the
 // entries added to any of them in this call.  f(valid, entry) is called by all 64 lanes together (it may ballot); the
 // caller validates an entry against the live feature word.  Every index read from memory is checked against its array, and

@@ -17,9 +17,11 @@
 // No kernel waits on another workgroup; every loop is bounded by a count read once.  An id has one entry and an entry one
 // thread, so every byte an erase clears has one writer; the descriptor of an id listed twice is written twice with the same
 // bytes.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "obs_walk.h"
+
+#include <algorithm>
 
 namespace {
 
@@ -390,8 +392,6 @@ __global__ void k_up_init(KfUpkeepView U) {
   if (threadIdx.x < kUpRecInts) U.rec[threadIdx.x] = 0;
 }
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
-
 struct UpLayout {
   uint8_t *block;
   size_t at = 0;
@@ -416,7 +416,7 @@ void up_layout(UpLayout &L, KfUpkeepView &U, int R, int NK) {
 
 }  // namespace
 
-namespace vo {
+namespace {
 
 size_t upkeep_bytes(int max_recent, int NK) {
   UpLayout L{nullptr};
@@ -438,6 +438,10 @@ int upkeep_init(const KfUpkeepView &U, hipStream_t st) {
   return VO_OK;
 }
 
+}  // namespace
+
+namespace vo {
+
 int upkeep_descriptors_enqueue(const KfStoreView &S, const KfObsView &O, const KfUpkeepView &U, int *status, int n, const int *dev_ids,
                                hipStream_t st) {
   if (n <= 0) return VO_OK;
@@ -448,6 +452,20 @@ int upkeep_descriptors_enqueue(const KfStoreView &S, const KfObsView &O, const K
   return VO_OK;
 }
 
+int upkeep_created_enqueue(const KfMapView &M, const KfUpkeepView &U, int *status, int current, hipStream_t st) {
+  // the created rows are (key-frame, idx1, idx2, id): the ids at a stride of four, their number in the result record
+  hipLaunchKernelGGL(k_up_append, dim3(1), dim3(kSeq), 0, st, U, status, (int)VO_KFSTORE_UPKEEP_CREATED, current,
+                     reinterpret_cast<const int *>(M.created) + 3, 4, kKfGraphNb * M.NK, (const int *)(M.rec + 1));
+  VO_HIP_CHECK(hipGetLastError());
+  return VO_OK;
+}
+
+}  // namespace vo
+
+namespace {
+
+// processNewKeyFrame up to the connection update: classify (U.list = the tracked ids, U.cand = the ids to append, per feature
+// of `current`), refresh, descriptors, append
 int upkeep_process_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                            const KfUpkeepView &U, double *normals, int *status, int current, hipStream_t st) {
   hipLaunchKernelGGL(k_up_classify, dim3((unsigned)((S.NK + 255) / 256)), dim3(256), 0, st, S, O, X, U, status, current);
@@ -456,14 +474,6 @@ int upkeep_process_enqueue(const KfStoreView &S, const KfObsView &O, const KfCul
   VO_CHECK(upkeep_descriptors_enqueue(S, O, U, status, S.NK, U.list, st));              // computeDescriptor (:120)
   hipLaunchKernelGGL(k_up_append, dim3(1), dim3(kSeq), 0, st, U, status, (int)VO_KFSTORE_UPKEEP_PROCESS, current, (const int *)U.cand, 1,
                      S.NK, (const int *)nullptr);
-  VO_HIP_CHECK(hipGetLastError());
-  return VO_OK;
-}
-
-int upkeep_created_enqueue(const KfMapView &M, const KfUpkeepView &U, int *status, int current, hipStream_t st) {
-  // the created rows are (key-frame, idx1, idx2, id): the ids at a stride of four, their number in the result record
-  hipLaunchKernelGGL(k_up_append, dim3(1), dim3(kSeq), 0, st, U, status, (int)VO_KFSTORE_UPKEEP_CREATED, current,
-                     reinterpret_cast<const int *>(M.created) + 3, 4, kKfGraphNb * M.NK, (const int *)(M.rec + 1));
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
@@ -482,4 +492,149 @@ int upkeep_cull_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullVi
   return VO_OK;
 }
 
-}  // namespace vo
+// "<W>: n ids, the store takes L": the longest id list a call takes
+int up_list_fits(const vo_kfstore *s, const char *W, int n) {
+  if (n <= s->U.L) return VO_OK;
+  set_error("%s: %d ids, the store takes %d (max_recent + max_features)", W, n, s->U.L);
+  return VO_ERR_CAPACITY;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_point_upkeep(vo_kfstore *s, int max_recent) {
+  const char *W = "vo_kfstore_enable_point_upkeep";
+  if (const int rc = enable_begin(s, W, kLayerLocalBa, kLayerUpkeep, max_recent >= 1)) return rc < 0 ? rc : VO_OK;
+  VO_CHECK(s->up.reserve(upkeep_bytes(max_recent, s->NK)));
+  s->U = upkeep_layout(s->up.p, max_recent, s->NK);
+  VO_CHECK(s->up_stage.reserve((size_t)s->U.L * 12));
+  VO_CHECK(connections_reserve(s->conn, 1, nullptr));  // process_new_keyframe's update of one key-frame allocates nothing
+  VO_CHECK(upkeep_init(s->U, s->st));
+  VO_CHECK(stream_sync(s->st, W));
+  s->layers |= kLayerUpkeep;
+  return VO_OK;
+}
+
+int vo_kfstore_compute_descriptors_dev(vo_kfstore *s, int n, const int32_t *dev_ids) {
+  const char *W = "vo_kfstore_compute_descriptors_dev";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  if (n < 0 || (n > 0 && !dev_ids)) return VO_ERR_INVALID;
+  VO_CHECK(up_list_fits(s, W, n));
+  if (n == 0) return VO_OK;
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return upkeep_descriptors_enqueue(kfstore_view(s), O, s->U, connections_view(s->conn).status, n, dev_ids, s->st);
+}
+
+int vo_kfstore_compute_descriptors(vo_kfstore *s, int n, const int32_t *ids) {
+  const char *W = "vo_kfstore_compute_descriptors";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  if (n < 0 || (n > 0 && !ids)) return VO_ERR_INVALID;
+  VO_CHECK(up_list_fits(s, W, n));
+  for (int i = 0; i < n; i++)
+    if (ids[i] < 0) {
+      set_error("%s: entry %d: id %d is negative", W, i, ids[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  memcpy(s->up_stage.data(), ids, (size_t)n * 4);
+  VO_CHECK(copy_h2d(s->U.list, s->up_stage.data(), (size_t)n * 4, s->st, W));
+  VO_CHECK(vo_kfstore_compute_descriptors_dev(s, n, s->U.list));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_process_new_keyframe(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_process_new_keyframe";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  VO_CHECK(need_keyframe(s, W, current));
+  // (that `current` has been erased only the device knows: nothing is then listed, and the sticky INVALID is raised)
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  const KfStoreView V = kfstore_view(s);
+  VO_CHECK(upkeep_process_enqueue(V, O, s->X, s->M, s->B, s->U, s->normals.as<double>(), connections_view(s->conn).status, current, s->st));
+  s->gen++;  // (flags and ids stay: the index does not go stale)
+  return connections_update(s->conn, V, O, 1, s->U.head + 2, s->st);  // keyframe_curr_->updateConnections() (:128)
+}
+
+int vo_kfstore_add_point_stats_dev(vo_kfstore *s, int n, const int32_t *dev_ids, const int32_t *dev_visible, const int32_t *dev_found) {
+  const char *W = "vo_kfstore_add_point_stats_dev";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  if (n < 0 || (n > 0 && (!dev_ids || !dev_visible || !dev_found))) return VO_ERR_INVALID;
+  s->gen++;
+  return upkeep_stats_enqueue(s->U, n, dev_ids, dev_visible, dev_found, s->st);
+}
+
+int vo_kfstore_add_point_stats(vo_kfstore *s, int n, const int32_t *ids, const int32_t *visible, const int32_t *found) {
+  const char *W = "vo_kfstore_add_point_stats";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  if (n < 0 || (n > 0 && (!ids || !visible || !found))) return VO_ERR_INVALID;
+  VO_CHECK(up_list_fits(s, W, n));
+  for (int i = 0; i < n; i++)
+    if (visible[i] < 0 || found[i] < 0) {
+      set_error("%s: entry %d: a negative increment (%d visible, %d found)", W, i, visible[i], found[i]);
+      return VO_ERR_INVALID;
+    }
+  if (n == 0) return VO_OK;
+  // staged as the block's list holds them: ids | visible | found, L entries each; one copy
+  const size_t L = (size_t)s->U.L;
+  int32_t *h = reinterpret_cast<int32_t *>(s->up_stage.data());
+  memset(h, 0xff, L * 4), memset(h + L, 0, L * 8);  // (beyond n: no id, no increment)
+  memcpy(h, ids, (size_t)n * 4), memcpy(h + L, visible, (size_t)n * 4), memcpy(h + 2 * L, found, (size_t)n * 4);
+  VO_CHECK(copy_h2d(s->U.list, h, L * 12, s->st, W));
+  VO_CHECK(vo_kfstore_add_point_stats_dev(s, n, s->U.list, s->U.list + L, s->U.list + 2 * L));
+  return stream_sync(s->st, W);
+}
+
+int vo_kfstore_cull_map_points(vo_kfstore *s, int current) {
+  const char *W = "vo_kfstore_cull_map_points";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  VO_CHECK(need_keyframe(s, W, current));
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  VO_CHECK(upkeep_cull_enqueue(kfstore_view(s), O, s->X, s->U, current, s->st));
+  s->obs_dirty = true, s->gen++;  // (whether anything was erased only the device knows)
+  return VO_OK;
+}
+
+int vo_kfstore_recent_points(vo_kfstore *s, int32_t *n, int32_t *ids, int32_t *first_kf, int32_t *found, int32_t *visible) {
+  const char *W = "vo_kfstore_recent_points";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  const size_t R = (size_t)s->U.R;
+  std::vector<int32_t> h(4 * R + 4);
+  VO_CHECK(copy_d2h(h.data(), s->U.head, 16, s->st, W));
+  const int32_t *cols[4] = {s->U.id, s->U.first_kf, s->U.found, s->U.visible};
+  for (int c = 0; c < 4; c++) VO_CHECK(copy_d2h(h.data() + 4 + c * R, cols[c], R * 4, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  const int cnt = std::min(std::max(h[0], 0), s->U.R);
+  std::vector<int> order((size_t)cnt);
+  for (int i = 0; i < cnt; i++) order[(size_t)i] = i;
+  const int32_t *id = h.data() + 4;
+  std::sort(order.begin(), order.end(), [&](int a, int b) { return id[a] < id[b]; });  // (an id has one entry)
+  int32_t *out[4] = {ids, first_kf, found, visible};
+  for (int c = 0; c < 4; c++)
+    if (out[c])
+      for (int i = 0; i < cnt; i++) out[c][i] = h[4 + c * R + (size_t)order[(size_t)i]];
+  if (n) *n = cnt;
+  return VO_OK;
+}
+
+int vo_kfstore_upkeep_result(vo_kfstore *s, int32_t *record, int32_t *erased_ids) {
+  const char *W = "vo_kfstore_upkeep_result";
+  VO_CHECK(need(s, W, kLayerUpkeep));
+  int32_t rec[kUpRecInts];
+  std::vector<int32_t> er((size_t)s->U.R);
+  VO_CHECK(copy_d2h(rec, s->U.rec, sizeof(rec), s->st, W));
+  if (erased_ids) VO_CHECK(copy_d2h(er.data(), s->U.erased, er.size() * 4, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  if (record) memcpy(record, rec, sizeof(rec));
+  if (erased_ids) {
+    const int ne = rec[kUpKind] == VO_KFSTORE_UPKEEP_CULL ? std::min(std::max(rec[kUpNErased], 0), s->U.R) : 0;
+    std::sort(er.begin(), er.begin() + ne);
+    memcpy(erased_ids, er.data(), (size_t)ne * 4);
+  }
+  return VO_OK;
+}
+
+}  // extern "C"

@@ -12,7 +12,7 @@
 // The order of the edges comes from counts and a scan; the only atomics are integer sums of the record.  Every index read
 // from memory is checked against its array before it addresses anything.
 // Compiled with -ffp-contract=off: sim3_compose.h rounds every double operation on its own.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include "sim3_compose.h"
 
@@ -22,7 +22,7 @@ using namespace vo;
 
 enum { kOk = VO_KFSTORE_BA_WINDOW_OK, kEmpty = VO_KFSTORE_BA_WINDOW_EMPTY, kOverflow = VO_KFSTORE_BA_WINDOW_OVERFLOW };
 
-size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+PgInputs pg_inputs(void *block, int n_corr, int n_lc, int n_cp);  // (behind the kernels)
 
 struct PgLayout {
   uint8_t *block;
@@ -415,10 +415,6 @@ __global__ void k_pg_add_edge(KfPgView P, KfCullView X, int a, int b) {
   }
 }
 
-}  // namespace
-
-namespace vo {
-
 PgInputs pg_inputs(void *block, int n_corr, int n_lc, int n_cp) {
   PgLayout L{reinterpret_cast<uint8_t *>(block)};
   PgInputs I{};
@@ -455,12 +451,14 @@ int pg_store_init(const KfPgView &P, hipStream_t st) {
   return VO_OK;
 }
 
+// addLoopEdge both ways and both erase locks; one launch
 int pg_add_loop_edge(const KfPgView &P, const KfCullView &X, int a, int b, hipStream_t st) {
   hipLaunchKernelGGL(k_pg_add_edge, dim3(1), dim3(64), 0, st, P, X, a, b);
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
 }
 
+// four launches: nodes (with the inputs' checks and the node Sim3s), counts, layout, emit
 int pg_window_enqueue(const KfStoreView &S, const KfConnView &C, const KfCullView &X, const KfMapView &M, const KfPgView &P,
                       const PgInputs &I, int curr, int match, hipStream_t st) {
   PgArgs A{S, C, X, M, P, I, curr, match};
@@ -473,6 +471,7 @@ int pg_window_enqueue(const KfStoreView &S, const KfConnView &C, const KfCullVie
   return VO_OK;
 }
 
+// two launches on the solver's result in P.sol: poses and S_wr, then the re-anchoring with the refresh list
 int pg_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView &X, const KfMapView &M, const KfBaView &B,
                      const KfPgView &P, const PgInputs &I, int n_nodes, hipStream_t st) {
   const int in_lds = n_nodes <= kPgLdsNodes ? 1 : 0;
@@ -484,4 +483,216 @@ int pg_apply_enqueue(const KfStoreView &S, const KfObsView &O, const KfCullView 
   return VO_OK;
 }
 
-}  // namespace vo
+int pg_check_counts(const vo_kfstore *s, const char *W, int curr, int match, int n_corr, int n_lc, int n_cp) {
+  VO_CHECK(need_keyframe(s, W, curr));
+  VO_CHECK(need_keyframe(s, W, match));
+  if (n_corr < 0 || n_lc < 0 || n_cp < 0) return VO_ERR_INVALID;
+  if (n_corr > s->P.max_corr || n_lc > s->P.max_edges || n_cp > s->P.max_cp) {
+    set_error("%s: %d corrected key-frames, %d loop connections, %d corrected points; the store was enabled for %d, %d, %d", W, n_corr,
+              n_lc, n_cp, s->P.max_corr, s->P.max_edges, s->P.max_cp);
+    return VO_ERR_CAPACITY;
+  }
+  return VO_OK;
+}
+
+int pg_enqueue_window(vo_kfstore *s, int curr, int match, int n_corr, int n_lc, int n_cp) {
+  const PgInputs I = pg_inputs(s->P.in, n_corr, n_lc, n_cp);
+  VO_CHECK(pg_window_enqueue(kfstore_view(s), connections_view(s->conn), s->X, s->M, s->P, I, curr, match, s->st));
+  s->pg_counts[0] = n_corr, s->pg_counts[1] = n_lc, s->pg_counts[2] = n_cp;
+  s->pg_win.begin(s->gen);
+  return VO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vo_kfstore_enable_pose_graph(vo_kfstore *s, int max_edges, int max_corrected, int max_corrected_points) {
+  const char *W = "vo_kfstore_enable_pose_graph";
+  const bool args_ok = max_edges >= 1 && max_corrected >= 1 && max_corrected_points >= 1;
+  if (const int rc = enable_begin(s, W, kLayerLocalBa, kLayerPoseGraph, args_ok)) return rc < 0 ? rc : VO_OK;
+  VO_CHECK(s->pg.reserve(pg_store_bytes(s->max_kf, s->NK, max_edges, max_corrected, max_corrected_points)));
+  s->P = pg_store_layout(s->pg.p, s->max_kf, s->NK, max_edges, max_corrected, max_corrected_points);
+  VO_CHECK(s->pg_win.stage.reserve(std::max(s->P.win_bytes, std::max(s->P.in_bytes, s->P.sol_bytes))));
+  s->pg_ledge.assign((size_t)s->max_kf * (1 + VO_KFSTORE_MAX_LOOP_EDGES), 0);
+  s->pg_q.resize((size_t)s->P.max_nodes * 4), s->pg_t.resize((size_t)s->P.max_nodes * 3);
+  VO_CHECK(pg_store_init(s->P, s->st));
+  VO_CHECK(stream_sync(s->st, W));
+  s->layers |= kLayerPoseGraph;
+  return VO_OK;
+}
+
+int vo_kfstore_add_loop_edge(vo_kfstore *s, int a, int b) {
+  const char *W = "vo_kfstore_add_loop_edge";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  VO_CHECK(need_keyframe(s, W, a));
+  VO_CHECK(need_keyframe(s, W, b));
+  if (a == b) {
+    set_error("%s: key-frame %d cannot be its own loop edge", W, a);
+    return VO_ERR_INVALID;
+  }
+  const int stride = 1 + VO_KFSTORE_MAX_LOOP_EDGES;
+  int32_t *ra = s->pg_ledge.data() + (size_t)a * stride, *rb = s->pg_ledge.data() + (size_t)b * stride;
+  const bool a_has = std::find(ra + 1, ra + 1 + ra[0], b) != ra + 1 + ra[0], b_has = std::find(rb + 1, rb + 1 + rb[0], a) != rb + 1 + rb[0];
+  if ((!a_has && ra[0] >= VO_KFSTORE_MAX_LOOP_EDGES) || (!b_has && rb[0] >= VO_KFSTORE_MAX_LOOP_EDGES)) {
+    set_error("%s: key-frame %d or %d holds %d loop edges already", W, a, b, VO_KFSTORE_MAX_LOOP_EDGES);
+    return VO_ERR_CAPACITY;
+  }
+  if (!a_has) ra[1 + ra[0]++] = b;
+  if (!b_has) rb[1 + rb[0]++] = a;
+  s->gen++;
+  return pg_add_loop_edge(s->P, s->X, a, b, s->st);  // (a repeat still sets both locks, as addLoopEdge does)
+}
+
+int vo_kfstore_get_loop_edges(vo_kfstore *s, int keyframe, int32_t *n, int32_t *edges) {
+  const char *W = "vo_kfstore_get_loop_edges";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  VO_CHECK(need_keyframe(s, W, keyframe));
+  int32_t h[1 + VO_KFSTORE_MAX_LOOP_EDGES];
+  VO_CHECK(copy_d2h(h, s->P.n_ledge + keyframe, 4, s->st, W));
+  VO_CHECK(copy_d2h(h + 1, s->P.ledge + (size_t)keyframe * VO_KFSTORE_MAX_LOOP_EDGES, VO_KFSTORE_MAX_LOOP_EDGES * 4, s->st, W));
+  VO_CHECK(stream_sync(s->st, W));
+  const int cnt = std::min(std::max(h[0], 0), VO_KFSTORE_MAX_LOOP_EDGES);
+  if (n) *n = cnt;
+  if (edges) memcpy(edges, h + 1, (size_t)cnt * 4);
+  return VO_OK;
+}
+
+int vo_kfstore_pose_graph_window(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
+                                 const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
+                                 const int32_t *cp_ref) {
+  const char *W = "vo_kfstore_pose_graph_window";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  if (n_corr < 0 || n_cp < 0 || !lc_start || (n_corr > 0 && (!corr_kf || !S_corr || !S_uncorr)) || (n_cp > 0 && (!cp_id || !cp_ref)))
+    return VO_ERR_INVALID;
+  if (lc_start[0] != 0 || lc_start[n_corr] < 0 || (lc_start[n_corr] > 0 && !lc_kf)) {
+    set_error("%s: the loop connections do not start at 0, or end at %d without a list", W, lc_start[n_corr]);
+    return VO_ERR_INVALID;
+  }
+  const int n_lc = lc_start[n_corr];
+  VO_CHECK(pg_check_counts(s, W, curr, match, n_corr, n_lc, n_cp));
+  for (int r = 0; r < n_corr; r++) {
+    if (corr_kf[r] < 0 || corr_kf[r] >= s->size || (r > 0 && corr_kf[r - 1] >= corr_kf[r])) {
+      set_error("%s: corrected key-frame %d (entry %d) outside [0, %d) or not in ascending order", W, corr_kf[r], r, s->size);
+      return VO_ERR_INVALID;
+    }
+    if (lc_start[r + 1] < lc_start[r] || lc_start[r + 1] > n_lc) {
+      set_error("%s: the loop connections of entry %d run from %d to %d of %d", W, r, lc_start[r], lc_start[r + 1], n_lc);
+      return VO_ERR_INVALID;
+    }
+    for (int e = lc_start[r]; e < lc_start[r + 1]; e++)
+      if (lc_kf[e] < 0 || lc_kf[e] >= s->size || (e > lc_start[r] && lc_kf[e - 1] >= lc_kf[e])) {
+        set_error("%s: loop connection %d of key-frame %d outside [0, %d) or not in ascending order", W, lc_kf[e], corr_kf[r], s->size);
+        return VO_ERR_INVALID;
+      }
+  }
+  for (int e = 0; e < n_cp; e++)
+    if (cp_id[e] < 0 || (e > 0 && cp_id[e - 1] >= cp_id[e]) || cp_ref[e] < 0 || cp_ref[e] >= s->size) {
+      set_error("%s: corrected point %d (entry %d) negative or not in ascending order, or its reference %d outside [0, %d)", W, cp_id[e], e,
+                cp_ref[e], s->size);
+      return VO_ERR_INVALID;
+    }
+  uint8_t *h = s->pg_win.stage.data();
+  const PgInputs H = pg_inputs(h, n_corr, n_lc, n_cp);
+  memcpy(H.S_corr, S_corr, (size_t)n_corr * 64), memcpy(H.S_unc, S_uncorr, (size_t)n_corr * 64);
+  memcpy(H.corr_kf, corr_kf, (size_t)n_corr * 4), memcpy(H.lc_start, lc_start, ((size_t)n_corr + 1) * 4);
+  memcpy(H.lc_kf, lc_kf, (size_t)n_lc * 4), memcpy(H.cp_id, cp_id, (size_t)n_cp * 4), memcpy(H.cp_ref, cp_ref, (size_t)n_cp * 4);
+  VO_CHECK(copy_h2d(s->P.in, h, H.bytes, s->st, W));  // the one copy
+  VO_CHECK(pg_enqueue_window(s, curr, match, n_corr, n_lc, n_cp));
+  return stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_pose_graph_window_dev(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr,
+                                     const double *dev_S_uncorr, const int32_t *dev_lc_start, int n_lc, const int32_t *dev_lc_kf, int n_cp,
+                                     const int32_t *dev_cp_id, const int32_t *dev_cp_ref) {
+  const char *W = "vo_kfstore_pose_graph_window_dev";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  if (!dev_lc_start || (n_corr > 0 && (!dev_corr_kf || !dev_S_corr || !dev_S_uncorr)) || (n_lc > 0 && !dev_lc_kf) ||
+      (n_cp > 0 && (!dev_cp_id || !dev_cp_ref)))
+    return VO_ERR_INVALID;
+  VO_CHECK(pg_check_counts(s, W, curr, match, n_corr, n_lc, n_cp));
+  const PgInputs I = pg_inputs(s->P.in, n_corr, n_lc, n_cp);
+  auto d2d = [&](void *dst, const void *src, size_t bytes) {
+    return bytes == 0 || hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, s->st) == hipSuccess;
+  };
+  if (!d2d(I.S_corr, dev_S_corr, (size_t)n_corr * 64) || !d2d(I.S_unc, dev_S_uncorr, (size_t)n_corr * 64) ||
+      !d2d(I.corr_kf, dev_corr_kf, (size_t)n_corr * 4) || !d2d(I.lc_start, dev_lc_start, ((size_t)n_corr + 1) * 4) ||
+      !d2d(I.lc_kf, dev_lc_kf, (size_t)n_lc * 4) || !d2d(I.cp_id, dev_cp_id, (size_t)n_cp * 4) || !d2d(I.cp_ref, dev_cp_ref, (size_t)n_cp * 4)) {
+    set_error("%s: hipMemcpyAsync failed", W);
+    return VO_ERR_HIP;
+  }
+  return pg_enqueue_window(s, curr, match, n_corr, n_lc, n_cp);
+}
+
+int vo_kfstore_pose_graph_window_result(vo_kfstore *s, int32_t *record, int32_t *node_kf, double *quats, double *trans, double *scales,
+                                        int32_t *edge_i, int32_t *edge_j, double *q_meas, double *t_meas, double *s_meas) {
+  const char *W = "vo_kfstore_pose_graph_window_result";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  const KfPgView &P = s->P;
+  const KfWindow &win = s->pg_win;
+  VO_CHECK(s->pg_win.fetch(P.win, P.win_bytes, false, s->st, W));
+  const int32_t *r = win.rec;
+  if (record) memcpy(record, r, sizeof(win.rec));
+  if (r[kPgStatus] != VO_KFSTORE_BA_WINDOW_OK) return VO_OK;
+  const size_t nn = (size_t)r[kPgNNodes], ne = (size_t)r[kPgNEdges];
+  if (node_kf) memcpy(node_kf, win.staged(P.node_kf, P.win), nn * 4);
+  if (quats) memcpy(quats, win.staged(P.quats, P.win), nn * 32);
+  if (trans) memcpy(trans, win.staged(P.trans, P.win), nn * 24);
+  if (scales) memcpy(scales, win.staged(P.scales, P.win), nn * 8);
+  if (edge_i) memcpy(edge_i, win.staged(P.e_i, P.win), ne * 4);
+  if (edge_j) memcpy(edge_j, win.staged(P.e_j, P.win), ne * 4);
+  if (q_meas) memcpy(q_meas, win.staged(P.q_meas, P.win), ne * 32);
+  if (t_meas) memcpy(t_meas, win.staged(P.t_meas, P.win), ne * 24);
+  if (s_meas) memcpy(s_meas, win.staged(P.s_meas, P.win), ne * 8);
+  return VO_OK;
+}
+
+int vo_kfstore_pose_graph_apply(vo_kfstore *s, const double *quats, const double *trans) {
+  const char *W = "vo_kfstore_pose_graph_apply";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  VO_CHECK(s->pg_win.check_apply(W, s->gen, s->P.win, s->st));
+  if (!quats || !trans) return VO_ERR_INVALID;
+  const size_t nn = (size_t)s->pg_win.rec[kPgNNodes];
+  uint8_t *h = s->pg_win.stage.data();
+  memcpy(h, quats, nn * 32), memcpy(h + nn * 32, trans, nn * 24);  // staged as k_pg_poses reads it: quats | trans
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));  // (rebuilt when stale: the refresh list is read off it)
+  VO_CHECK(copy_h2d(s->P.sol, h, nn * 56, s->st, W));
+  const PgInputs I = pg_inputs(s->P.in, s->pg_counts[0], s->pg_counts[1], s->pg_counts[2]);
+  const KfStoreView V = kfstore_view(s);
+  VO_CHECK(pg_apply_enqueue(V, O, s->X, s->M, s->B, s->P, I, (int)nn, s->st));
+  VO_CHECK(ba_refresh_list_enqueue(V, O, s->X, s->M, s->B, s->normals.as<double>(), connections_view(s->conn).status, s->size * s->NK,
+                                   s->P.rl, s->st));  // updateNormalAndDepth of every live point (:1299)
+  s->obs_dirty = true, s->gen++;
+  return stream_sync(s->st, W);  // (the staging block is free again)
+}
+
+int vo_kfstore_pose_graph(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr, const double *S_uncorr,
+                          const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id, const int32_t *cp_ref,
+                          int max_iterations, vo_lm_summary *summary) {
+  const char *W = "vo_kfstore_pose_graph";
+  VO_CHECK(need(s, W, kLayerPoseGraph));
+  VO_CHECK(vo_kfstore_pose_graph_window(s, curr, match, n_corr, corr_kf, S_corr, S_uncorr, lc_start, lc_kf, n_cp, cp_id, cp_ref));
+  const KfPgView &P = s->P;
+  const KfWindow &win = s->pg_win;
+  VO_CHECK(s->pg_win.fetch(P.win, P.win_bytes, false, s->st, W));  // the ONE device-to-host copy
+  const int32_t *r = win.rec;
+  if (r[kPgStatus] == VO_KFSTORE_BA_WINDOW_OVERFLOW) {
+    set_error("%s: %d nodes, %d edges; the solver takes %d nodes and the store was enabled for %d edges", W, r[kPgNNodes], r[kPgNEdges],
+              P.max_nodes, P.max_edges);
+    return VO_ERR_CAPACITY;
+  }
+  if (r[kPgStatus] != VO_KFSTORE_BA_WINDOW_OK) {
+    set_error("%s: the window is empty (curr or match erased, a key-frame without a pose, or lists only the device could refuse)", W);
+    return VO_ERR_INVALID;
+  }
+  const size_t nn = (size_t)r[kPgNNodes];
+  memcpy(s->pg_q.data(), win.staged(P.quats, P.win), nn * 32), memcpy(s->pg_t.data(), win.staged(P.trans, P.win), nn * 24);
+  // whatever the solver refuses is returned and nothing is written back (the shim's rule, optimizer_hip.inl:280-287)
+  VO_CHECK(vo_pose_graph_solve((int)nn, s->pg_q.data(), s->pg_t.data(), win.staged(P.scales, P.win), r[kPgFixed], r[kPgNEdges],
+                               win.staged(P.e_i, P.win), win.staged(P.e_j, P.win), win.staged(P.q_meas, P.win),
+                               win.staged(P.t_meas, P.win), win.staged(P.s_meas, P.win), 1, max_iterations, summary));
+  return vo_kfstore_pose_graph_apply(s, s->pg_q.data(), s->pg_t.data());
+}
+
+}  // extern "C"

@@ -16,7 +16,7 @@
 //
 // A frame that does not take part in a step has a negative count in that step's per-frame array: its workgroups return
 // at once.  All of a frame's walk state is one 8-int record (kRec*) that one workgroup per frame reads and rewrites.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include <algorithm>
 #include <cmath>

@@ -23,7 +23,7 @@
 // solves (two events order them).  Round 2 kept this sequence in Python (vo_slam_test_amd/tracking.py) without the
 // culling step and with the local-map projections fixed before the first solve; host code is now C++
 // throughout, as the reference's callers are.
-#include "vo_common.h"
+#include "kfstore.h"
 
 #include <cmath>
 #include <new>
