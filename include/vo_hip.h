@@ -1516,6 +1516,87 @@ int vo_kfstore_pose_graph_apply(vo_kfstore *s, const double *quats, const double
 int vo_kfstore_pose_graph(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
                           const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
                           const int32_t *cp_ref, int max_iterations, vo_lm_summary *summary);
+/* Key-frame creation on the device: a tracked frame written into the store as a key-frame --
+ * VisualOdometry::createNewKeyFrame (visualOdometry.cpp:463-517) with cullingTempMapPoints' slot rule (:844-853), and the first
+ * key-frame of initVisualOdometry (:170-198) -- for a caller who keeps no host copy of ids or flags: the link between "frame
+ * tracked" and vo_kfstore_process_new_keyframe.  Opt-in and additive: a store without it allocates and behaves as before.  The
+ * definitions are section 4i's (j HOLDS p, j's OBSERVATION of p, obs(p), bad(j)).
+ * enable_keyframe_create: valid on an EMPTY store on which vo_kfstore_enable_local_ba has succeeded (poses, xy, octave / depth /
+ * u_right, the id counter, normals, ref_kf and the observation index); anything else VO_ERR_INVALID.  One device block of
+ *   8 P + up16(8 NK) + 64 + 16 + 16 + 5 up16(4 NK) + up16(8 NK) + up16(96 + 7 up16(4 NK) + 32 NK)   bytes, NK = max_features,
+ *   P = the power of two >= NK, up16(x) = x rounded up to 16:
+ * the sort keys, the created rows, the record (16 ints), need_stats' counts, the effective count, the step's scratch (slot, first observation, new
+ * id, word, node per feature; weight) and the host forms' staging (Tcw12, seven columns, the descriptors).  Synchronises once.
+ * create_keyframe_dev(vocab, n, dev_Tcw12, dev_x, dev_y, dev_octave, dev_angle, dev_depth, dev_u_right, dev_desc, dev_slot_ids,
+ * th_depth, initial, index): validated on the host: 0 <= n <= max_features (itself <= 16384, the FeatureVector kernel's sort:
+ * vo_kfstore_enable_mapping refuses a wider store) and a free key-frame (else VO_ERR_CAPACITY), vocab and
+ * the arrays present, dev_desc on a 16-byte boundary (else VO_ERR_INVALID).  *index = the store's size before the call.
+ * Everything else is ENQUEUED on the store's stream -- the index rebuilt first when stale, then four launches (walk, fill,
+ * k_bow_transform, k_featvec): no host synchronisation, no device-to-host copy, no allocation; the arrays must stay untouched
+ * until the stream has passed the call.  dev_slot_ids[i] = frame_curr_->mappoints_[i] as a global map-point id, negative =
+ * null, as the slots stand when the reference calls createNewKeyFrame (before cullingOutliersOfFrame).  In the reference's order:
+ *  1 temp cull (:844-853): a slot whose id is negative, or whose id no non-erased key-frame holds (getObsCnt() < 1 decided by
+ *    holders, section 4l's rule), is NULL -- which makes `!mp || mp->getObsCnt() < 1` (:493) one condition.  The key-frame
+ *    being created is not among the holders.
+ *  2 depth walk (:469-513, initial == 0): the pairs (d, i) with d > 0 (float compare: NaN, -0 and -1 are out) ascending by d,
+ *    then i (sort on pair<float, int>, a total order).  c_j = 1 where pair j's slot is null, C_j its inclusive prefix sum, J the
+ *    first j with d_j > th_depth && C_j > 100, or the last pair.  The check follows the creation: the pair at which the count
+ *    reaches 101 is created when it is far, and a far TRACKED pair behind 101 creations ends the walk too.  Exactly the pairs
+ *    j <= J with c_j = 1 get a new point, id = counter + C_j - 1 (factory_id_++ in walk order); the counter advances by C_J.
+ *  3 initial == 1 (:179-198): every feature with !(d < 0), in feature order, gets a point; ids ascend with the feature index.
+ *    d == 0 and NaN are created (quirk Q-V1).  dev_slot_ids is ignored and may be NULL.
+ *  4 a created point (camera.cpp:82-94, mappoint.cpp:36-50, 52-64, 66-116, 118-179 with one observation):
+ *    x = ((u - cx) * d) / fx and likewise y in float, every operation rounded, widened to double; p_w = R^T (p_c - t) on Tcw12
+ *    in double (q = p_c + (-t), p_w[i] = (R[0][i] q[0] + R[1][i] q[1]) + R[2][i] q[2]; Sophus' quaternion rounding is not
+ *    reproduced).  flags = 3, ids = the new id, ref_kf = the new key-frame, point_desc = the feature's descriptor, normal and
+ *    min / max distance what vo_kfstore_refresh_points computes for one holder (a later refresh changes no byte).
+ *  5 a tracked slot (not null after 1, with or without depth): flags = 3, ids = the slot's id; points, point_desc, normal,
+ *    min / max distance and ref_kf are copied from the id's first observation: the lowest non-erased key-frame that holds it,
+ *    at that key-frame's observation.  vo_kfstore_process_new_keyframe refreshes them afterwards.
+ *  6 a null slot that gets no point: flags 0, id -1, ref_kf -1, zero columns.
+ *  7 angle, desc, octave / depth / u_right, xy and the pose with its pose-set word are copied; the FeatureVector is built by
+ *    k_bow_transform (levelsup 3) and k_featvec; bad = 0.  The observation index is stale afterwards and the generation word has
+ *    advanced.  Graph row and connections are vo_kfstore_process_new_keyframe's.
+ * create_keyframe: the same from host arrays; octave within the store's levels is validated too (VO_ERR_INVALID); one staging
+ * copy, one synchronisation at the end.  On an error nothing changes.
+ * create_keyframe_from_frames(vocab, frames, slot, n, dev_Tcw12, dev_slot_ids, th_depth, initial, index): the feature columns
+ * are those of `slot` of a vo_frames handle (the one vo_tracker_frames returns: an extracted frame never leaves the device);
+ * slot and n <= the frames' capacity are validated too.  n is the caller's (VO_TRACKER_KEYPOINT_COUNTS, vo_frames_download): if
+ * it differs from the slot's count on the device the key-frame gets n = 0 features in its head, the n rows the getters span
+ * are written as null slots without a feature (zeros; id, ref_kf, depth, u_right -1), the record's status is 1 and the sticky
+ * VO_KFSTORE_CONNECTIONS_INVALID is raised.  The store's stream waits, by an event, for what the
+ * stream that last wrote the frames (vo_frames_build_dev, vo_frames_upload) holds at the call; ENQUEUED like the device form.
+ * keyframe_result(record, created_feature, created_id): synchronises; any pointer may be NULL.  record [16] = key-frame, n,
+ * depth pairs, pairs walked (J + 1), n_created, n_tracked, first id, next id, whether the walk ended early, status (0, or 1:
+ * the frames form's n was not the slot's), six zeros (initial: the "pairs" are the features with !(d < 0)).  created_feature / created_id [n_created] in walk order.
+ * keyframe_need_stats_dev(ref_kf, min_obs, n, dev_depth, dev_slot_ids, th_depth, dev_out): the three counts of needNewKeyFrame
+ * (:406-428), nothing of its decision.  ENQUEUED: one launch behind the index rebuild.  out[0] =
+ * keyframe_trackRef_->trackedMapPoints(min_obs) (keyframe.cpp:210-226): features of ref_kf with bit 0 whose obs(p) >= min_obs;
+ * out[1] = map_cnt, out[2] = total_cnt over the frame's features with 0 < d < th_depth (a slot counts when some non-erased
+ * key-frame holds its id); out[3] = 0.  ref_kf erased or outside the store: zeros and the sticky
+ * VO_KFSTORE_CONNECTIONS_INVALID.  keyframe_need_stats: host arrays in (n <= max_features), out [4] on the host; one copy up, one
+ * down, one synchronisation. */
+int vo_kfstore_enable_keyframe_create(vo_kfstore *s);
+int vo_kfstore_create_keyframe_dev(vo_kfstore *s, const vo_vocab *vocab, int n, const double *dev_Tcw12, const float *dev_x,
+                                   const float *dev_y, const int32_t *dev_octave, const float *dev_angle, const float *dev_depth,
+                                   const float *dev_u_right, const uint8_t *dev_desc, const int32_t *dev_slot_ids, float th_depth,
+                                   int initial, int32_t *index);
+int vo_kfstore_create_keyframe(vo_kfstore *s, const vo_vocab *vocab, int n, const double *Tcw12, const float *x, const float *y,
+                               const int32_t *octave, const float *angle, const float *depth, const float *u_right, const uint8_t *desc,
+                               const int32_t *slot_ids, float th_depth, int initial, int32_t *index);
+int vo_kfstore_create_keyframe_from_frames(vo_kfstore *s, const vo_vocab *vocab, vo_frames *frames, int slot, int n,
+                                           const double *dev_Tcw12, const int32_t *dev_slot_ids, float th_depth, int initial,
+                                           int32_t *index);
+/* The feature side of a key-frame as the store holds it (read-only, beside vo_kfstore_get_points; needs vo_kfstore_enable_mapping):
+ * angle, desc [n][32], octave, depth, u_right, xy [n][2] (n as inserted) and the FeatureVector -- n_nodes, node [n_nodes], start
+ * [n_nodes + 1], feat [start[n_nodes]], in arrays of n (start: n + 1) entries.  Any pointer may be NULL.  Synchronises. */
+int vo_kfstore_get_features(vo_kfstore *s, int keyframe, float *angle, uint8_t *desc, int32_t *octave, float *depth, float *u_right,
+                            float *xy, int32_t *n_nodes, int32_t *node, int32_t *start, int32_t *feat);
+int vo_kfstore_keyframe_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *created_feature, int32_t *created_id);
+int vo_kfstore_keyframe_need_stats_dev(vo_kfstore *s, int ref_kf, int min_obs, int n, const float *dev_depth,
+                                       const int32_t *dev_slot_ids, float th_depth, int32_t *dev_out /*[4]*/);
+int vo_kfstore_keyframe_need_stats(vo_kfstore *s, int ref_kf, int min_obs, int n, const float *depth, const int32_t *slot_ids,
+                                   float th_depth, int32_t *out /*[4]*/);
 /* vo_tracker_relocalize with the candidates read from a store: dev_cand [batch][cand_stride] key-frame numbers in walk
  * order and dev_n_cand [batch] in device memory -- the output layout of vo_kfdb_query_reloc_dev.  The first
  * min(n_cand[f], max_reloc_candidates) of a frame are walked.  Frame construction, computeBow, the frames' FeatureVectors

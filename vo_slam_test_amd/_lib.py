@@ -73,6 +73,9 @@ SYMBOLS = [
     "vo_kfstore_loop_result", "vo_kfstore_loop_solver_inputs", "vo_kfstore_loop_ransac_max_iters",
     "vo_kfstore_enable_pose_graph", "vo_kfstore_add_loop_edge", "vo_kfstore_get_loop_edges", "vo_kfstore_pose_graph_window",
     "vo_kfstore_pose_graph_window_dev", "vo_kfstore_pose_graph_window_result", "vo_kfstore_pose_graph_apply", "vo_kfstore_pose_graph",
+    "vo_kfstore_enable_keyframe_create", "vo_kfstore_create_keyframe", "vo_kfstore_create_keyframe_dev",
+    "vo_kfstore_create_keyframe_from_frames", "vo_kfstore_keyframe_result", "vo_kfstore_get_features",
+    "vo_kfstore_keyframe_need_stats", "vo_kfstore_keyframe_need_stats_dev",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -2086,6 +2089,100 @@ class KeyFrameStore:
         check(lib().vo_kfstore_pose_graph(self._h, int(curr), int(match), len(ck), _p(ck), _p(sc), _p(su), _p(ls), _p(lk), len(ci), _p(ci),
                                           _p(cr), int(max_iterations), C.byref(s)), "vo_kfstore_pose_graph")
         return s
+
+    KC_RECORD = ("keyframe", "n", "n_pairs", "n_walked", "n_created", "n_tracked", "first_id", "next_id", "ended_early", "status")
+    _KC_COLUMNS = (("x", "float32"), ("y", "float32"), ("octave", "int32"), ("angle", "float32"), ("depth", "float32"), ("u_right", "float32"))
+
+    def enable_keyframe_create(self):
+        """createNewKeyFrame / the first key-frame of initVisualOdometry on the device from now on; valid on
+        an empty store after enable_local_ba only"""
+        check(lib().vo_kfstore_enable_keyframe_create(self._h), "vo_kfstore_enable_keyframe_create")
+
+    def create_keyframe(self, vocab, f, th_depth, initial=False):
+        """a tracked frame written into the store as a key-frame -> its number.  f: dict(Tcw12 f64 [12], x, y, angle, depth, u_right
+        f32 [n], octave i32 [n], desc u8 [n, 32], slot_ids i32 [n]: the frame's map-point slots as global ids, negative = null;
+        ignored and optional with initial).  numpy arrays are validated, copied once and synchronise once; device tensors (all of
+        them) are enqueued only and must stay untouched until the store's stream has passed the call"""
+        idx = C.c_int32(-1)
+        if hasattr(f["Tcw12"], "data_ptr"):
+            n = int(f["depth"].numel())
+            _need_tensor(f["Tcw12"], "float64", 12, "create_keyframe")
+            for k, dt in self._KC_COLUMNS:
+                _need_tensor(f[k], dt, n, "create_keyframe")
+            _need_tensor(f["desc"], "uint8", n * 32, "create_keyframe")
+            slot = None if initial else f["slot_ids"]
+            if slot is not None:
+                _need_tensor(slot, "int32", n, "create_keyframe")
+            check(lib().vo_kfstore_create_keyframe_dev(self._h, vocab._h, n, _p(f["Tcw12"]), _p(f["x"]), _p(f["y"]), _p(f["octave"]), _p(f["angle"]),
+                                                       _p(f["depth"]), _p(f["u_right"]), _p(f["desc"]), _p(slot), C.c_float(th_depth),
+                                                       int(bool(initial)), C.byref(idx)), "vo_kfstore_create_keyframe_dev")
+            return int(idx.value)
+        T = np.ascontiguousarray(f["Tcw12"], np.float64).reshape(12)
+        a = {k: np.ascontiguousarray(f[k], dt).reshape(-1) for k, dt in self._KC_COLUMNS}
+        n = len(a["depth"])
+        desc = np.ascontiguousarray(f["desc"], np.uint8).reshape(n, 32)
+        slot = None if initial else np.ascontiguousarray(f["slot_ids"], np.int32).reshape(-1)
+        if any(len(v) != n for v in a.values()) or (slot is not None and len(slot) != n):
+            raise VoError("vo_kfstore_create_keyframe failed with status -1: the frame's arrays differ in length")
+        check(lib().vo_kfstore_create_keyframe(self._h, vocab._h, n, _p(T), _p(a["x"]), _p(a["y"]), _p(a["octave"]), _p(a["angle"]), _p(a["depth"]),
+                                               _p(a["u_right"]), _p(desc), _p(slot), C.c_float(th_depth), int(bool(initial)), C.byref(idx)),
+              "vo_kfstore_create_keyframe")
+        return int(idx.value)
+
+    def create_keyframe_from_frames(self, vocab, frames, slot, n, Tcw12, slot_ids, th_depth, initial=False):
+        """create_keyframe with the feature columns of `slot` of a Frames handle (Tracker.frames_handle() wrapped, or one of the
+        caller's); n: the slot's feature count as the caller knows it; Tcw12 (f64 [12]) and slot_ids (i32 [n]) device tensors.
+        Enqueued only; a wrong n shows as status 1 in keyframe_result() and raises the sticky CONNECTIONS_INVALID"""
+        _need_tensor(Tcw12, "float64", 12, "create_keyframe_from_frames")
+        if not initial:
+            _need_tensor(slot_ids, "int32", int(n), "create_keyframe_from_frames")
+        idx = C.c_int32(-1)
+        h = frames._h if hasattr(frames, "_h") else C.c_void_p(frames)
+        check(lib().vo_kfstore_create_keyframe_from_frames(self._h, vocab._h, h, int(slot), int(n), _p(Tcw12), _p(None if initial else slot_ids),
+                                                           C.c_float(th_depth), int(bool(initial)), C.byref(idx)),
+              "vo_kfstore_create_keyframe_from_frames")
+        return int(idx.value)
+
+    def features(self, keyframe, n):
+        """the feature side of a key-frame as the store holds it (n as inserted) -> dict(angle, desc, octave, depth, u_right, xy of
+        numpy arrays and feature_vector: [(node, [features])] in ascending node)"""
+        n = int(n)
+        out = dict(angle=np.zeros(n, np.float32), desc=np.zeros((n, 32), np.uint8), octave=np.zeros(n, np.int32), depth=np.zeros(n, np.float32),
+                   u_right=np.zeros(n, np.float32), xy=np.zeros((n, 2), np.float32))
+        nn, node, start, feat = C.c_int32(0), np.zeros(n, np.int32), np.zeros(n + 1, np.int32), np.zeros(n, np.int32)
+        check(lib().vo_kfstore_get_features(self._h, int(keyframe), *(_p(v) for v in out.values()), C.byref(nn), _p(node), _p(start), _p(feat)),
+              "vo_kfstore_get_features")
+        k = min(max(int(nn.value), 0), n)
+        out["feature_vector"] = [(int(node[j]), [int(x) for x in feat[start[j]:start[j + 1]]]) for j in range(k)]
+        return out
+
+    def keyframe_result(self):
+        """the last create_keyframe -> dict over KC_RECORD plus created [(feature, id)] in walk order; synchronises"""
+        rec = np.zeros(16, np.int32)
+        feat, ids = np.zeros(self.max_features, np.int32), np.zeros(self.max_features, np.int32)
+        check(lib().vo_kfstore_keyframe_result(self._h, _p(rec), _p(feat), _p(ids)), "vo_kfstore_keyframe_result")
+        out = {k: int(rec[i]) for i, k in enumerate(self.KC_RECORD)}
+        out["created"] = [(int(feat[i]), int(ids[i])) for i in range(out["n_created"])]
+        return out
+
+    def keyframe_need_stats(self, ref_kf, min_obs, depth, slot_ids, th_depth, out=None):
+        """the three counts of needNewKeyFrame -> (trackedMapPoints(min_obs) of ref_kf, map_cnt, total_cnt).  numpy arrays: copied,
+        synchronises once; device tensors (depth f32, slot_ids i32, out i32 [4]): enqueued only, the counts land in out"""
+        if hasattr(depth, "data_ptr"):
+            n = int(depth.numel())
+            _need_tensor(depth, "float32", n, "keyframe_need_stats")
+            _need_tensor(slot_ids, "int32", n, "keyframe_need_stats")
+            _need_tensor(out, "int32", 4, "keyframe_need_stats")
+            check(lib().vo_kfstore_keyframe_need_stats_dev(self._h, int(ref_kf), int(min_obs), n, _p(depth), _p(slot_ids), C.c_float(th_depth),
+                                                           _p(out)), "vo_kfstore_keyframe_need_stats_dev")
+            return None
+        d, s = np.ascontiguousarray(depth, np.float32).reshape(-1), np.ascontiguousarray(slot_ids, np.int32).reshape(-1)
+        if len(d) != len(s):
+            raise VoError("vo_kfstore_keyframe_need_stats failed with status -1: depth and slot_ids differ in length")
+        o = np.zeros(4, np.int32)
+        check(lib().vo_kfstore_keyframe_need_stats(self._h, int(ref_kf), int(min_obs), len(d), _p(d), _p(s), C.c_float(th_depth), _p(o)),
+              "vo_kfstore_keyframe_need_stats")
+        return int(o[0]), int(o[1]), int(o[2])
 
 
 def rgb_to_gray(img, first_is_red=True):

@@ -902,6 +902,7 @@ struct vo_frames {
   vo::OwnedDevBuf b_pool, b_rank, b_ovf, b_ovfr, b_qrec, b_used, b_best, b_asg, b_push, b_nm, b_err, b_sf;
   size_t pool_stride = 0, replay_lds_attr = 0;
   float sf_host[16] = {0};  // scale factors last uploaded for vo_track_gather_dev
+  hipStream_t producer = nullptr;  // the stream the slots were last written on (vo_frames_build_dev, vo_frames_upload)
 };
 
 namespace {
@@ -1070,6 +1071,7 @@ int vo_frames_build_dev(vo_frames *h, int slot0, int n_frames, const vo_keypoint
     return VO_ERR_INVALID;
   }
   hipStream_t st = (hipStream_t)hip_stream;
+  h->producer = st;
   const int nmax = std::min(capacity, h->cap);
   if (!h->b_err.p) {  // the handle's sticky flag (read and cleared by vo_match_guided_status)
     VO_CHECK(h->b_err.reserve(64));
@@ -1092,9 +1094,10 @@ int vo_frames_upload(vo_frames *h, int slot, const vo_frame_view *view, const fl
   hipStream_t st = (hipStream_t)hip_stream;
   const int n = view->n;
   const size_t o = (size_t)slot * h->cap;
+  if (n > 0 && (!view->x || !view->y || !view->octave || !view->desc)) return VO_ERR_INVALID;
+  h->producer = st;  // (every refusal lies above: from here on the slot is written on st)
   frames_set_bounds(h, view->xmin, view->ymin, view->xmax, view->ymax);
   if (n > 0) {
-    if (!view->x || !view->y || !view->octave || !view->desc) return VO_ERR_INVALID;
     VO_CHECK(vo::copy_h2d(h->D.x + o, view->x, (size_t)n * 4, st, "vo_frames_upload"));
     VO_CHECK(vo::copy_h2d(h->D.y + o, view->y, (size_t)n * 4, st, "vo_frames_upload"));
     VO_CHECK(vo::copy_h2d(h->D.octave + o, view->octave, (size_t)n * 4, st, "vo_frames_upload"));
@@ -1488,5 +1491,7 @@ int vo_match_sim3_mutual(const vo_frame_view *kf1, const vo_frame_view *kf2, con
 vo::FrameStoreView vo::frame_store_view(const vo_frames *h) {
   return vo::FrameStoreView{h->cap, h->D.desc, h->D.angle, h->D.n, h->D.x, h->D.y, h->D.uright, h->D.octave};
 }
+
+vo::FrameStoreSource vo::frame_store_source(const vo_frames *h) { return vo::FrameStoreSource{h->D.depth, h->max_frames, h->producer}; }
 
 const int *vo::guided_error_flag(const vo_frames *h) { return h ? h->b_err.as<int>() : nullptr; }

@@ -1,4 +1,4 @@
-// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4o; not part of the C-ABI): the
+// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4p; not part of the C-ABI): the
 // kernel-argument views of the store and of its opt-in layers, the functions a layer's file shares with another file, the
 // handle itself, and the guards every entry point starts with.  Included by kfstore.hip, by the layer files and by the
 // store's readers (match.hip, reloc.hip, tracker.hip, local_map.hip).
@@ -294,6 +294,44 @@ struct PgInputs {
   size_t bytes;
 };
 
+// Key-frame creation on the device (keyframe_create.hip): VisualOdometry::createNewKeyFrame
+// (visualOdometry.cpp:463-517) and the first key-frame of initVisualOdometry (:170-198) written into the store.  What
+// vo_kfstore_enable_keyframe_create allocates, one block (P = pow2_ceil(NK)): keys [P], the depth walk's sort keys when they
+// do not fit in LDS; created [NK] rows (feature, id) in walk order; rec [kKcRecInts]; stats [4], need_stats' counts of the host
+// form; n_eff, the count the fill and k_featvec run with (n, or 0 when the frames form's n is not the slot's); and the step's
+// scratch: slot [NK] (the slot's id after the temp cull, -1: null), first [NK] (the entry of that id's first observation),
+// newid [NK] (the id of the point created at the feature, -1: none), word / node [NK] and weight [NK], k_bow_transform's
+// outputs; `in`, the host forms' inputs as their one staging copy brings them: Tcw12 | x | y | octave | angle | depth |
+// u_right | slot ids [NK] each | desc [NK][32].
+constexpr int kKcRecInts = 16, kKcLdsKeys = 4096;
+enum { kKcKeyframe = 0, kKcN, kKcNPairs, kKcNWalked, kKcNCreated, kKcNTracked, kKcFirstId, kKcNextId, kKcEarly, kKcStatus };
+struct KfCreateView {
+  int NK, P;
+  unsigned long long *keys;
+  int2 *created;
+  int *rec, *stats, *n_eff, *slot, *first, *newid, *word, *node;
+  double *weight;
+  uint8_t *in;
+  size_t in_bytes;
+};
+// where the columns of a host form lie inside `in` (or a staging block laid out like it)
+struct KcInputs {
+  double *T;
+  float *x, *y, *angle, *depth, *u_right;
+  int *octave, *slot;
+  uint8_t *desc;
+};
+__host__ __device__ __forceinline__ KcInputs kc_inputs(uint8_t *in, int NK) {
+  const size_t col = ((size_t)NK * 4 + 15) & ~(size_t)15;
+  KcInputs I;
+  I.T = reinterpret_cast<double *>(in);
+  uint8_t *p = in + 96;
+  I.x = reinterpret_cast<float *>(p), I.y = reinterpret_cast<float *>(p + col), I.octave = reinterpret_cast<int *>(p + 2 * col);
+  I.angle = reinterpret_cast<float *>(p + 3 * col), I.depth = reinterpret_cast<float *>(p + 4 * col);
+  I.u_right = reinterpret_cast<float *>(p + 5 * col), I.slot = reinterpret_cast<int *>(p + 6 * col), I.desc = p + 7 * col;
+  return I;
+}
+
 // pair p = f * per + c searches key-frame dev_pair_kf[p] of the store (a number outside [0, size): no key-frame, the pair
 // matches nothing); per <= the buffers' `per`.  search_bad: a key-frame flagged bad is searched like any other
 // (trackRefKeyFrame) instead of matching nothing (relocalisation).
@@ -333,6 +371,7 @@ enum KfLayer : unsigned {
   kLayerFuse = 1u << 5,
   kLayerLoop = 1u << 6,
   kLayerPoseGraph = 1u << 7,
+  kLayerKeyframeCreate = 1u << 8,
 };
 
 // The window protocol local BA and the pose graph share: a *_window call enqueues the window and notes the store's
@@ -400,6 +439,9 @@ struct vo_kfstore {
   int pg_counts[3] = {0, 0, 0};       // n_corr, n_lc, n_cp of the last window: where its inputs lie in P.in
   std::vector<int32_t> pg_ledge;      // the loop edges as the host knows them: [max_kf][1 + VO_KFSTORE_MAX_LOOP_EDGES], count first
   std::vector<double> pg_q, pg_t;     // the composed call's solver state (sized by the capacities: no allocation per call)
+  vo::OwnedDevBuf kc;                 // vo_kfstore_enable_keyframe_create: the block of section 4p
+  vo::OwnedPinnedBuf kc_stage;        // a host form's inputs going up: one copy
+  vo::KfCreateView K{};
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 

@@ -1494,10 +1494,10 @@ int vo::bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int le
 }
 
 int vo::featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int *dev_node, int *dev_start, int *dev_feat,
-                    hipStream_t st) {
+                    hipStream_t st, const int *dev_n) {
   if (n < 0 || n > kNodeMaxB || !dev_n_nodes || !dev_start || (n > 0 && (!dev_node_of_feature || !dev_node || !dev_feat)))
     return VO_ERR_INVALID;
-  FeatVecArgs A{nullptr, n, n, dev_node_of_feature, dev_n_nodes, 0, dev_node, dev_start, dev_feat};
+  FeatVecArgs A{dev_n, n, n, dev_node_of_feature, dev_n_nodes, 0, dev_node, dev_start, dev_feat};
   return launch_featvec(A, 1, st);
 }
 

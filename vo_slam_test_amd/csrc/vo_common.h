@@ -229,6 +229,14 @@ struct FrameStoreView {
   const int *octave = nullptr;
 };
 FrameStoreView frame_store_view(const vo_frames *h);
+// what vo_kfstore_create_keyframe_from_frames reads beyond the view (guided.hip): the depth column [slots][cap], the number of
+// slots, and the stream the slots were last written on (vo_frames_build_dev, vo_frames_upload)
+struct FrameStoreSource {
+  const float *depth;
+  int slots;
+  hipStream_t producer;
+};
+FrameStoreSource frame_store_source(const vo_frames *h);
 
 // The relocalisation route of the tracker (reloc.hip): VisualOdometry::relocalization() (visualOdometry.cpp:313-395) for
 // the frames resident in the tracker's frame store.  The tracker owns the per-feature frame state and the pose solver's
@@ -303,9 +311,10 @@ int bow_walk_reserve(BowWalkBufs &b, int B, int cap, int per, int NK, hipStream_
 int bow_featvec_resident(const vo_vocab *v, vo_frames *frames, int B, int levelsup, BowWalkBufs &b, hipStream_t st,
                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);  // (events around k_featvec)
 // the FeatureVector of n features from their node ids (device arrays): n_nodes into *dev_n_nodes, node [n] ascending,
-// start [n + 1], feat [n] (the features of a node in index order); n <= 16384
+// start [n + 1], feat [n] (the features of a node in index order); n <= 16384.  dev_n: NULL, or a device count that replaces n
+// (clamped to [0, n]: the arrays are sized by n)
 int featvec_dev(int n, const int *dev_node_of_feature, int *dev_n_nodes, int *dev_node, int *dev_start, int *dev_feat,
-                hipStream_t st);
+                hipStream_t st, const int *dev_n = nullptr);
 
 // The store routes of the tracker (reloc.hip): reloc_run with the candidates read from a store, optionally chosen by
 // the database.  reloc_store_prepare sizes the route's own buffers (first call) before anything is enqueued.
