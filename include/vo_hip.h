@@ -1516,6 +1516,56 @@ int vo_kfstore_pose_graph_apply(vo_kfstore *s, const double *quats, const double
 int vo_kfstore_pose_graph(vo_kfstore *s, int curr, int match, int n_corr, const int32_t *corr_kf, const double *S_corr,
                           const double *S_uncorr, const int32_t *lc_start, const int32_t *lc_kf, int n_cp, const int32_t *cp_id,
                           const int32_t *cp_ref, int max_iterations, vo_lm_summary *summary);
+/* The loop fusion on the device: LoopClosing::searchAndFuse (loopClosing.cpp:496-516) with
+ * Matcher::fuseByPose (matcher.cpp:1135-1238) and MapPoint::replaceMapPoint (mappoint.cpp:214-253) on the store, the step of
+ * correctLoop between its pose propagation and the pose graph.  Opt-in and additive: a store without it allocates and behaves
+ * as before.  The definitions, a map point's "isBad", beObserved and ATTRIBUTES, and replace(A -> B) with its carrier limit are
+ * the fusion block's above; corr_kf and S_corr are the arrays vo_kfstore_pose_graph_window[_dev] takes, so one upload serves both.
+ * enable_loop_fuse(max_corrected, max_loop_points): valid on an EMPTY store on which vo_kfstore_enable_fuse has succeeded,
+ * capacities >= 1, else VO_ERR_INVALID.  One device block of 16 + up16(4 (C + 1)) + 32 C + 64 C + up16(4 C) + up16(4 P) bytes
+ * (C = max_corrected, P = max_loop_points): the call's head, per pass its first match and its record, and the host form's
+ * arrays.  It works on the fusion layer's overlay and match list: enable_fuse's max_candidates bounds the candidates that pass
+ * the gates in ONE pass and the matches of one CALL.  Synchronises once.
+ * search_and_fuse(n_corr, corr_kf, S_corr, n_points, ids, threshold): n_corr passes, T = corr_kf[0], corr_kf[1], ... (strictly
+ * ascending: correctPose is walked in ascending key-frame number), each fuseByPose(T, S_corr[T], ids, replace, threshold) and
+ * then replace[i] -> replaceMapPoint(ids[i]) in list order.  S_corr: 8 doubles per key-frame, quaternion x y z w (normalised
+ * when read), translation, scale.  ids: loopConnectKFMapPoints_ in list order, distinct (a negative entry is skipped).
+ *  1. Tcw = SE3(R(q), t), t NOT divided by the scale (matcher.cpp:1144), Ow = -(R^T t); doubles, each operation rounded.
+ *  2. Candidate i is skipped unless: id >= 0; somebody holds it (a loop point replaced in an earlier pass is bad); T does not;
+ *     z >= 0 (float); isInImg(u, v); 0.8f * min <= dist <= 1.2f * max; line . normal >= 0.5 * dist (double); level =
+ *     predictScale.  These are the fusion block's gates with the Sim3's pose in place of T's pose column.
+ *  3. The window is the fusion block's with radius = threshold * scale_factors[level]; of its features with octave in
+ *     [level - 1, level] -- there is NO chi-square gate and no u_right -- the strictly smallest Hamming distance between the
+ *     candidate's point_desc and the feature's desc wins in the order cell column, cell row, feature; a match needs <= 50.
+ *  4. Feature EMPTY (bit 0 clear): it takes the candidate's id, bit 0 and attributes at once; a later candidate of the pass
+ *     that hits it finds that loop point there.  Feature carries org: replace[i] = org, nothing is written yet.
+ *  5. After the list, in list order: replace(replace[i] -> ids[i]), always org -> loop point.  An org a former replace of the
+ *     pass has emptied is NOT skipped: no carrier moves, the counters are added once more when both are in the recent list,
+ *     compute_descriptors(ids[i]) runs.  A == B by id does nothing.
+ *  6. Afterwards the index is stale and the generation word has advanced.  Connections are NOT updated (correctLoop calls
+ *     vo_kfstore_update_connections itself, :469).  A T outside [0, size), erased or without a pose column gives a pass that
+ *     changes nothing and raises VO_KFSTORE_CONNECTIONS_INVALID.
+ *  7. Capacity, three limits on the device, each raising VO_KFSTORE_FUSE_CAPACITY: more than max_candidates candidates passing in
+ *     one pass leave that pass undone; matches of the call beyond max_candidates leave that pass and every later one undone;
+ *     a replace between points of which one has more than VO_KFSTORE_FUSE_MAX_CARRIERS live features is left undone.
+ * The host form validates: n_corr > max_corrected or n_points > max_loop_points is VO_ERR_CAPACITY; corr_kf not strictly
+ * ascending, threshold <= 0, a negative count or a NULL array with a positive count VO_ERR_INVALID, nothing changed; ONE copy
+ * up, the call enqueued, one synchronisation.  search_and_fuse_dev: the same arrays in device memory, read in place; counts
+ * and NULLs validated as above, everything else on the device; ENQUEUED only: the index rebuilt first when stale, three
+ * memsets, 1 + 2 n_corr launches (1 when n_points is 0), no host synchronisation, no copy, no allocation.
+ * search_and_fuse_loop: the loop points are the list the last vo_kfstore_compute_sim3 left on the device, read in place; needs
+ * vo_kfstore_enable_loop (else VO_ERR_INVALID); ENQUEUED only, the same launches.  A last call whose state is not
+ * VO_KFSTORE_LOOP_ACCEPTED is decided on the device: nothing changes, the record has 0 passes, VO_KFSTORE_CONNECTIONS_INVALID.
+ * loop_fuse_result(record, per_pass): synchronises; either pointer may be NULL.  record [8] = passes run, then the totals of
+ * the six columns, 0; per_pass [max_corrected][6] = candidates that passed the gates, matches, adds, replaces recorded,
+ * replaces that moved at least one carrier, features cleared (rows beyond the passes are 0). */
+int vo_kfstore_enable_loop_fuse(vo_kfstore *s, int max_corrected, int max_loop_points);
+int vo_kfstore_search_and_fuse(vo_kfstore *s, int n_corr, const int32_t *corr_kf, const double *S_corr /*[n_corr][8]*/, int n_points,
+                               const int32_t *ids, float threshold);
+int vo_kfstore_search_and_fuse_dev(vo_kfstore *s, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr, int n_points,
+                                   const int32_t *dev_ids, float threshold);
+int vo_kfstore_search_and_fuse_loop(vo_kfstore *s, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr, float threshold);
+int vo_kfstore_loop_fuse_result(vo_kfstore *s, int32_t *record /*[8]*/, int32_t *per_pass /*[max_corrected][6]*/);
 /* Key-frame creation on the device: a tracked frame written into the store as a key-frame --
  * VisualOdometry::createNewKeyFrame (visualOdometry.cpp:463-517) with cullingTempMapPoints' slot rule (:844-853), and the first
  * key-frame of initVisualOdometry (:170-198) -- for a caller who keeps no host copy of ids or flags: the link between "frame

@@ -76,6 +76,8 @@ SYMBOLS = [
     "vo_kfstore_enable_keyframe_create", "vo_kfstore_create_keyframe", "vo_kfstore_create_keyframe_dev",
     "vo_kfstore_create_keyframe_from_frames", "vo_kfstore_keyframe_result", "vo_kfstore_get_features",
     "vo_kfstore_keyframe_need_stats", "vo_kfstore_keyframe_need_stats_dev",
+    "vo_kfstore_enable_loop_fuse", "vo_kfstore_search_and_fuse", "vo_kfstore_search_and_fuse_dev", "vo_kfstore_search_and_fuse_loop",
+    "vo_kfstore_loop_fuse_result",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -2089,6 +2091,45 @@ class KeyFrameStore:
         check(lib().vo_kfstore_pose_graph(self._h, int(curr), int(match), len(ck), _p(ck), _p(sc), _p(su), _p(ls), _p(lk), len(ci), _p(ci),
                                           _p(cr), int(max_iterations), C.byref(s)), "vo_kfstore_pose_graph")
         return s
+
+    LOOP_FUSE_COLUMNS = ("passed", "matches", "adds", "replaces", "moved", "cleared")
+
+    def enable_loop_fuse(self, max_corrected, max_loop_points):
+        """LoopClosing::searchAndFuse on the device from now on (DESIGN.md section 4q); valid on an empty store after enable_fuse
+        only.  max_corrected: the corrected key-frames (passes) of a call; max_loop_points: the loop points of a call"""
+        check(lib().vo_kfstore_enable_loop_fuse(self._h, int(max_corrected), int(max_loop_points)), "vo_kfstore_enable_loop_fuse")
+        self._lf_corrected = int(max_corrected)
+
+    def search_and_fuse(self, corr_kf, S_corr, ids=None, threshold=4.0):
+        """searchAndFuse(correctPose) over the loop points `ids`: corr_kf ascending, S_corr [n, 8] (quaternion x y z w,
+        translation, scale) as pose_graph_window takes them.  numpy arrays / lists are validated, copied once and the call
+        synchronises once; device tensors (all three) are enqueued only.  ids = None (corr_kf and S_corr device tensors): the
+        loop points the last compute_sim3 left on the device, enqueued only"""
+        th = C.c_float(threshold)
+        if hasattr(corr_kf, "data_ptr"):
+            _need_tensor(corr_kf, "int32", None, "search_and_fuse")
+            _need_tensor(S_corr, "float64", int(corr_kf.numel()) * 8, "search_and_fuse")
+            if ids is None:
+                check(lib().vo_kfstore_search_and_fuse_loop(self._h, int(corr_kf.numel()), _p(corr_kf), _p(S_corr), th),
+                      "vo_kfstore_search_and_fuse_loop")
+                return
+            _need_tensor(ids, "int32", None, "search_and_fuse")
+            check(lib().vo_kfstore_search_and_fuse_dev(self._h, int(corr_kf.numel()), _p(corr_kf), _p(S_corr), int(ids.numel()), _p(ids), th),
+                  "vo_kfstore_search_and_fuse_dev")
+            return
+        ck, sc = np.ascontiguousarray(corr_kf, np.int32).reshape(-1), np.ascontiguousarray(S_corr, np.float64).reshape(-1, 8)
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        if len(sc) != len(ck):
+            raise VoError("vo_kfstore_search_and_fuse failed with status -1: corr_kf and S_corr differ in length")
+        check(lib().vo_kfstore_search_and_fuse(self._h, len(ck), _p(ck), _p(sc), len(a), _p(a), th), "vo_kfstore_search_and_fuse")
+
+    def loop_fuse_result(self):
+        """the last search_and_fuse -> dict(passes, per_pass [(passed, matches, adds, replaces, moved, cleared)], totals);
+        synchronises"""
+        rec, per = np.zeros(8, np.int32), np.zeros((getattr(self, "_lf_corrected", 1), 6), np.int32)
+        check(lib().vo_kfstore_loop_fuse_result(self._h, _p(rec), _p(per)), "vo_kfstore_loop_fuse_result")
+        n = int(rec[0])
+        return dict(passes=n, per_pass=[tuple(int(x) for x in row) for row in per[:n]], totals=tuple(int(x) for x in rec[1:7]))
 
     KC_RECORD = ("keyframe", "n", "n_pairs", "n_walked", "n_created", "n_tracked", "first_id", "next_id", "ended_early", "status")
     _KC_COLUMNS = (("x", "float32"), ("y", "float32"), ("octave", "int32"), ("angle", "float32"), ("depth", "float32"), ("u_right", "float32"))

@@ -1,4 +1,4 @@
-// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4p; not part of the C-ABI): the
+// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4q; not part of the C-ABI): the
 // kernel-argument views of the store and of its opt-in layers, the functions a layer's file shares with another file, the
 // handle itself, and the guards every entry point starts with.  Included by kfstore.hip, by the layer files and by the
 // store's readers (match.hip, reloc.hip, tracker.hip, local_map.hip).
@@ -260,6 +260,24 @@ struct LoopArgs {
 // the front's searchByBoW(current, cand[c], mode 1, checkRot) for c < n_cand in ONE k_node_replay launch (match.hip)
 int loop_bow_replay(const LoopArgs &A, int current, int n_cand, hipStream_t st);
 
+// The loop fusion on the device (loop_fuse.hip): LoopClosing::searchAndFuse (loopClosing.cpp:496-516)
+// with Matcher::fuseByPose (matcher.cpp:1135-1238) from the store, over section 4m's overlay and match list.  What
+// vo_kfstore_enable_loop_fuse allocates, one block (C = max_corrected, P = max_loop_points): head [4] (passes of the last call,
+// "the call runs" -- 0 when the _loop form met a compute_sim3 that is not ACCEPTED --, the length of its list, 0); base
+// [C + 1], the call's match count at the start of a pass; rec [C][8]: (target, passed, matches, adds, replaces recorded,
+// replaces that moved a carrier, cleared, undone) per pass; and `in`, the host form's arrays as its one copy brings them:
+// S_corr [C][8] | corr_kf [C] | ids [P].
+constexpr int kLfRecInts = 8;
+enum { kLfTarget = 0, kLfPassed, kLfMatches, kLfAdds, kLfReplaces, kLfMoved, kLfCleared, kLfUndone };
+enum { kLfPasses = 0, kLfRuns, kLfNPoints };
+struct KfLoopFuseView {
+  int C, P;
+  int *head, *base, *rec;
+  double *S_corr;
+  int *corr_kf, *ids;
+  size_t reset_bytes, in_bytes;  // from head: what a call resets; from S_corr: the whole of `in`
+};
+
 // The loop pose graph from the store (pose_graph_store.hip): the pose collection and the four edge
 // families of Optimizer::solvePoseGraphLoop (optimizer_ceres.cpp:1062-1236) gathered on the device, and its write-back
 // (:1264-1301).  What vo_kfstore_enable_pose_graph allocates, one block: ledge [max_kf][kPgMaxLoopEdges] ascending (-1 beyond
@@ -372,6 +390,7 @@ enum KfLayer : unsigned {
   kLayerLoop = 1u << 6,
   kLayerPoseGraph = 1u << 7,
   kLayerKeyframeCreate = 1u << 8,
+  kLayerLoopFuse = 1u << 9,
 };
 
 // The window protocol local BA and the pose graph share: a *_window call enqueues the window and notes the store's
@@ -442,6 +461,9 @@ struct vo_kfstore {
   vo::OwnedDevBuf kc;                 // vo_kfstore_enable_keyframe_create: the block of section 4p
   vo::OwnedPinnedBuf kc_stage;        // a host form's inputs going up: one copy
   vo::KfCreateView K{};
+  vo::OwnedDevBuf lf;                 // vo_kfstore_enable_loop_fuse: the block of section 4q
+  vo::OwnedPinnedBuf lf_stage;        // the host form's arrays going up, the result coming down: one copy each
+  vo::KfLoopFuseView Q{};
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
