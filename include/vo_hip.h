@@ -1566,6 +1566,79 @@ int vo_kfstore_search_and_fuse_dev(vo_kfstore *s, int n_corr, const int32_t *dev
                                    const int32_t *dev_ids, float threshold);
 int vo_kfstore_search_and_fuse_loop(vo_kfstore *s, int n_corr, const int32_t *dev_corr_kf, const double *dev_S_corr, float threshold);
 int vo_kfstore_loop_fuse_result(vo_kfstore *s, int32_t *record /*[8]*/, int32_t *per_pass /*[max_corrected][6]*/);
+/* The loop correction on the device: the two steps of LoopClosing::correctLoop that PRODUCE the arrays
+ * vo_kfstore_search_and_fuse_loop and vo_kfstore_pose_graph_window_dev take -- the propagation of the loop Sim3 over the current
+ * key-frame's neighbours with the correction of their map points (loopClosing.cpp:364-437) and the loop connections (:461-479).
+ * Opt-in and additive: a store without it allocates and behaves as before.  A Sim3 is 8 doubles (quaternion x y z w,
+ * translation, scale); all Sim3 arithmetic is csrc/sim3_compose.h's, every operation rounded on its own; pointer-keyed
+ * containers are walked in ascending key-frame number; "holds", bit 0, bad(j), "erased" are the culling block's definitions.
+ * enable_loop_correct(max_corrected, max_corrected_points, max_loop_connections): valid on an EMPTY store on which
+ * vo_kfstore_enable_pose_graph has succeeded, capacities >= 1, else VO_ERR_INVALID.  One device block of
+ *   64 + 16 + 64 + up16(4 K) + up16(4 C) + 64 C + up16(4 B) + up16(4 P) + up16(C K)
+ *   + 2 up16(4 C) + 128 C + 2 up16(4 P) + up16(4 (C + 1)) + up16(4 E)   bytes
+ * (K = max_keyframes, C, P, E the three capacities, B = the observation index's capacity / 256): the record, the one-entry list
+ * of step 1, the Sim3 as received, position-in-corr_kf per key-frame, the list position per corrected key-frame, S_corr^-1, a count per workgroup of the index grid, the entry of every corrected point, a loop-connection row
+ * per list position; then the result, contiguous: list, corr_kf, S_corr, S_uncorr, cp_id, cp_ref, lc_start, lc_kf.  It also
+ * grows the connection layer's scratch (connections.hip: 16 n + 4 n K + 4 n bytes for a list of n entries, grow-only) to
+ * n = max_corrected when it is smaller: a second allocation at most, here and not in a call.  Synchronises once.
+ * Every propagate_loop and loop_connections call advances the generation word, also one that the device then refuses: the
+ * host cannot know, and a window taken before the call is conservatively no longer applicable.
+ * propagate_loop(curr, Scw[8]):
+ *  1. update(curr) as vo_kfstore_update_connections does it; the index is rebuilt first when stale.
+ *  2. currConnect = curr's ordered list as step 1 left it, then curr -- EVERY entry: isBad is not tested (:367).  It is kept in
+ *     this order for loop_connections; corr_kf is the same set strictly ascending.  More than max_corrected entries: status
+ *     OVERFLOW and the sticky VO_KFSTORE_CORRECT_LOOP_CAPACITY.  curr or a listed key-frame erased or without a pose column, or a
+ *     scale of Scw that is not > 0 (step 6 divides by it):
+ *     status EMPTY and the sticky VO_KFSTORE_CONNECTIONS_INVALID.  In either case nothing beyond step 1 is written.
+ *  3. S_uncorr[k] = s3_from_pose(T_k); S_corr[curr] = s3_load(Scw); for every other k, Swc = s3_inv(s3_from_pose(T_curr)),
+ *     Sic = s3_mul(S_uncorr[k], Swc), S_corr[k] = s3_mul(Sic, Scw): the reference's SE3 algebra as Sim3 algebra at scale 1.
+ *  4. corr_kf ascending, features ascending, bit 0 set: a point is corrected ONCE, through the lowest-numbered corrected
+ *     key-frame k that holds it, at its first carrying feature there, whose row is p:
+ *     p' = s3_act(s3_inv(S_corr[k]), s3_act(S_uncorr[k], p)), written to every live feature that carries the id, in EVERY
+ *     key-frame.  cp_ref of the point is k; cp_id is strictly ascending.  More than max_corrected_points: status OVERFLOW, the
+ *     sticky VO_KFSTORE_CORRECT_LOOP_CAPACITY, nothing beyond step 1 written.
+ *  5. updateNormalAndDepth of the point at once (:426), on the poses the reference's loop has at that moment: a holder, or the
+ *     reference key-frame, that is a corrected key-frame at a position of corr_kf BELOW k's has its corrected pose (step 6);
+ *     one at k's position or above, and one outside corr_kf, its stored pose.  Since k is the LOWEST corrected key-frame that
+ *     holds the point, and the reference key-frame is a holder, no holder lies below k: every pose is the stored one, although
+ *     step 6 overwrites it in the same call.  Everything else is vo_kfstore_refresh_points' contract and operation order.  A
+ *     point is refreshed once.
+ *  6. The pose column of corr_kf[j] becomes SE3(s3_matrix(q), t / s) of S_corr[j] (q normalised as step 3 left it, each
+ *     division rounded on its own).
+ *  7. update(k) for k in corr_kf ascending, as one update_connections list.
+ *  8. The generation word advances; the observation index stays valid (no id and no flag changes).
+ * The host form copies Scw up, enqueues, synchronises once; curr outside [0, size) or Scw NULL is VO_ERR_INVALID.
+ * propagate_loop_dev(curr, dev_Scw): Scw in device memory, read in place; ENQUEUED only: the index rebuilt when stale, one memset,
+ * 12 launches, no host synchronisation, no device-to-host copy, no allocation.  propagate_loop_sim3(): curr and Scw (13
+ * doubles R, t, s -> s3_from_pose(R, t) with the scale appended) where the last vo_kfstore_compute_sim3 left them, read in
+ * place; needs vo_kfstore_enable_loop (else VO_ERR_INVALID); ENQUEUED only.  A state other than VO_KFSTORE_LOOP_ACCEPTED is
+ * decided on the device: nothing changes, status EMPTY, VO_KFSTORE_CONNECTIONS_INVALID.
+ * loop_connections(): after the caller's search_and_fuse.  For kf in currConnect in LIST order: old = the members of kf's ordered
+ * list as this step finds it (after the updates of the earlier entries of this loop); update(kf); new = { j : W[kf][j] != 0 } as
+ * the step leaves it (the whole weight map; an update that finds no connection leaves the old row);
+ * loopConnections[kf] = new \ old \ currConnect, fixed at its own step.  Output: CSR over corr_kf ascending (lc_start [n_corr + 1],
+ * lc_kf, every row strictly ascending).  More than max_loop_connections: connections status OVERFLOW, the sticky
+ * VO_KFSTORE_CORRECT_LOOP_CAPACITY, no array valid.  The connection state afterwards is that of
+ * vo_kfstore_update_connections(currConnect in list order).  Without a successful propagate_loop before it (none since enable, or
+ * the last one refused): nothing changes, connections status EMPTY, VO_KFSTORE_CONNECTIONS_INVALID.  ENQUEUED only: the index
+ * rebuilt when stale, four launches; the generation word advances.
+ * loop_correct_result(record, list, corr_kf, S_corr, S_uncorr, cp_id, cp_ref, lc_start, lc_kf): synchronises; any pointer may be
+ * NULL.  record [16] = n_corr, n_cp, n_lc, curr, status of the last propagate (VO_KFSTORE_BA_WINDOW_OK / _EMPTY / _OVERFLOW), the
+ * feature rows step 4 wrote, status of the last loop_connections, 0 ...  The arrays are cut to the counts (nothing is copied
+ * for a status that is not OK); list [n_corr] is currConnect in list order.
+ * loop_correct_arrays(...): the DEVICE addresses of corr_kf, S_corr, S_uncorr, cp_id, cp_ref, lc_start and lc_kf (any pointer may
+ * be NULL); no synchronisation.  They stay where they are for the store's life; their contents are those of the last calls. */
+#define VO_KFSTORE_CORRECT_LOOP_CAPACITY 256
+int vo_kfstore_enable_loop_correct(vo_kfstore *s, int max_corrected, int max_corrected_points, int max_loop_connections);
+int vo_kfstore_propagate_loop(vo_kfstore *s, int curr, const double *Scw /*[8]*/);
+int vo_kfstore_propagate_loop_dev(vo_kfstore *s, int curr, const double *dev_Scw);
+int vo_kfstore_propagate_loop_sim3(vo_kfstore *s);
+int vo_kfstore_loop_connections(vo_kfstore *s);
+int vo_kfstore_loop_correct_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *list, int32_t *corr_kf, double *S_corr, double *S_uncorr,
+                                   int32_t *cp_id, int32_t *cp_ref, int32_t *lc_start, int32_t *lc_kf);
+int vo_kfstore_loop_correct_arrays(vo_kfstore *s, const int32_t **dev_corr_kf, const double **dev_S_corr, const double **dev_S_uncorr,
+                                   const int32_t **dev_cp_id, const int32_t **dev_cp_ref, const int32_t **dev_lc_start,
+                                   const int32_t **dev_lc_kf);
 /* Key-frame creation on the device: a tracked frame written into the store as a key-frame --
  * VisualOdometry::createNewKeyFrame (visualOdometry.cpp:463-517) with cullingTempMapPoints' slot rule (:844-853), and the first
  * key-frame of initVisualOdometry (:170-198) -- for a caller who keeps no host copy of ids or flags: the link between "frame

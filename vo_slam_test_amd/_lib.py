@@ -78,6 +78,8 @@ SYMBOLS = [
     "vo_kfstore_keyframe_need_stats", "vo_kfstore_keyframe_need_stats_dev",
     "vo_kfstore_enable_loop_fuse", "vo_kfstore_search_and_fuse", "vo_kfstore_search_and_fuse_dev", "vo_kfstore_search_and_fuse_loop",
     "vo_kfstore_loop_fuse_result",
+    "vo_kfstore_enable_loop_correct", "vo_kfstore_propagate_loop", "vo_kfstore_propagate_loop_dev", "vo_kfstore_propagate_loop_sim3",
+    "vo_kfstore_loop_connections", "vo_kfstore_loop_correct_result", "vo_kfstore_loop_correct_arrays",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -2130,6 +2132,57 @@ class KeyFrameStore:
         check(lib().vo_kfstore_loop_fuse_result(self._h, _p(rec), _p(per)), "vo_kfstore_loop_fuse_result")
         n = int(rec[0])
         return dict(passes=n, per_pass=[tuple(int(x) for x in row) for row in per[:n]], totals=tuple(int(x) for x in rec[1:7]))
+
+    CONNECTIONS_CORRECT_LOOP_CAPACITY = 256
+    LC_RECORD = ("n_corr", "n_cp", "n_lc", "curr", "status", "n_rows_moved", "connections_status")
+
+    def enable_loop_correct(self, max_corrected, max_corrected_points, max_loop_connections):
+        """the propagation of the loop Sim3 and the loop connections on the device from now on; valid on an
+        empty store after enable_pose_graph only"""
+        check(lib().vo_kfstore_enable_loop_correct(self._h, int(max_corrected), int(max_corrected_points), int(max_loop_connections)),
+              "vo_kfstore_enable_loop_correct")
+        self._lc_caps = (int(max_corrected), int(max_corrected_points), int(max_loop_connections))
+
+    def propagate_loop(self, curr=None, Scw=None):
+        """loopClosing.cpp:364-437 for the current key-frame and the loop Sim3 Scw (8 doubles: quaternion x y z w, translation,
+        scale).  A list / numpy array is copied and the call synchronises once; a device tensor (float64 [8]) is enqueued only;
+        curr = None: curr and Scw where the last compute_sim3 left them, enqueued only"""
+        if curr is None:
+            check(lib().vo_kfstore_propagate_loop_sim3(self._h), "vo_kfstore_propagate_loop_sim3")
+        elif hasattr(Scw, "data_ptr"):
+            _need_tensor(Scw, "float64", 8, "propagate_loop")
+            check(lib().vo_kfstore_propagate_loop_dev(self._h, int(curr), _p(Scw)), "vo_kfstore_propagate_loop_dev")
+        else:
+            S = np.ascontiguousarray(Scw, np.float64).reshape(-1)
+            if len(S) != 8:
+                raise VoError("vo_kfstore_propagate_loop failed with status -1: Scw is not 8 doubles")
+            check(lib().vo_kfstore_propagate_loop(self._h, int(curr), _p(S)), "vo_kfstore_propagate_loop")
+
+    def loop_connections(self):
+        """loopClosing.cpp:461-479 on the lists the last propagate_loop left, after the caller's search_and_fuse; enqueued only"""
+        check(lib().vo_kfstore_loop_connections(self._h), "vo_kfstore_loop_connections")
+
+    def loop_correct_result(self):
+        """the last propagate_loop / loop_connections -> dict(record (dict over LC_RECORD), list, corr_kf, S_corr, S_uncorr, cp_id,
+        cp_ref, lc_start, lc_kf) cut to the record's counts; the last seven are what pose_graph_window takes.  Synchronises"""
+        Cc, P, E = getattr(self, "_lc_caps", (1, 1, 1))
+        rec = np.zeros(16, np.int32)
+        a = dict(list=np.zeros(Cc, np.int32), corr_kf=np.zeros(Cc, np.int32), S_corr=np.zeros((Cc, 8)), S_uncorr=np.zeros((Cc, 8)),
+                 cp_id=np.zeros(P, np.int32), cp_ref=np.zeros(P, np.int32), lc_start=np.zeros(Cc + 1, np.int32), lc_kf=np.zeros(E, np.int32))
+        check(lib().vo_kfstore_loop_correct_result(self._h, _p(rec), *(_p(v) for v in a.values())), "vo_kfstore_loop_correct_result")
+        r = {k: int(rec[i]) for i, k in enumerate(self.LC_RECORD)}
+        ok = r["status"] == self.BA_WINDOW_OK
+        conn_ok = ok and r["connections_status"] == self.BA_WINDOW_OK
+        nc, ncp, nlc = (r["n_corr"] if ok else 0), (r["n_cp"] if ok else 0), (r["n_lc"] if conn_ok else 0)
+        n = dict(list=nc, corr_kf=nc, S_corr=nc, S_uncorr=nc, cp_id=ncp, cp_ref=ncp, lc_start=nc + 1 if conn_ok else 0, lc_kf=nlc)
+        return dict({k: v[:n[k]].copy() for k, v in a.items()}, record=r)
+
+    def loop_correct_arrays(self):
+        """-> dict(corr_kf, S_corr, S_uncorr, cp_id, cp_ref, lc_start, lc_kf) of DEVICE addresses (ints), as
+        vo_kfstore_search_and_fuse_loop and vo_kfstore_pose_graph_window_dev take them; no synchronisation"""
+        ptrs = [C.c_void_p() for _ in range(7)]
+        check(lib().vo_kfstore_loop_correct_arrays(self._h, *(C.byref(p) for p in ptrs)), "vo_kfstore_loop_correct_arrays")
+        return {k: int(p.value or 0) for k, p in zip(("corr_kf", "S_corr", "S_uncorr", "cp_id", "cp_ref", "lc_start", "lc_kf"), ptrs)}
 
     KC_RECORD = ("keyframe", "n", "n_pairs", "n_walked", "n_created", "n_tracked", "first_id", "next_id", "ended_early", "status")
     _KC_COLUMNS = (("x", "float32"), ("y", "float32"), ("octave", "int32"), ("angle", "float32"), ("depth", "float32"), ("u_right", "float32"))

@@ -9,6 +9,8 @@
 //                 key-frame inside a step, a barrier separates the steps.  Nothing is sorted here.
 //   k_conn_order  a workgroup per touched key-frame: its ordered list from its weight row and mode bit (:127-134, :176-198),
 //                 its children from the parent column, its graph row for k_lm_keyframes.
+// k_conn_apply_rows is k_conn_apply for the loop correction: the same sequence, which also emits per step
+// the row of the loop connections, from the list membership as the step finds it.
 // As in local_map.hip nothing depends on which thread runs when: the counts are integer sums, a step of the sequence
 // writes every word from one thread, and the order comes from a fixed sorting network over distinct keys.
 #include "kfstore.h"
@@ -76,12 +78,17 @@ __device__ __forceinline__ void block_reduce(int &n, unsigned long long &a, unsi
 }
 
 // meta[t] = (key-frame or -1: skipped, entries >= 15, kfmax or -1: no connection, front of the sorted list)
+// n_live: NULL, or the device word that says how many entries of the list count; those beyond it are skipped silently
 __global__ __launch_bounds__(256) void k_conn_count(KfStoreView S, KfObsView O, const int *list, const int *erased, int *rows, int4 *meta,
-                                                    int *status) {
+                                                    int *status, const int *n_live) {
   __shared__ int hist[kMaxKf];
   __shared__ int s_n[256];
   __shared__ unsigned long long s_a[256], s_b[256];
   const int t = blockIdx.x, tid = threadIdx.x, size = S.size, NK = S.NK;
+  if (n_live && t >= *n_live) {  // (uniform over the workgroup)
+    if (tid == 0) meta[t] = make_int4(-1, 0, -1, -1);
+    return;
+  }
   const int k = list[t];
   if (k < 0 || k >= size || (erased && erased[k])) {  // (uniform over the workgroup; an erased key-frame is never updated)
     if (tid == 0) atomicOr(status, (int)kConnInvalid), meta[t] = make_int4(-1, 0, -1, -1);
@@ -161,6 +168,70 @@ __global__ __launch_bounds__(1024) void k_conn_apply(int size, int max_kf, int n
     if (tid == 0) {
       store_wg(mode + k, 0), store_wg(touched + k, 1);
       if (k != 0 && load_wg(first + k)) {  // (:145-150)
+        store_wg(parent + k, m.w), store_wg(first + k, 0), store_wg(touched + m.w, 1);
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    __syncthreads();
+  }
+}
+
+// k_conn_apply's sequence, and per step the ROW of the loop connections (loopClosing.cpp:461-479):
+// out[t][j] = 1 iff key-frame j is in k's weight map as the step leaves it (`getConnectKFs`: the whole map, and the old one when
+// the update finds no connection), was NOT a member of k's ordered list as the step found it, and is not listed.  The
+// membership is the function of the weight row and the mode bit k_conn_order sorts by: the whole map, or the entries >= 15,
+// or -- when there is none -- the first strictly largest one.  It is taken from the state of the SEQUENCE: an earlier step that
+// changed a weight of k has switched k to its whole map.  No prefetch here: a step is one row, the list is short.
+__global__ __launch_bounds__(1024) void k_conn_apply_rows(int size, int max_kf, int n, const int *rows, const int4 *meta, int *W, int *mode,
+                                                          int *first, int *parent, int *touched, const int *listed, uint8_t *out) {
+  constexpr int kPer = kMaxKf / 1024;
+  __shared__ int s_n[1024];
+  __shared__ unsigned long long s_a[1024];
+  const int tid = threadIdx.x;
+  for (int t = 0; t < n; t++) {
+    const int4 m = meta[t];
+    const int k = m.x;
+    uint8_t *row = out + (size_t)t * max_kf;
+    if (k < 0) {  // skipped, or beyond the list (uniform): an empty row
+      for (int j = tid; j < size; j += 1024) row[j] = 0;
+      continue;
+    }
+    const bool live = m.z >= 0;
+    const bool whole = load_wg(mode + k) != 0;
+    int w0[kPer], nt = 0;
+    unsigned long long best = 0;
+    for (int r = 0; r < kPer; r++) {
+      const int j = tid + r * 1024;
+      w0[r] = j < size ? load_wg(W + (size_t)k * max_kf + j) : 0;
+      if (w0[r] > 0) best = max(best, key_lowest(w0[r], j));
+      if (w0[r] >= kThreshold) nt++;
+    }
+    __syncthreads();  // (the arrays of the previous step have been read)
+    s_n[tid] = nt, s_a[tid] = best;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+      if (tid < w) s_n[tid] += s_n[tid + w], s_a[tid] = s_a[tid + w] > s_a[tid] ? s_a[tid + w] : s_a[tid];
+      __syncthreads();
+    }
+    nt = s_n[0], best = s_a[0];
+    const int kfmax0 = best ? 0x7fffffff - (int)(best & 0xffffffffu) : -1;
+    for (int r = 0; r < kPer; r++) {
+      const int j = tid + r * 1024;
+      if (j >= size) continue;
+      const bool old = whole ? w0[r] > 0 : (nt > 0 ? w0[r] >= kThreshold : j == kfmax0);
+      int c = w0[r];  // `new` without a connection: the row as it stands (:95)
+      if (live) {
+        c = rows[(size_t)t * max_kf + j];
+        const bool in = m.y > 0 ? c >= kThreshold : j == m.z;
+        if (in && load_wg(W + (size_t)j * max_kf + k) != c)
+          store_wg(W + (size_t)j * max_kf + k, c), store_wg(mode + j, 1), store_wg(touched + j, 1);
+        store_wg(W + (size_t)k * max_kf + j, c);
+      }
+      row[j] = (c != 0 && !old && !listed[j]) ? 1 : 0;
+    }
+    if (live && tid == 0) {
+      store_wg(mode + k, 0), store_wg(touched + k, 1);
+      if (k != 0 && load_wg(first + k)) {
         store_wg(parent + k, m.w), store_wg(first + k, 0), store_wg(touched + m.w, 1);
       }
     }
@@ -295,9 +366,30 @@ int connections_reserve(KfConnections *c, int n, int **dev_list) {
 int connections_update(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n, const int *dev_list, hipStream_t st) {
   if (n <= 0 || S.size <= 0) return VO_OK;
   VO_CHECK(connections_reserve(c, n, nullptr));
-  hipLaunchKernelGGL(k_conn_count, dim3(n), dim3(256), 0, st, S, O, dev_list, c->erased, c->rows, c->meta, c->status);
+  hipLaunchKernelGGL(k_conn_count, dim3(n), dim3(256), 0, st, S, O, dev_list, c->erased, c->rows, c->meta, c->status, (const int *)nullptr);
   hipLaunchKernelGGL(k_conn_apply, dim3(1), dim3(1024), 0, st, S.size, c->max_kf, n, (const int *)c->rows, (const int4 *)c->meta, c->W,
                      c->mode, c->first, c->parent, c->touched);
+  return connections_order(c, S.size, st);
+}
+
+// (the scratch for n_max entries was reserved when the caller's layer was enabled: nothing is allocated here)
+int connections_update_counted(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n_max, const int *dev_list, const int *dev_n,
+                               hipStream_t st) {
+  if (n_max <= 0 || S.size <= 0) return VO_OK;
+  if (n_max > c->n_cap) return VO_ERR_CAPACITY;
+  hipLaunchKernelGGL(k_conn_count, dim3(n_max), dim3(256), 0, st, S, O, dev_list, c->erased, c->rows, c->meta, c->status, dev_n);
+  hipLaunchKernelGGL(k_conn_apply, dim3(1), dim3(1024), 0, st, S.size, c->max_kf, n_max, (const int *)c->rows, (const int4 *)c->meta, c->W,
+                     c->mode, c->first, c->parent, c->touched);
+  return connections_order(c, S.size, st);
+}
+
+int connections_update_rows(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n_max, const int *dev_list, const int *dev_n,
+                            const int *listed, uint8_t *out, hipStream_t st) {
+  if (n_max <= 0 || S.size <= 0) return VO_OK;
+  if (n_max > c->n_cap) return VO_ERR_CAPACITY;
+  hipLaunchKernelGGL(k_conn_count, dim3(n_max), dim3(256), 0, st, S, O, dev_list, c->erased, c->rows, c->meta, c->status, dev_n);
+  hipLaunchKernelGGL(k_conn_apply_rows, dim3(1), dim3(1024), 0, st, S.size, c->max_kf, n_max, (const int *)c->rows, (const int4 *)c->meta,
+                     c->W, c->mode, c->first, c->parent, c->touched, listed, out);
   return connections_order(c, S.size, st);
 }
 

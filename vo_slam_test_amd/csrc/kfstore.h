@@ -1,4 +1,4 @@
-// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4q; not part of the C-ABI): the
+// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4r; not part of the C-ABI): the
 // kernel-argument views of the store and of its opt-in layers, the functions a layer's file shares with another file, the
 // handle itself, and the guards every entry point starts with.  Included by kfstore.hip, by the layer files and by the
 // store's readers (match.hip, reloc.hip, tracker.hip, local_map.hip).
@@ -61,6 +61,16 @@ struct KfConnView {
   int *W, *ordered, *n_ordered, *mode, *parent, *touched, *status;
 };
 KfConnView connections_view(const KfConnections *c);
+// for the loop correction (loop_correct.hip), whose list and length only the device knows.  n_max: the
+// entries the launches are sized for (reserved beforehand); dev_n: how many of them count -- the rest is skipped without a
+// sticky bit.  connections_update_counted is connections_update for such a list.  connections_update_rows also writes, per
+// list position t, out[t * max_kf + j] = 1 for the key-frames j that update(list[t]) connects list[t] to -- the weight row as
+// the step leaves it, less the members of list[t]'s ordered list as the step FOUND it, less the key-frames with listed[j] != 0
+// (loopClosing.cpp:461-479); the connection state afterwards is connections_update's.
+int connections_update_counted(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n_max, const int *dev_list, const int *dev_n,
+                               hipStream_t st);
+int connections_update_rows(KfConnections *c, const KfStoreView &S, const KfObsView &O, int n_max, const int *dev_list, const int *dev_n,
+                            const int *listed, uint8_t *out, hipStream_t st);
 void connections_set_erased(KfConnections *c, const int *erased);
 int connections_order(KfConnections *c, int size, hipStream_t st);
 
@@ -312,6 +322,31 @@ struct PgInputs {
   size_t bytes;
 };
 
+// The loop correction from the store (loop_correct.hip): the propagation of the loop Sim3 over the current
+// key-frame's neighbours with the point correction (loopClosing.cpp:364-437) and the loop connections (:461-479).  What
+// vo_kfstore_enable_loop_correct allocates, one block (C = max_corrected, P = max_corrected_points, E = max_loop_connections):
+// rec [kLcRecInts] (enum below); cur [4], the one-entry list of step 1; scw [8], the loop Sim3 as the call received it; pos_of
+// [max_kf], position + 1 in corr_kf (0: not corrected); perm [C], the list position of corr_kf[r]; S_inv [C][8], S_corr^-1; blk, the first-occurrence count of every workgroup of the index grid; cp_ent [P], the
+// entry a corrected point is read at; rows [C][max_kf] bytes, a loop-connection row per list position; and the RESULT,
+// contiguous so that one copy fetches it: list [C] (currConnect in list order), corr_kf [C], S_corr | S_unc [C][8], cp_id |
+// cp_ref [P], lc_start [C + 1], lc_kf [E].
+constexpr int kLcRecInts = 16;
+enum { kLcNCorr = 0, kLcNCp, kLcNLc, kLcCurr, kLcStatus, kLcNRows, kLcConnStatus, kLcLive, kLcValid, kLcSetup };
+struct KfLoopCorrectView {
+  int C, P, E, max_kf, n_blk;
+  int *rec, *cur;
+  double *scw;
+  int *pos_of, *perm;
+  double *S_inv;
+  int *blk, *cp_ent;
+  uint8_t *rows;
+  uint8_t *res;
+  size_t res_bytes;
+  int *list, *corr_kf;
+  double *S_corr, *S_unc;
+  int *cp_id, *cp_ref, *lc_start, *lc_kf;
+};
+
 // Key-frame creation on the device (keyframe_create.hip): VisualOdometry::createNewKeyFrame
 // (visualOdometry.cpp:463-517) and the first key-frame of initVisualOdometry (:170-198) written into the store.  What
 // vo_kfstore_enable_keyframe_create allocates, one block (P = pow2_ceil(NK)): keys [P], the depth walk's sort keys when they
@@ -391,6 +426,7 @@ enum KfLayer : unsigned {
   kLayerPoseGraph = 1u << 7,
   kLayerKeyframeCreate = 1u << 8,
   kLayerLoopFuse = 1u << 9,
+  kLayerLoopCorrect = 1u << 10,
 };
 
 // The window protocol local BA and the pose graph share: a *_window call enqueues the window and notes the store's
@@ -464,6 +500,9 @@ struct vo_kfstore {
   vo::OwnedDevBuf lf;                 // vo_kfstore_enable_loop_fuse: the block of section 4q
   vo::OwnedPinnedBuf lf_stage;        // the host form's arrays going up, the result coming down: one copy each
   vo::KfLoopFuseView Q{};
+  vo::OwnedDevBuf lc;                 // vo_kfstore_enable_loop_correct: the block of section 4r
+  vo::OwnedPinnedBuf lc_stage;        // the host form's Sim3 going up, the result coming down: one copy each
+  vo::KfLoopCorrectView R{};
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 

@@ -13,6 +13,7 @@
 //   k_ba_erase   a lane per point: the erased edges' key-frames leave the holders, the point dies when obs <= 2; a thread
 //                per free camera writes its pose
 //   k_ba_refresh a lane per point: the new position into every live feature that carries it, then updateNormalAndDepth
+//                (refresh_point.h: the body, shared with the loop correction)
 // Nothing depends on which thread runs when: positions come from counts and scans, the atomics are integer sums, and every
 // byte and word of the store has one writer per launch (an entry of the index carries one id, a point has one lane).
 // Compiled with -ffp-contract=off: the refresh rounds every double operation on its own, in the order section 4k writes down.
@@ -21,6 +22,7 @@
 #include "ba_math.h"
 #include "new_points_geom.h"
 #include "obs_walk.h"
+#include "refresh_point.h"
 
 #include <algorithm>
 
@@ -352,72 +354,13 @@ __global__ __launch_bounds__(256) void k_ba_erase(ApplyArgs A) {
 // or NULL (the position is the store's row at the id's first live key); dead: [n] or NULL.  The index may be older than the
 // flags: a key is live iff its flags byte has bit 0 now.
 __global__ __launch_bounds__(256) void k_ba_refresh(ApplyArgs A, int n, const int *ids, const double *new_pos, const uint8_t *dead) {
-  const int t = blockIdx.x * 256 + threadIdx.x, NK = A.S.NK, size = A.S.size;
+  const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n || (dead && dead[t])) return;  // dead points are not refreshed, rows of cleared features keep their bytes
   const int id = ids[t];
   if (id < 0) return;  // (a device list's "no point here": the host forms validate their ids)
-  const int start = obs_lower_bound(A.O, id);
-  auto live = [&](int kk, unsigned e) { return !A.X.erased[kk] && (*flag_byte(A.S, e) & 1); };
-  double p[3] = {0, 0, 0}, sum[3] = {0, 0, 0};
+  double p[3] = {0, 0, 0};
   if (new_pos) p[0] = new_pos[3 * (size_t)t], p[1] = new_pos[3 * (size_t)t + 1], p[2] = new_pos[3 * (size_t)t + 2];
-  int r0 = -2, lowest = -1, cnt = 0;
-  bool r0_holds = false, no_pose = false;
-  double len_r0 = -1, len_low = -1;  // |p - Ow| of the two reference candidates (< 0: without a pose)
-  int oct_r0 = 0, oct_low = 0;
-  obs_run_holders(A.O, NK, size, start, id, live, [&](int kk, int f) {
-    if (r0 == -2) {  // the first live key
-      r0 = A.B.ref_kf[(size_t)kk * NK + f], lowest = kk;
-      if (!new_pos) {
-        const double *P = kf_sec<double>(A.S, kk, A.S.o_points) + 3 * (size_t)f;
-        p[0] = P[0], p[1] = P[1], p[2] = P[2];
-      }
-    }
-    double len = -1;
-    if (*np_pose_set(A.M, kk)) {
-      double Ow[3], d[3];
-      np_center(np_pose(A.M, kk), Ow);
-      for (int c = 0; c < 3; c++) d[c] = __dadd_rn(p[c], -Ow[c]);
-      len = __dsqrt_rn(np_dot3(d[0], d[0], d[1], d[1], d[2], d[2]));
-      for (int c = 0; c < 3; c++) sum[c] = __dadd_rn(sum[c], __ddiv_rn(d[c], len));
-      cnt++;
-    } else {
-      no_pose = true;
-    }
-    const int oct = min(max(cull_octave(A.X, kk)[f], 0), 15);
-    if (kk == lowest) len_low = len, oct_low = oct;
-    if (kk == r0) r0_holds = true, len_r0 = len, oct_r0 = oct;
-    return true;
-  });
-  if (no_pose) atomicOr(A.status, (int)VO_KFSTORE_CONNECTIONS_INVALID);
-  if (lowest < 0) return;  // no holder: nothing to write
-  const int ref = r0_holds ? r0 : lowest;  // (mappoint.cpp:350-351 under the ascending rule)
-  const double len_ref = r0_holds ? len_r0 : len_low;
-  const bool has_dist = len_ref >= 0, has_normal = cnt > 0;
-  float maxd = 0.f, mind = 0.f;
-  if (has_dist) {
-    maxd = (float)len_ref * A.M.sf[r0_holds ? oct_r0 : oct_low];
-    mind = maxd / A.M.sf[min(max(A.M.n_levels - 1, 0), 15)];
-  }
-  double nrm[3] = {0, 0, 0};
-  if (has_normal)
-    for (int c = 0; c < 3; c++) nrm[c] = __ddiv_rn(sum[c], (double)cnt);
-  obs_run_each(A.O, start, id, [&](unsigned e) {
-    const int kk = (int)(e / (unsigned)NK);
-    if (kk >= size || !live(kk, e)) return true;
-    const int f = (int)(e - (unsigned)kk * (unsigned)NK);
-    uint8_t *r = const_cast<uint8_t *>(A.S.base) + (size_t)kk * A.S.rec;
-    if (new_pos) {
-      double *pt = reinterpret_cast<double *>(r + A.S.o_points) + 3 * (size_t)f;
-      pt[0] = p[0], pt[1] = p[1], pt[2] = p[2];
-    }
-    A.B.ref_kf[(size_t)kk * NK + f] = ref;
-    if (has_normal) {
-      double *nv = A.normals + ((size_t)kk * NK + f) * 3;
-      nv[0] = nrm[0], nv[1] = nrm[1], nv[2] = nrm[2];
-    }
-    if (has_dist) reinterpret_cast<float *>(r + A.S.o_mind)[f] = mind, reinterpret_cast<float *>(r + A.S.o_maxd)[f] = maxd;
-    return true;
-  });
+  refresh_point(A.S, A.O, A.X, A.M, A.B.ref_kf, A.normals, A.status, id, p, new_pos != nullptr);  // (refresh_point.h)
 }
 
 __global__ void k_ba_init(KfBaView B) {
