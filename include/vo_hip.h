@@ -1639,6 +1639,65 @@ int vo_kfstore_loop_correct_result(vo_kfstore *s, int32_t *record /*[16]*/, int3
 int vo_kfstore_loop_correct_arrays(vo_kfstore *s, const int32_t **dev_corr_kf, const double **dev_S_corr, const double **dev_S_uncorr,
                                    const int32_t **dev_cp_id, const int32_t **dev_cp_ref, const int32_t **dev_lc_start,
                                    const int32_t **dev_lc_kf);
+/* The merge of the loop matches on the device: the loop of LoopClosing::correctLoop that gives the current
+ * key-frame the loop's map points (loopClosing.cpp:439-455), between propagate_loop and search_and_fuse; and the composed
+ * vo_kfstore_correct_loop.  Opt-in and additive: a store without it allocates and behaves as before.  "Holds", "observation",
+ * isBad ("nobody holds it"), a point's attributes (those of its lowest live carrier), replace(A -> B) with its carrier limit and
+ * compute_descriptors are the fusion block's definitions.
+ * enable_loop_merge(): valid on an EMPTY store on which vo_kfstore_enable_loop_fuse has succeeded, else VO_ERR_INVALID.  One
+ * device block of
+ *   16 + 64 + 6 up16(4 NK)   bytes, NK = max_features:
+ * the call's head, the record (16 ints), per feature of the current key-frame the step's plan (the branch taken, ALONE / ORDERED,
+ * the ordered steps' features, the overlay node of an add: two words), and the host form's match_ids.  Synchronises once.  The
+ * calls work on the fusion layer's overlay slots (reset at the start of a call) with the nodes of this block, one per feature, so
+ * that an add never meets max_candidates; the match list and the records of the last fuse / search_and_fuse call survive.
+ * merge_loop_matches(curr, n, match_ids): for i ascending over [0, min(n, features of curr)) with B = match_ids[i] >= 0, each step
+ * on the state the steps before it left:
+ *  - NO-OP: feature i of curr has bit 0 and carries A >= 0 with A == B: nothing happens, no descriptor is recomputed
+ *    (mappoint.cpp:216).
+ *  - DEAD B: nobody holds B when the step comes (an earlier step of the call replaced it away, or the caller handed in a dead id).
+ *    The reference would copy a dead object's attributes; the store has none: the step is skipped and counted.
+ *  - REPLACE: feature i has bit 0 and carries A >= 0, A != B: replace(A -> B) as the fusion block defines it -- an observation of
+ *    A whose key-frame does not hold B takes B's id and attributes, every other carrier of A loses bit 0, the recent-list counters
+ *    are added when both are listed, compute_descriptors(B).  Always org -> loop point: no observation count is compared.  More
+ *    than VO_KFSTORE_FUSE_MAX_CARRIERS live features on either side: left undone, the sticky VO_KFSTORE_FUSE_CAPACITY.
+ *  - ADD: feature i has bit 0 clear (or a negative id): it takes B's id, bit 0 and B's attributes, then compute_descriptors(B).
+ *    Whether curr holds B at another feature already is NOT tested (the reference does not): the id then stands in two features
+ *    of curr, and curr's observation is the lowest-numbered of them (the pointer model keeps the one registered first).  A B that
+ *    then has more than VO_KFSTORE_FUSE_MAX_CARRIERS live features keeps its descriptor, the sticky VO_KFSTORE_UPKEEP_CAPACITY.
+ *  There is no updateNormalAndDepth in either branch.  Afterwards the observation index is stale and the generation word has
+ *  advanced; connections are NOT updated (the reference updates them at :469: vo_kfstore_loop_connections).
+ * Decided on the device: curr outside [0, size) or erased, or (the _loop form) a compute_sim3 state other than
+ * VO_KFSTORE_LOOP_ACCEPTED: nothing changes, the record shows 0 steps, VO_KFSTORE_CONNECTIONS_INVALID.
+ * The host form validates before anything is enqueued: n > max_features VO_ERR_CAPACITY; n < 0, or NULL with n > 0,
+ * VO_ERR_INVALID (so do the _dev form's); then ONE copy up, the enqueue, ONE synchronisation.  merge_loop_matches_dev: the list in
+ * device memory, read in place; ENQUEUED only: the index rebuilt when stale, two memsets, four launches, no host synchronisation,
+ * no device-to-host copy, no allocation.  merge_loop_matches_loop(): curr, matchMapPoints_ and its length where the last
+ * vo_kfstore_compute_sim3 left them, read in place; needs vo_kfstore_enable_loop (else VO_ERR_INVALID); ENQUEUED only.
+ * loop_merge_result(record, per_feature): synchronises; either may be NULL.  record [16] = steps (entries >= 0), adds, no-ops,
+ * replaces recorded (carried out or left undone), replaces that moved at least one carrier, features cleared, dead Bs, replaces
+ * left undone for the carrier limit, steps that ran on the ordered path (those that share an id with another step of the call),
+ * curr, 0 ...; per_feature [max_features] = the branch at feature i: 0 none, 1 add, 2 no-op, 3 replace, 4 dead, 5 undone.
+ * correct_loop(threshold, max_iterations, summary, record): correctLoop from :364 to :485 on the state the last compute_sim3
+ * left; needs enable_loop, enable_loop_correct and enable_loop_merge (else VO_ERR_INVALID).  A fixed sequence:
+ *  1. propagate_loop_sim3; 2. merge_loop_matches_loop; 3. ONE synchronising read (the propagation's record, the merge's,
+ *  compute_sim3's state, the sticky word -- read, not cleared); 4. search_and_fuse_loop(n_corr, the layer's corr_kf and S_corr,
+ *  threshold) (the reference passes 4); 5. loop_connections; 6. ONE synchronising read (n_lc, the connections status, the sticky
+ *  word, the fusion's record); 7. pose_graph_window_dev on the layer's device arrays with curr and match of compute_sim3's record,
+ *  then vo_kfstore_pose_graph's tail: the window copied down, vo_pose_graph_solve with fix_scale as compute_sim3 was called, the
+ *  apply; 8. add_loop_edge(curr, match).
+ * Returns VO_ERR_INVALID when the last compute_sim3 was not ACCEPTED or a step reports EMPTY; VO_ERR_CAPACITY when a step
+ * overflowed or VO_KFSTORE_FUSE_CAPACITY stands in the sticky word at step 3 or 6 (a bit an earlier call left counts: read and
+ * clear the word first); whatever the solver refuses as it is, with nothing written back by step 7 or 8.  The store is then as
+ * the steps before the stop specify.  record [16] (may be NULL) = curr, match, n_corr, n_cp, n_lc, the merge's adds and replaces,
+ * the fusion's totals of adds and replaces, the window's n_nodes and n_edges, the apply's n_points_moved (one more small read,
+ * made only when record is given), the step at which the call stopped (0 = finished), 0 ... */
+int vo_kfstore_enable_loop_merge(vo_kfstore *s);
+int vo_kfstore_merge_loop_matches(vo_kfstore *s, int curr, int n, const int32_t *match_ids);
+int vo_kfstore_merge_loop_matches_dev(vo_kfstore *s, int curr, int n, const int32_t *dev_match_ids);
+int vo_kfstore_merge_loop_matches_loop(vo_kfstore *s);
+int vo_kfstore_loop_merge_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *per_feature /*[max_features]*/);
+int vo_kfstore_correct_loop(vo_kfstore *s, float threshold, int max_iterations, vo_lm_summary *summary, int32_t *record /*[16], may be NULL*/);
 /* Key-frame creation on the device: a tracked frame written into the store as a key-frame --
  * VisualOdometry::createNewKeyFrame (visualOdometry.cpp:463-517) with cullingTempMapPoints' slot rule (:844-853), and the first
  * key-frame of initVisualOdometry (:170-198) -- for a caller who keeps no host copy of ids or flags: the link between "frame

@@ -80,6 +80,8 @@ SYMBOLS = [
     "vo_kfstore_loop_fuse_result",
     "vo_kfstore_enable_loop_correct", "vo_kfstore_propagate_loop", "vo_kfstore_propagate_loop_dev", "vo_kfstore_propagate_loop_sim3",
     "vo_kfstore_loop_connections", "vo_kfstore_loop_correct_result", "vo_kfstore_loop_correct_arrays",
+    "vo_kfstore_enable_loop_merge", "vo_kfstore_merge_loop_matches", "vo_kfstore_merge_loop_matches_dev",
+    "vo_kfstore_merge_loop_matches_loop", "vo_kfstore_loop_merge_result", "vo_kfstore_correct_loop",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -2183,6 +2185,47 @@ class KeyFrameStore:
         ptrs = [C.c_void_p() for _ in range(7)]
         check(lib().vo_kfstore_loop_correct_arrays(self._h, *(C.byref(p) for p in ptrs)), "vo_kfstore_loop_correct_arrays")
         return {k: int(p.value or 0) for k, p in zip(("corr_kf", "S_corr", "S_uncorr", "cp_id", "cp_ref", "lc_start", "lc_kf"), ptrs)}
+
+    LM_RECORD = ("steps", "adds", "noops", "replaces", "moved", "cleared", "n_dead", "undone", "ordered", "curr")
+    LM_NONE, LM_ADD, LM_NOOP, LM_REPLACE, LM_DEAD, LM_UNDONE = range(6)
+    CL_RECORD = ("curr", "match", "n_corr", "n_cp", "n_lc", "merge_adds", "merge_replaces", "fuse_adds", "fuse_replaces", "n_nodes", "n_edges",
+                 "n_points_moved", "stopped_at")
+
+    def enable_loop_merge(self):
+        """the merge of the loop matches (loopClosing.cpp:439-455) and the composed correct_loop on the device from now on
+        (DESIGN.md section 4s); valid on an empty store after enable_loop_fuse only"""
+        check(lib().vo_kfstore_enable_loop_merge(self._h), "vo_kfstore_enable_loop_merge")
+
+    def merge_loop_matches(self, curr=None, match_ids=None):
+        """the current key-frame takes the loop's map points: feature i replaces its point by match_ids[i] >= 0, or takes it when
+        it has none.  A list / numpy array is copied and the call synchronises once; a device tensor (int32) is enqueued only;
+        curr = None: curr and matchMapPoints_ where the last compute_sim3 left them, enqueued only"""
+        if curr is None:
+            check(lib().vo_kfstore_merge_loop_matches_loop(self._h), "vo_kfstore_merge_loop_matches_loop")
+        elif hasattr(match_ids, "data_ptr"):
+            _need_tensor(match_ids, "int32", None, "merge_loop_matches")
+            check(lib().vo_kfstore_merge_loop_matches_dev(self._h, int(curr), int(match_ids.numel()), _p(match_ids)),
+                  "vo_kfstore_merge_loop_matches_dev")
+        else:
+            a = np.ascontiguousarray(match_ids, np.int32).reshape(-1)
+            check(lib().vo_kfstore_merge_loop_matches(self._h, int(curr), len(a), _p(a)), "vo_kfstore_merge_loop_matches")
+
+    def loop_merge_result(self):
+        """the last merge_loop_matches -> dict(record (dict over LM_RECORD), per_feature [max_features]: LM_NONE, LM_ADD, LM_NOOP,
+        LM_REPLACE, LM_DEAD, LM_UNDONE); synchronises"""
+        rec, per = np.zeros(16, np.int32), np.zeros(self.max_features, np.int32)
+        check(lib().vo_kfstore_loop_merge_result(self._h, _p(rec), _p(per)), "vo_kfstore_loop_merge_result")
+        return dict(record={k: int(rec[i]) for i, k in enumerate(self.LM_RECORD)}, per_feature=per)
+
+    def correct_loop(self, threshold=4.0, max_iterations=20):
+        """correctLoop (loopClosing.cpp:364-485) on the state the last compute_sim3 left: propagate_loop, merge_loop_matches,
+        search_and_fuse, loop_connections, the pose graph (window, solve, write-back) and the loop edge in one call
+        -> (summary, record: dict over CL_RECORD).  A refusal raises; self.correct_loop_record then holds the record"""
+        s, rec = LmSummary(), np.zeros(16, np.int32)
+        rc = lib().vo_kfstore_correct_loop(self._h, C.c_float(threshold), int(max_iterations), C.byref(s), _p(rec))
+        self.correct_loop_record = {k: int(rec[i]) for i, k in enumerate(self.CL_RECORD)}
+        check(rc, "vo_kfstore_correct_loop")
+        return s, self.correct_loop_record
 
     KC_RECORD = ("keyframe", "n", "n_pairs", "n_walked", "n_created", "n_tracked", "first_id", "next_id", "ended_early", "status")
     _KC_COLUMNS = (("x", "float32"), ("y", "float32"), ("octave", "int32"), ("angle", "float32"), ("depth", "float32"), ("u_right", "float32"))

@@ -48,6 +48,7 @@ SOURCES = [
     ("keyframe_create.hip", ["-ffp-contract=off"]),
     ("loop_fuse.hip", ["-ffp-contract=off"]),
     ("loop_correct.hip", ["-ffp-contract=off"]),
+    ("loop_merge.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

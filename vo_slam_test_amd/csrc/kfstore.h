@@ -1,4 +1,4 @@
-// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4r; not part of the C-ABI): the
+// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4s; not part of the C-ABI): the
 // kernel-argument views of the store and of its opt-in layers, the functions a layer's file shares with another file, the
 // handle itself, and the guards every entry point starts with.  Included by kfstore.hip, by the layer files and by the
 // store's readers (match.hip, reloc.hip, tracker.hip, local_map.hip).
@@ -347,6 +347,24 @@ struct KfLoopCorrectView {
   int *cp_id, *cp_ref, *lc_start, *lc_kf;
 };
 
+// The merge of the loop matches from the store (loop_merge.hip): loopClosing.cpp:439-455, a step per
+// feature of the current key-frame, on section 4m's overlay and fuse_ops.h.  What vo_kfstore_enable_loop_merge allocates, one
+// block: head [4] (enum below); rec [kMgRecInts] (enum below); per feature of the current key-frame the step's PLAN -- branch
+// [NK] (the branch taken, include/vo_hip.h's per_feature), kind [NK] (0 no step, kMgAlone, kMgOrdered), ordered [NK] (the
+// ordered steps' features, ascending), node_entry / node_next [NK] (the overlay node of the add at that feature: the call walks
+// the fusion layer's m_next / m_tail / a_head with THESE nodes, so that an add never meets max_candidates) -- which is what a
+// call resets; and ids [NK], the host form's match_ids as its one copy brings them.
+constexpr int kMgRecInts = 16;
+enum { kMgRuns = 0, kMgCurr, kMgN, kMgNOrdered };  // head
+enum { kMgSteps = 0, kMgAdds, kMgNoops, kMgReplaces, kMgMoved, kMgCleared, kMgDead, kMgUndone, kMgOrderedSteps, kMgRecCurr };
+enum { kMgAlone = 1, kMgOrdered = 2 };
+enum { kMgBrNone = 0, kMgBrAdd, kMgBrNoop, kMgBrReplace, kMgBrDead, kMgBrUndone };
+struct KfLoopMergeView {
+  int NK;
+  int *head, *rec, *branch, *kind, *ordered, *node_entry, *node_next, *ids;
+  size_t reset_bytes;  // from head: what a call resets
+};
+
 // Key-frame creation on the device (keyframe_create.hip): VisualOdometry::createNewKeyFrame
 // (visualOdometry.cpp:463-517) and the first key-frame of initVisualOdometry (:170-198) written into the store.  What
 // vo_kfstore_enable_keyframe_create allocates, one block (P = pow2_ceil(NK)): keys [P], the depth walk's sort keys when they
@@ -427,6 +445,7 @@ enum KfLayer : unsigned {
   kLayerKeyframeCreate = 1u << 8,
   kLayerLoopFuse = 1u << 9,
   kLayerLoopCorrect = 1u << 10,
+  kLayerLoopMerge = 1u << 11,
 };
 
 // The window protocol local BA and the pose graph share: a *_window call enqueues the window and notes the store's
@@ -503,6 +522,9 @@ struct vo_kfstore {
   vo::OwnedDevBuf lc;                 // vo_kfstore_enable_loop_correct: the block of section 4r
   vo::OwnedPinnedBuf lc_stage;        // the host form's Sim3 going up, the result coming down: one copy each
   vo::KfLoopCorrectView R{};
+  vo::OwnedDevBuf lm;                 // vo_kfstore_enable_loop_merge: the block of section 4s
+  vo::OwnedPinnedBuf lm_stage;        // the host form's match_ids going up, the result coming down: one copy each
+  vo::KfLoopMergeView G{};
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 
