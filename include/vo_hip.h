@@ -478,6 +478,9 @@ int vo_kfdb_set_neighbors(vo_kfdb *db, int keyframe, int n, const int32_t *ids);
 /* set_neighbors for the key-frames first .. first + count - 1 in one call (two copies, no launch per key-frame):
  * n[count] list lengths (<= 10), ids [count][10] (entries beyond n[k] are ignored). */
 int vo_kfdb_set_neighbors_batch(vo_kfdb *db, int first, int count, const int32_t *n, const int32_t *ids);
+/* The neighbour row of one key-frame as the database holds it (set_neighbors, or vo_kfstore_detect_loop's refresh): *n its
+ * length, ids [10] with -1 beyond it.  Synchronises. */
+int vo_kfdb_get_neighbors(vo_kfdb *db, int keyframe, int32_t *n, int32_t *ids /*[10]*/);
 int vo_kfdb_query_reloc(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
                         const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand, float *score_out);
 int vo_kfdb_query_reloc_dev(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,
@@ -1698,6 +1701,103 @@ int vo_kfstore_merge_loop_matches_dev(vo_kfstore *s, int curr, int n, const int3
 int vo_kfstore_merge_loop_matches_loop(vo_kfstore *s);
 int vo_kfstore_loop_merge_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *per_feature /*[max_features]*/);
 int vo_kfstore_correct_loop(vo_kfstore *s, float threshold, int max_iterations, vo_lm_summary *summary, int32_t *record /*[16], may be NULL*/);
+/* Loop detection on the device: LoopClosing::detectLoop (loopClosing.cpp:52-175) with the consistency
+ * groups, the erase locks of the loop thread (setNotEraseLoopDetectingKF / setEraseLoopDetectingKF, keyframe.cpp:541-557) and ONE
+ * iteration of LoopClosing::run (:17-37) as a composed call.  Opt-in and additive: a store without it allocates and behaves as
+ * before.  The database is the vo_kfdb whose insertion numbers are the store's.
+ * enable_detect_loop(D = max_detect_candidates, G = max_groups): valid on an EMPTY store on which vo_kfstore_enable_loop and
+ * vo_kfstore_enable_pose_graph have succeeded (the layer reads the loop edges for the lock rule and hands over to compute_sim3),
+ * with 1 <= D <= G <= VO_KFSTORE_DETECT_MAX_GROUPS; anything else VO_ERR_INVALID.  One device block of
+ *   64 + 64 + 96 + 2 up16(4 D) + up16(8 G) + 2 up16(4 K) + 16 G W + up16(8 D W) + up16(D G)   bytes,
+ *   K = max_keyframes, W = ceil(K / 64), up16(x) = x rounded up to 16:
+ * the words the calls hand on, the record, the lock record, candidates and the enough list, the groups' counters (two halves),
+ * the query's excl and conn lists, the groups as bitsets over key-frames (two halves), the candidates' bitsets and the
+ * consistency bytes.  Synchronises once.
+ * detect_loop(db, current, last_loop_keyframe): detectLoop for key-frame `current`, which the caller has inserted into db already
+ * (the reference adds a key-frame to the map before the loop thread sees it, map.cpp:224-226); the query's BoW vector is db's own
+ * row of `current`.  ENQUEUED ONLY: six launches on the store's stream (plus the four that rebuild db's index after an
+ * insertion), db's stream ordered around them by events; no host synchronisation, no device-to-host copy, no allocation.  Checked
+ * on the host before anything is enqueued, each VO_ERR_INVALID: the layer enabled, db given, current in [0, size),
+ * last_loop_keyframe >= 0, db and the store holding the same number of key-frames.  On the device, in the reference's order:
+ *  1. the erase lock of `current` is set (:59).
+ *  2. current < last_loop_keyframe + 10 (:62): GATED.  The groups are not touched; the lock is released by the rule below.
+ *  3. conn = `current`'s ordered list as the connection state holds it, without the key-frames flagged bad (:72-76), in list
+ *     order; excl = every j with W[current][j] != 0, and `current` (map.cpp:212-215).
+ *  4. min_score as vo_kfdb_query_loop computes it from conn (1.0f for an empty list).
+ *  5. db's neighbour rows are refreshed from the store: EVERY key-frame in [0, size) gets the first VO_KFSTORE_MAX_NEIGHBORS of its
+ *     ordered list (its graph row), so that getBestCovisibleKFs(10) of map.cpp:284 is the store's.  This OVERWRITES what
+ *     vo_kfdb_set_neighbors / _batch put there.  (A GATED call returns before it, as the reference does.)
+ *  6. one loop query, vo_kfdb_query_loop_dev's kernel unchanged, max_out = D.
+ *  7. no candidate (:87-93): the groups are cleared, NO_CANDIDATES, the lock is released.
+ *  8. DEVIATION: a true candidate count above D, or more than G groups in step 9: OVERFLOW, the sticky VO_KFSTORE_DETECT_CAPACITY
+ *     (vo_kfstore_connections_status), the groups are cleared, the lock is released.  The reference's vectors grow instead.
+ *  9. the consistency groups (:95-165) exactly as written: the group of candidate c is { j : W[c][j] != 0 } and c itself, bad and
+ *     erased members included (getConnectKFs filters nothing); candidates in query order, previous groups in stored order; a
+ *     candidate is CONSISTENT with a previous group when the two share a key-frame; the first candidate consistent with previous
+ *     group j pushes (its group, count of j + 1) and flags j, later ones push nothing for j (:142-147); a candidate joins the
+ *     enough list at most once, when such a count reaches 3, flagged or not (:149-153); a candidate consistent with no previous
+ *     group pushes (its group, 0) (:158-162); the new list replaces the old one (:165).
+ * 10. the enough list empty: NOT_CONSISTENT, the lock is released (:167-171).  Else DETECTED: the lock stays, and the enough list
+ *     stays on the device for compute_sim3_detected.
+ * The lock RELEASE of this block is setEraseLoopDetectingKF: the lock comes off only when the key-frame has no loop edge
+ * (vo_kfstore_add_loop_edge); nothing is erased; a released key-frame whose `pending` word is set (vo_kfstore_cull_state) is
+ * reported, and the caller calls vo_kfstore_erase_keyframe (vo_kfstore_set_erase_lock's contract).  A `current` that is erased:
+ * nothing runs, no lock is touched, outcome NONE, the sticky VO_KFSTORE_CONNECTIONS_INVALID.
+ * detect_loop_result(record, candidates, enough): synchronises; each may be NULL.  record [16] = outcome (below), current, n_excl,
+ * n_conn, min_score as its float bits (0 when the call did not get that far), the TRUE candidate count, groups before, groups
+ * after, n_enough, the lock of `current` afterwards, its pending word, 0 ...; candidates [D] and enough [D]: the first min(count, D)
+ * / n_enough entries are written.
+ * detect_loop_groups(n, counts, members): synchronises; prevConsistentGroups_ as the layer holds it: *n groups, counts [G], and
+ * members [G][size] bytes (1: the key-frame is in the group); entries beyond *n are not written.
+ * compute_sim3_detected(fix_scale, n_rand, rand_values, rand_max, max_rounds) / _dev: vo_kfstore_compute_sim3 for `current` and the
+ * enough list of the last detect_loop, read in place (the _dev form takes rand_values in device memory and is ENQUEUED only; the
+ * host form copies them up and synchronises once at its end).  It sets the erase lock of every enough candidate first (:208),
+ * enqueues the front for max_candidates of the loop layer and leaves every array a result reads byte-identical to
+ * vo_kfstore_compute_sim3 called with the same list.  Unless the last outcome is DETECTED it walks nothing, leaves the loop layer's
+ * state NO MATCH with zero candidates and raises VO_KFSTORE_CONNECTIONS_INVALID; more enough candidates than max_candidates:
+ * the same with VO_KFSTORE_LOOP_CAPACITY instead.  No detect_loop enqueued on this store yet: VO_ERR_INVALID.
+ * release_loop_locks(): ENQUEUED only, one launch.  The releases computeSim3 ends with (:290-296, :331-346), by the state of the
+ * last compute_sim3*: ACCEPTED every candidate but the matched one; NO MATCH and REJECTED every candidate and `current`;
+ * UNDECIDED none.  Each follows the release rule above.  loop_locks_result(n_released, n_pending, pending): synchronises; the
+ * number of key-frames the call released the lock of, and those of them whose pending word is set (at most
+ * VO_KFSTORE_LOOP_MAX_CANDIDATES + 1).
+ * set_ / get_last_loop_keyframe: lastLoopKFId_ of the composed step (0 on a new store, as in the reference's constructor).
+ * loop_closing_step(db, current, fix_scale, n_rand, rand_values, rand_max, max_rounds, threshold, max_iterations, summary,
+ * record): one iteration of LoopClosing::run for key-frame `current`; needs enable_detect_loop and what vo_kfstore_correct_loop
+ * needs.  A fixed sequence of this header's entry points, no kernel of its own:
+ *  1. detect_loop(db, current, the last-loop word); 2. compute_sim3_detected in its host form, without its synchronisation and
+ *  without the sticky bit for an outcome other than DETECTED (how almost every key-frame ends);
+ *  3. ONE synchronising read: the detect record and compute_sim3's state; a key-frame that ends GATED, NO_CANDIDATES,
+ *  NOT_CONSISTENT or OVERFLOW costs exactly this one synchronisation; 4. while UNDECIDED: compute_sim3_continue(max_rounds) and one
+ *  read of the state each, until it is decided or a pass adds no round (the rand() values have run out: returned as UNDECIDED, no
+ *  lock released); 5. release_loop_locks; 6. on ACCEPTED vo_kfstore_correct_loop(threshold, max_iterations, summary), and on its
+ *  success the last-loop word becomes `current` (:491).
+ * record [16] (may be NULL) = the detect outcome, compute_sim3's state (-1: not reached), correct_loop's return code (1: not
+ * reached), the step at which it stopped, n_enough, the matched key-frame or -1, continue passes, the last-loop word afterwards,
+ * 0 ...  Returns the first failing entry point's code (OVERFLOW: VO_ERR_CAPACITY; an erased `current`: VO_ERR_INVALID), else
+ * VO_OK; the arguments are checked before anything is enqueued (more rand() values than max_rand: VO_ERR_CAPACITY). */
+#define VO_KFSTORE_DETECT_CAPACITY 512
+#define VO_KFSTORE_DETECT_MAX_GROUPS 1024
+#define VO_KFSTORE_DETECT_NONE 0
+#define VO_KFSTORE_DETECT_GATED 1
+#define VO_KFSTORE_DETECT_NO_CANDIDATES 2
+#define VO_KFSTORE_DETECT_NOT_CONSISTENT 3
+#define VO_KFSTORE_DETECT_DETECTED 4
+#define VO_KFSTORE_DETECT_OVERFLOW 5
+int vo_kfstore_enable_detect_loop(vo_kfstore *s, int max_detect_candidates, int max_groups);
+int vo_kfstore_detect_loop(vo_kfstore *s, vo_kfdb *db, int current, int last_loop_keyframe);
+int vo_kfstore_detect_loop_result(vo_kfstore *s, int32_t *record /*[16]*/, int32_t *candidates /*[D]*/, int32_t *enough /*[D]*/);
+int vo_kfstore_detect_loop_groups(vo_kfstore *s, int32_t *n, int32_t *counts /*[G]*/, uint8_t *members /*[G][size]*/);
+int vo_kfstore_compute_sim3_detected(vo_kfstore *s, int fix_scale, int n_rand, const int32_t *rand_values, int32_t rand_max, int max_rounds);
+int vo_kfstore_compute_sim3_detected_dev(vo_kfstore *s, int fix_scale, int n_rand, const int32_t *dev_rand_values, int32_t rand_max,
+                                         int max_rounds);
+int vo_kfstore_release_loop_locks(vo_kfstore *s);
+int vo_kfstore_loop_locks_result(vo_kfstore *s, int32_t *n_released, int32_t *n_pending, int32_t *pending /*[17]*/);
+int vo_kfstore_set_last_loop_keyframe(vo_kfstore *s, int keyframe);
+int vo_kfstore_get_last_loop_keyframe(vo_kfstore *s, int32_t *keyframe);
+int vo_kfstore_loop_closing_step(vo_kfstore *s, vo_kfdb *db, int current, int fix_scale, int n_rand, const int32_t *rand_values,
+                                 int32_t rand_max, int max_rounds, float threshold, int max_iterations, vo_lm_summary *summary,
+                                 int32_t *record /*[16], may be NULL*/);
 /* Key-frame creation on the device: a tracked frame written into the store as a key-frame --
  * VisualOdometry::createNewKeyFrame (visualOdometry.cpp:463-517) with cullingTempMapPoints' slot rule (:844-853), and the first
  * key-frame of initVisualOdometry (:170-198) -- for a caller who keeps no host copy of ids or flags: the link between "frame

@@ -82,6 +82,10 @@ SYMBOLS = [
     "vo_kfstore_loop_connections", "vo_kfstore_loop_correct_result", "vo_kfstore_loop_correct_arrays",
     "vo_kfstore_enable_loop_merge", "vo_kfstore_merge_loop_matches", "vo_kfstore_merge_loop_matches_dev",
     "vo_kfstore_merge_loop_matches_loop", "vo_kfstore_loop_merge_result", "vo_kfstore_correct_loop",
+    "vo_kfstore_enable_detect_loop", "vo_kfstore_detect_loop", "vo_kfstore_detect_loop_result", "vo_kfstore_detect_loop_groups",
+    "vo_kfstore_compute_sim3_detected", "vo_kfstore_compute_sim3_detected_dev", "vo_kfstore_release_loop_locks",
+    "vo_kfstore_loop_locks_result", "vo_kfstore_set_last_loop_keyframe", "vo_kfstore_get_last_loop_keyframe",
+    "vo_kfstore_loop_closing_step", "vo_kfdb_get_neighbors",
     "vo_tracker_create", "vo_tracker_destroy", "vo_tracker_info", "vo_tracker_extractor", "vo_tracker_frames",
     "vo_tracker_stream", "vo_tracker_set_last_frame", "vo_tracker_set_local_map", "vo_tracker_track_dev", "vo_tracker_track",
     "vo_tracker_results", "vo_tracker_get", "vo_tracker_sync", "vo_tracker_set_timing", "vo_tracker_get_timing",
@@ -1521,6 +1525,12 @@ class KeyFrameDatabase:
             ids[k, :len(x)] = x
         check(lib().vo_kfdb_set_neighbors_batch(self._h, int(first), len(lists), _p(n), _p(ids)), "vo_kfdb_set_neighbors_batch")
 
+    def neighbors(self, keyframe):
+        """the neighbour row of a key-frame as the database holds it -> list; synchronises"""
+        n, ids = C.c_int32(0), np.full(10, -1, np.int32)
+        check(lib().vo_kfdb_get_neighbors(self._h, int(keyframe), C.byref(n), _p(ids)), "vo_kfdb_get_neighbors")
+        return [int(x) for x in ids[:n.value]]
+
     def _unpack(self, rc, what, n_cand, cand, score, want_scores, max_out):
         if rc == -4 and max_out >= 0:  # VO_ERR_CAPACITY: n_cand still holds the true counts
             raise VoError(f"{what} failed with status {rc}: {lib().vo_last_error().decode()}", n_cand)
@@ -2226,6 +2236,86 @@ class KeyFrameStore:
         self.correct_loop_record = {k: int(rec[i]) for i, k in enumerate(self.CL_RECORD)}
         check(rc, "vo_kfstore_correct_loop")
         return s, self.correct_loop_record
+
+    CONNECTIONS_DETECT_CAPACITY = 512
+    DETECT_MAX_GROUPS = 1024
+    DETECT_NONE, DETECT_GATED, DETECT_NO_CANDIDATES, DETECT_NOT_CONSISTENT, DETECT_DETECTED, DETECT_OVERFLOW = range(6)
+    DL_RECORD = ("outcome", "current", "n_excl", "n_conn", "min_score_bits", "n_candidates", "groups_before", "groups_after", "n_enough",
+                 "locked", "pending")
+    LCS_RECORD = ("outcome", "state", "correct_loop", "stopped_at", "n_enough", "match", "continue_passes", "last_loop_keyframe")
+
+    def enable_detect_loop(self, max_detect_candidates, max_groups):
+        """LoopClosing::detectLoop with its consistency groups, the loop thread's erase locks and the composed loop_closing_step
+        on the device from now on; valid on an empty store after enable_loop and enable_pose_graph only"""
+        check(lib().vo_kfstore_enable_detect_loop(self._h, int(max_detect_candidates), int(max_groups)), "vo_kfstore_enable_detect_loop")
+        self._dl_caps = (int(max_detect_candidates), int(max_groups))
+
+    def detect_loop(self, db, current, last_loop_keyframe=0):
+        """detectLoop for key-frame `current`, which db (a KeyFrameDatabase with the store's numbering) holds already; enqueued
+        only.  db's neighbour rows are overwritten from the store's graph rows"""
+        check(lib().vo_kfstore_detect_loop(self._h, db._h, int(current), int(last_loop_keyframe)), "vo_kfstore_detect_loop")
+
+    def detect_loop_result(self):
+        """the last detect_loop -> dict over DL_RECORD plus min_score (float32), candidates and enough (lists); synchronises"""
+        D, _ = getattr(self, "_dl_caps", (1, 1))
+        rec, cand, en = np.zeros(16, np.int32), np.full(D, -1, np.int32), np.full(D, -1, np.int32)
+        check(lib().vo_kfstore_detect_loop_result(self._h, _p(rec), _p(cand), _p(en)), "vo_kfstore_detect_loop_result")
+        out = {k: int(rec[i]) for i, k in enumerate(self.DL_RECORD)}
+        out.update(min_score=rec[4:5].view(np.float32)[0], candidates=[int(x) for x in cand[:min(max(out["n_candidates"], 0), D)]],
+                   enough=[int(x) for x in en[:min(max(out["n_enough"], 0), D)]])
+        return out
+
+    def detect_loop_groups(self):
+        """prevConsistentGroups_ as the layer holds it -> (counts list, members uint8 [n, size]); synchronises"""
+        _, G = getattr(self, "_dl_caps", (1, 1))
+        size = len(self)
+        n, counts, members = C.c_int32(0), np.zeros(G, np.int32), np.zeros((G, max(size, 1)), np.uint8)
+        check(lib().vo_kfstore_detect_loop_groups(self._h, C.byref(n), _p(counts), _p(members)), "vo_kfstore_detect_loop_groups")
+        return [int(x) for x in counts[:n.value]], members.reshape(-1)[:n.value * size].reshape(n.value, size).copy()
+
+    def compute_sim3_detected(self, rand_values, rand_max, fix_scale=True, max_rounds=8):
+        """compute_sim3 for `current` and the enough list of the last detect_loop, read in place.  A list / numpy array of rand()
+        values is copied and the call synchronises once; a device tensor (int32) is enqueued only"""
+        if hasattr(rand_values, "data_ptr"):
+            _need_tensor(rand_values, "int32", None, "compute_sim3_detected")
+            check(lib().vo_kfstore_compute_sim3_detected_dev(self._h, int(bool(fix_scale)), int(rand_values.numel()), _p(rand_values),
+                                                             int(rand_max), int(max_rounds)), "vo_kfstore_compute_sim3_detected_dev")
+            return
+        r = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+        check(lib().vo_kfstore_compute_sim3_detected(self._h, int(bool(fix_scale)), len(r), _p(r), int(rand_max), int(max_rounds)),
+              "vo_kfstore_compute_sim3_detected")
+
+    def release_loop_locks(self):
+        """computeSim3's lock releases by the state the last compute_sim3 ended in; enqueued only"""
+        check(lib().vo_kfstore_release_loop_locks(self._h), "vo_kfstore_release_loop_locks")
+
+    def loop_locks_result(self):
+        """the last release_loop_locks -> (n_released, [released key-frames whose pending word is set]); synchronises"""
+        nr, npend, pend = C.c_int32(0), C.c_int32(0), np.full(17, -1, np.int32)
+        check(lib().vo_kfstore_loop_locks_result(self._h, C.byref(nr), C.byref(npend), _p(pend)), "vo_kfstore_loop_locks_result")
+        return int(nr.value), [int(x) for x in pend[:npend.value]]
+
+    @property
+    def last_loop_keyframe(self):
+        k = C.c_int32(0)
+        check(lib().vo_kfstore_get_last_loop_keyframe(self._h, C.byref(k)), "vo_kfstore_get_last_loop_keyframe")
+        return int(k.value)
+
+    @last_loop_keyframe.setter
+    def last_loop_keyframe(self, keyframe):
+        check(lib().vo_kfstore_set_last_loop_keyframe(self._h, int(keyframe)), "vo_kfstore_set_last_loop_keyframe")
+
+    def loop_closing_step(self, db, current, rand_values, rand_max, fix_scale=True, max_rounds=8, threshold=4.0, max_iterations=20):
+        """one iteration of LoopClosing::run for key-frame `current`: detect_loop, compute_sim3_detected, ONE read, more rounds
+        while undecided, release_loop_locks and, on an accepted loop, correct_loop -> (summary, record: dict over LCS_RECORD).  A
+        refusal raises; self.loop_closing_record then holds the record"""
+        r = np.ascontiguousarray(rand_values, np.int32).reshape(-1)
+        s, rec = LmSummary(), np.zeros(16, np.int32)
+        rc = lib().vo_kfstore_loop_closing_step(self._h, db._h, int(current), int(bool(fix_scale)), len(r), _p(r), int(rand_max),
+                                                int(max_rounds), C.c_float(threshold), int(max_iterations), C.byref(s), _p(rec))
+        self.loop_closing_record = {k: int(rec[i]) for i, k in enumerate(self.LCS_RECORD)}
+        check(rc, "vo_kfstore_loop_closing_step")
+        return s, self.loop_closing_record
 
     KC_RECORD = ("keyframe", "n", "n_pairs", "n_walked", "n_created", "n_tracked", "first_id", "next_id", "ended_early", "status")
     _KC_COLUMNS = (("x", "float32"), ("y", "float32"), ("octave", "int32"), ("angle", "float32"), ("depth", "float32"), ("u_right", "float32"))

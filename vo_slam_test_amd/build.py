@@ -49,6 +49,7 @@ SOURCES = [
     ("loop_fuse.hip", ["-ffp-contract=off"]),
     ("loop_correct.hip", ["-ffp-contract=off"]),
     ("loop_merge.hip", ["-ffp-contract=off"]),
+    ("detect_loop.hip", ["-ffp-contract=off"]),
     ("dataset_io.cpp", []),
 ]
 COMMON = ["-O3", "-std=c++17", f"--offload-arch={ARCH}", "-fPIC", "-Wall", "-Wno-unused-function"]

@@ -383,6 +383,32 @@ __global__ __launch_bounds__(256) void k_kfdb_query(QueryArgs a) {
   if (tid == 0) a.n_cand[q] = s_run;  // the true count, also beyond max_out
 }
 
+// LoopClosing::detectLoop's minScore (loopClosing.cpp:71-83) for ONE query whose vector is a row of the database: the float minimum
+// of wave_score over the connected key-frames, 1.0f for an empty list -- what k_kfdb_query<true> computes from `conn` when no
+// min_score is given (a minimum does not depend on the order it is taken in).  One workgroup, a wave per connected key-frame.
+__global__ __launch_bounds__(256) void k_kfdb_min_score(int size, int stride, const int *kf_start, const int *kf_words, const double *kf_vals,
+                                                        const int *q_start, const int *conn_start, const int *conn, float *out) {
+  __shared__ float s_m[4];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int qb = q_start[0], nq = max(q_start[1] - qb, 0);
+  const int cb = conn_start[0], nc = min(max(conn_start[1] - cb, 0), stride);
+  float m = 1.0f;
+  for (int c = wave; c < nc; c += 4) {
+    const int k = conn[cb + c];
+    if (k < 0 || k >= size) continue;  // (uniform in the wave)
+    const int kb = kf_start[k];
+    const float v = (float)wave_score(kf_words + qb, kf_vals + qb, nq, kf_words + kb, kf_vals + kb, kf_start[k + 1] - kb);
+    if (v < m) m = v;
+  }
+  if (lane == 0) s_m[wave] = m;
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 1; w < 4; w++)
+      if (s_m[w] < m) m = s_m[w];
+    out[0] = m;
+  }
+}
+
 }  // namespace
 
 struct vo_kfdb {
@@ -598,6 +624,46 @@ int vo::kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const in
   return VO_OK;
 }
 
+// ---- the loop query of one key-frame on a caller's stream (the store's: detect_loop.hip)
+vo::KfdbDevView vo::kfdb_dev_view(const vo_kfdb *db) {
+  return vo::KfdbDevView{db->size, db->max_kf, db->kf_start.as<int>(), db->nbr_n.as<int>(), db->nbr.as<int>()};
+}
+
+int vo::kfdb_order_before(vo_kfdb *db, hipStream_t st) {
+  if (!db) return VO_ERR_INVALID;
+  if (db->st == st) return VO_OK;
+  if (!db->ev_in) VO_HIP_CHECK(hipEventCreateWithFlags(&db->ev_in, hipEventDisableTiming));
+  VO_HIP_CHECK(hipEventRecord(db->ev_in, db->st));
+  VO_HIP_CHECK(hipStreamWaitEvent(st, db->ev_in, 0));
+  return VO_OK;
+}
+
+int vo::kfdb_query_loop_on(vo_kfdb *db, hipStream_t st, const int32_t *dev_q_start, const int32_t *dev_excl_start, const int32_t *dev_excl,
+                           const int32_t *dev_conn_start, const int32_t *dev_conn, float *dev_min_score, int max_out, int32_t *n_cand,
+                           int32_t *cand) {
+  if (!db || !dev_q_start || !dev_excl_start || !dev_excl || !dev_conn_start || !dev_conn || !dev_min_score) return VO_ERR_INVALID;
+  hipStream_t own = db->st;
+  VO_CHECK(kfdb_order_before(db, st));
+  db->st = st;  // (the rebuild and the query launch read the handle's stream)
+  int rc = kfdb_rebuild(db);
+  if (rc == VO_OK) {
+    hipLaunchKernelGGL(k_kfdb_min_score, dim3(1), dim3(256), 0, st, db->size, db->max_kf, db->kf_start.as<int>(), db->kf_words.as<int>(),
+                       db->kf_vals.as<double>(), dev_q_start, dev_conn_start, dev_conn, dev_min_score);
+    if (hipGetLastError() != hipSuccess) rc = VO_ERR_HIP;
+  }
+  if (rc == VO_OK)
+    rc = kfdb_query_dev(db, true, 1, dev_q_start, db->kf_words.as<int>(), db->kf_vals.as<double>(), nullptr, dev_excl_start, dev_excl,
+                        dev_min_score, nullptr, nullptr, max_out, n_cand, cand, nullptr, "vo_kfstore_detect_loop");
+  db->st = own;
+  VO_CHECK(rc);
+  if (own != st) {
+    if (!db->ev_out) VO_HIP_CHECK(hipEventCreateWithFlags(&db->ev_out, hipEventDisableTiming));
+    VO_HIP_CHECK(hipEventRecord(db->ev_out, st));
+    VO_HIP_CHECK(hipStreamWaitEvent(own, db->ev_out, 0));
+  }
+  return VO_OK;
+}
+
 extern "C" {
 
 int vo_bow_vector_dev(int n_frames, int n_features, const int32_t *dev_feat_start, const int32_t *dev_word, const double *dev_weight,
@@ -780,6 +846,14 @@ int vo_kfdb_set_neighbors_batch(vo_kfdb *db, int first, int count, const int32_t
   VO_CHECK(vo::copy_h2d(db->nbr_n.as<int>() + first, n, (size_t)count * 4, db->st, W));
   VO_CHECK(vo::copy_h2d(db->nbr.as<int>() + (size_t)first * kMaxNbr, rows.data(), rows.size() * 4, db->st, W));
   return vo::stream_sync(db->st, W);  // (rows is a local: the copies must have read it)
+}
+
+int vo_kfdb_get_neighbors(vo_kfdb *db, int keyframe, int32_t *n, int32_t *ids) {
+  const char *W = "vo_kfdb_get_neighbors";
+  if (!db || keyframe < 0 || keyframe >= db->size || !n || !ids) return VO_ERR_INVALID;
+  VO_CHECK(vo::copy_d2h(n, db->nbr_n.as<int>() + keyframe, 4, db->st, W));
+  VO_CHECK(vo::copy_d2h(ids, db->nbr.as<int>() + (size_t)keyframe * kMaxNbr, kMaxNbr * 4, db->st, W));
+  return vo::stream_sync(db->st, W);
 }
 
 int vo_kfdb_query_reloc(vo_kfdb *db, int n_queries, const int32_t *q_start, const int32_t *q_words, const double *q_values,

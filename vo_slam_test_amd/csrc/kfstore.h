@@ -1,4 +1,4 @@
-// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4s; not part of the C-ABI): the
+// kfstore.h -- the key-frame feature store as its own files see it (DESIGN.md sections 4f-4t; not part of the C-ABI): the
 // kernel-argument views of the store and of its opt-in layers, the functions a layer's file shares with another file, the
 // handle itself, and the guards every entry point starts with.  Included by kfstore.hip, by the layer files and by the
 // store's readers (match.hip, reloc.hip, tracker.hip, local_map.hip).
@@ -365,6 +365,36 @@ struct KfLoopMergeView {
   size_t reset_bytes;  // from head: what a call resets
 };
 
+// Loop detection from the store (detect_loop.hip): LoopClosing::detectLoop (loopClosing.cpp:52-175) with
+// its consistency groups, the erase locks of the loop thread (keyframe.cpp:541-557) and the composed loop-closing step.  What
+// vo_kfstore_enable_detect_loop allocates, one block (D = max_detect_candidates, G = max_groups, words = ceil(max_kf / 64)):
+// head [kDlHeadInts] (enum below: what carries over between calls -- the live half and its group count -- and what one call's
+// kernels hand to each other, among it the three CSR pairs and the candidate count k_kfdb_query reads and writes); rec
+// [kDlRecInts], the record (enum below); lrec [kDlLockInts], release_loop_locks' record: (n released, n pending, state, 0 |
+// the pending key-frames); cand [D], the query's candidates; enough [D], enoughConCandidates_; counts [2][G], the groups'
+// counters of either half; excl [max_kf], conn [max_kf], the query's lists; bits [2][G][words], the groups as bitsets over
+// key-frames, ping-pong between the halves; cbits [D][words], the candidates' groups; consist [D][G] bytes.
+constexpr int kDlHeadInts = 16, kDlRecInts = 16, kDlLockInts = 4 + VO_KFSTORE_LOOP_MAX_CANDIDATES + 4, kDlMaxGroups = VO_KFSTORE_DETECT_MAX_GROUPS;
+enum { kDhRun = 0, kDhHalf, kDhNGroups, kDhNCand, kDhQStart, kDhExclStart = 6, kDhConnStart = 8, kDhMinScore = 10, kDhNEnough };
+enum { kDlOutcome = 0, kDlCurrent, kDlNExcl, kDlNConn, kDlMinScore, kDlNCand, kDlGroupsBefore, kDlGroupsAfter, kDlNEnough, kDlLocked,
+       kDlPending };
+enum { kDkReleased = 0, kDkNPending, kDkState, kDkList = 4 };
+struct KfDetectView {
+  int D, G, max_kf, words;
+  int *head, *rec, *lrec, *cand, *enough, *counts, *excl, *conn;
+  unsigned long long *bits, *cbits;
+  uint8_t *consist;
+};
+// compute_sim3 for a candidate list whose length only the device knows (loop_sim3.hip): the candidates are src[0 .. *dev_n) when
+// *dev_go == go_value, else none; k_loop_begin_counted copies them into the block, sets their erase locks (loopClosing.cpp:208)
+// and writes the count; the front and the construction are enqueued for max_candidates, and k_loop_trim puts the rows beyond
+// the count back to what k_loop_begin left, so that everything a result reads is compute_sim3's for the same list.  No list
+// (the sticky VO_KFSTORE_CONNECTIONS_INVALID) or more than max_candidates entries (the sticky VO_KFSTORE_LOOP_CAPACITY): nothing is
+// walked and the state is NO MATCH with zero candidates (quiet: "no list" raises nothing -- the composed step, for which that is
+// how almost every key-frame ends).  Launches and a memset only.
+int loop_compute_counted(vo_kfstore *s, int current, const int *dev_go, int go_value, const int *dev_n, const int *dev_src, int fix_scale,
+                         int n_rand, int32_t rand_max, int max_rounds, bool quiet = false);
+
 // Key-frame creation on the device (keyframe_create.hip): VisualOdometry::createNewKeyFrame
 // (visualOdometry.cpp:463-517) and the first key-frame of initVisualOdometry (:170-198) written into the store.  What
 // vo_kfstore_enable_keyframe_create allocates, one block (P = pow2_ceil(NK)): keys [P], the depth walk's sort keys when they
@@ -446,6 +476,7 @@ enum KfLayer : unsigned {
   kLayerLoopFuse = 1u << 9,
   kLayerLoopCorrect = 1u << 10,
   kLayerLoopMerge = 1u << 11,
+  kLayerDetectLoop = 1u << 12,
 };
 
 // The window protocol local BA and the pose graph share: a *_window call enqueues the window and notes the store's
@@ -525,6 +556,11 @@ struct vo_kfstore {
   vo::OwnedDevBuf lm;                 // vo_kfstore_enable_loop_merge: the block of section 4s
   vo::OwnedPinnedBuf lm_stage;        // the host form's match_ids going up, the result coming down: one copy each
   vo::KfLoopMergeView G{};
+  vo::OwnedDevBuf dl;                 // vo_kfstore_enable_detect_loop: the block of section 4t
+  vo::OwnedPinnedBuf dl_stage;        // a result coming down, the composed step's one read
+  vo::KfDetectView Dv{};
+  int dl_current = -1;                // `current` of the last detect_loop (-1: none yet): what compute_sim3_detected walks for
+  int last_loop_kf = 0;               // lastLoopKFId_ (loopClosing.cpp:13, :491) of the composed step
   uint8_t *record(int k) const { return rec.as<uint8_t>() + (size_t)k * V.rec; }
 };
 

@@ -129,7 +129,7 @@ int kfstore_obs_view(vo_kfstore *s, KfObsView *out) {
 
 int need(const vo_kfstore *s, const char *W, unsigned layers) {
   static const char *const kEnable[] = {"connections", "culling", "mapping", "local_ba", "point_upkeep", "fuse", "loop", "pose_graph",
-                                        "keyframe_create", "loop_fuse", "loop_correct", "loop_merge"};
+                                        "keyframe_create", "loop_fuse", "loop_correct", "loop_merge", "detect_loop"};
   if (!s) return VO_ERR_INVALID;
   const unsigned missing = layers & ~s->layers;
   if (!missing) return VO_OK;

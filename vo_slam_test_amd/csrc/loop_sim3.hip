@@ -103,8 +103,7 @@ __device__ __forceinline__ int block_rank(bool keep, int *s_wave /*[16]*/, int &
 }
 
 // ---- a new call
-__global__ void k_loop_begin(LoopArgs A, int current, int n_cand, int fix_scale, int n_rand, int rand_max) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+__device__ void loop_begin(const LoopArgs &A, int current, int n_cand, int fix_scale, int n_rand, int rand_max) {
   int *st = A.L.st;
   for (int i = 0; i < kLoopStateInts; i++) st[i] = 0;
   st[kLsMatchPos] = st[kLsMatchKf] = -1;
@@ -117,6 +116,41 @@ __global__ void k_loop_begin(LoopArgs A, int current, int n_cand, int fix_scale,
   A.L.off[0] = A.L.off[1] = 0;
   for (int i = 0; i < VO_KFSTORE_LOOP_MAX_CANDIDATES * kLoopPerInts; i++) A.L.per[i] = 0;
   for (int i = 0; i < 13; i++) A.L.Scm[i] = A.L.Scw[i] = 0.0;
+}
+__global__ void k_loop_begin(LoopArgs A, int current, int n_cand, int fix_scale, int n_rand, int rand_max) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  loop_begin(A, current, n_cand, fix_scale, n_rand, rand_max);
+}
+
+// k_loop_begin for a list and a count only the device knows (kfstore.h: loop_compute_counted): the candidates copied into the
+// block (-1 beyond the count, as the host form's copy leaves them), their erase locks set (loopClosing.cpp:208), the count
+// written.  No list or too long a list: the state of a call that found nothing, and no walk.
+__global__ void k_loop_begin_counted(LoopArgs A, int current, const int *go, int go_value, const int *n_src, const int *src, int fix_scale,
+                                     int n_rand, int rand_max, int quiet) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const bool has = go[0] == go_value;
+  int n = has ? max(n_src[0], 0) : 0;
+  const bool fits = n <= A.L.C;
+  if (!fits) n = 0;
+  for (int c = 0; c < VO_KFSTORE_LOOP_MAX_CANDIDATES; c++) A.L.cand[c] = c < n ? src[c] : -1;
+  loop_begin(A, current, n, fix_scale, n_rand, rand_max);
+  if (n == 0) {
+    A.L.st[kLsState] = VO_KFSTORE_LOOP_NO_MATCH, A.L.st[kLsPhase] = kLoopDone;
+    if (!fits) atomicOr(A.status, VO_KFSTORE_LOOP_CAPACITY);
+    else if (!quiet) atomicOr(A.status, VO_KFSTORE_CONNECTIONS_INVALID);
+  }
+  for (int c = 0; c < n; c++) {
+    const int kf = A.L.cand[c];
+    if (kf >= 0 && kf < A.S.size) A.X.locked[kf] = 1;
+  }
+}
+
+// behind k_loop_construct in the counted form: the front ran for max_candidates; the rows beyond the count go back to what
+// k_loop_begin left (the walk reads none of them)
+__global__ void k_loop_trim(LoopArgs A) {
+  const int c = threadIdx.x;
+  if (c >= VO_KFSTORE_LOOP_MAX_CANDIDATES || c < min(max(A.L.st[kLsNCand], 0), A.L.C)) return;
+  for (int i = 0; i < kLoopPerInts; i++) A.L.per[c * kLoopPerInts + i] = 0;
 }
 
 // ---- the discards (:210-222) and Sim3Solver's constructor (sim3Solver.cpp:8-96)
@@ -783,6 +817,24 @@ int loop_check(vo_kfstore *s, const char *W, int n_cand, const void *cand, int n
 }
 
 }  // namespace
+
+int vo::loop_compute_counted(vo_kfstore *s, int current, const int *dev_go, int go_value, const int *dev_n, const int *dev_src, int fix_scale,
+                             int n_rand, int32_t rand_max, int max_rounds, bool quiet) {
+  KfObsView O;
+  VO_CHECK(kfstore_obs_view(s, &O));
+  const LoopArgs A = loop_args(s, O);
+  hipStream_t st = s->st;
+  VO_HIP_CHECK(hipMemsetAsync(A.L.match_ids, 0xff, (size_t)A.L.NK * 4, st));
+  hipLaunchKernelGGL(k_loop_begin_counted, dim3(1), dim3(64), 0, st, A, current, dev_go, go_value, dev_n, dev_src, fix_scale ? 1 : 0, n_rand,
+                     rand_max, quiet ? 1 : 0);
+  VO_HIP_CHECK(hipGetLastError());
+  VO_CHECK(loop_bow_replay(A, current, A.L.C, st));
+  hipLaunchKernelGGL(k_loop_construct, dim3((unsigned)A.L.C), dim3(256), 0, st, A);
+  hipLaunchKernelGGL(k_loop_trim, dim3(1), dim3(64), 0, st, A);
+  VO_HIP_CHECK(hipGetLastError());
+  s->loop_fix_scale = fix_scale ? 1 : 0, s->loop_called = true;
+  return loop_rounds_enqueue(A, max_rounds, s->loop_fix_scale, st);
+}
 
 extern "C" {
 

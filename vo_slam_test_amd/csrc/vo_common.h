@@ -293,6 +293,21 @@ int sim3_solve_dev(int n_problems, int fix_scale, const int *off, const double *
 void kfdb_info(const vo_kfdb *db, int *size, int *max_batch);
 int kfdb_query_reloc_on(vo_kfdb *db, hipStream_t st, int n_queries, const int32_t *q_start, const int32_t *q_words,
                         const double *q_values, const float *stale_score, int max_out, int32_t *n_cand, int32_t *cand);
+// The loop query of ONE key-frame of the database on a stream of the caller's (the store's: detect_loop.hip), ordered the same
+// way.  The query's BoW vector is a row of the database itself: dev_q_start [2] = (kf_start[k], kf_start[k + 1]), or an empty
+// pair for "no query".  k_kfdb_min_score writes detectLoop's minScore over dev_conn to dev_min_score [1] (1.0f for an empty
+// list), and k_kfdb_query takes it from there.  kfdb_dev_view: the rows a store kernel reads (kf_start) or refreshes (the
+// neighbour rows); kfdb_order_before makes `st` wait for what the database's stream holds now.
+struct KfdbDevView {
+  int size, max_kf;
+  const int *kf_start;
+  int *nbr_n, *nbr;
+};
+KfdbDevView kfdb_dev_view(const vo_kfdb *db);
+int kfdb_order_before(vo_kfdb *db, hipStream_t st);
+int kfdb_query_loop_on(vo_kfdb *db, hipStream_t st, const int32_t *dev_q_start, const int32_t *dev_excl_start, const int32_t *dev_excl,
+                       const int32_t *dev_conn_start, const int32_t *dev_conn, float *dev_min_score, int max_out, int32_t *n_cand,
+                       int32_t *cand);
 
 // ---- searchByBoW against key-frames of a store with the common-node walk on the device (match.hip): k_bow_transform and
 // k_featvec build every resident frame's FeatureVector; k_bow_walk writes every (frame, candidate) pair's query list and
