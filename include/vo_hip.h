@@ -2021,11 +2021,84 @@ enum {
   VO_TRACKER_LOCAL_DESC = 32,        /* uint8 [..][32] */
   VO_TRACKER_LOCAL_MAP_FLAGS = 33,   /* uint8: the flags as set / built (VO_TRACKER_LOCAL_FLAGS: after isInFrame) */
   VO_TRACKER_LOCAL_LINK = 34,        /* int32 */
-  VO_TRACKER_POSE_START = 35         /* double [batch][6]: the se3 the route's first solve started from: log of the Tcw given
+  VO_TRACKER_POSE_START = 35,        /* double [batch][6]: the se3 the route's first solve started from: log of the Tcw given
                                         (vo_tracker_set_last_frame, vo_tracker_set_ref_keyframe, and computed on the device
-                                        by vo_tracker_track_ref_keyframe_store) */
+                                        by vo_tracker_track_ref_keyframe_store and vo_tracker_begin_frame) */
+  /* the hand-over (vo_tracker_end_frame / vo_tracker_begin_frame below) */
+  VO_TRACKER_SLOT_IDS = 36,          /* int32 [batch][max_features]: id of frame->mappoints_[i] after cullingTempMapPoints, -1 = null */
+  VO_TRACKER_SLOT_DESC = 37,         /* uint8 [batch][max_features][32]: that map point's descriptor (zeros: null) */
+  VO_TRACKER_FRAME_POSE = 38,        /* double [batch][12]: R, t of exp(pose) of the frame handed over */
+  VO_TRACKER_VELOCITY = 39,          /* double [batch][12]: Tcl_ */
+  VO_TRACKER_MOTION_STATE = 40,      /* int32 [batch]: motionModel_ */
+  VO_TRACKER_TEMP_COUNT = 41,        /* int32 [batch]: updateLastFrame's temporary points (C_J) */
+  /* the last-frame list as it stands ([batch][max_last]; set by vo_tracker_set_last_frame / _ids or handed over) */
+  VO_TRACKER_LAST_POINTS = 42,       /* double [..][3] */
+  VO_TRACKER_LAST_FLAGS = 43,        /* uint8 */
+  VO_TRACKER_LAST_OCTAVE = 44,       /* int32 */
+  VO_TRACKER_LAST_ANGLE = 45,        /* float */
+  VO_TRACKER_LAST_DESC = 46,         /* uint8 [..][32] */
+  VO_TRACKER_LAST_IDS = 47,          /* int32: map-point id per entry, -1 = none */
+  VO_TRACKER_LAST_N = 48,            /* int32 [1]: the list's n */
+  VO_TRACKER_TCW_START = 49          /* double [batch][12]: the pose the last-frame points are projected with (Tcw12 of
+                                        vo_tracker_set_last_frame / _ref_keyframe, or VELOCITY * last pose of vo_tracker_begin_frame) */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
+/* frame_last_ = frame_curr_ on the device: what VisualOdometry::run does between two frames
+ * (visualOdometry.cpp:80-128) and the preamble of trackWithMotion (:233-236), for every frame of the batch, so that
+ * vo_tracker_track*_dev follows vo_tracker_track*_dev with nothing but launches in between.  The calls produce, on the device,
+ * the arrays vo_tracker_set_last_frame fills from the host; no existing array moves.  Their own state is ONE device block,
+ * allocated by the first call of any of the five functions below:
+ *   slot ids 4 BF, slot descriptors 32 BF, slot flags BF, last ids 4 BL, three poses 3 x 96 B (+ B validity bytes), two counts
+ *   2 x 4 B, and 8 BP sort keys only where P > 4096    (B = batch, F = max_features, L = max_last, P = the power of two >= F;
+ *   every array rounded up to 4 KiB).
+ * vo_tracker_set_last_frame_ids(n, ids [batch][n]): the map-point id of every entry of the last-frame list, negative = none; the
+ * last-frame counterpart of vo_tracker_set_local_map_ids.  n must be the list's n (else VO_ERR_INVALID); the ids belong to the
+ * list they were set for (vo_tracker_set_last_frame, vo_tracker_set_ref_keyframe and the store form of trackRefKeyFrame forget
+ * them).  One copy, one synchronisation.
+ * vo_tracker_set_last_pose(Tcw12 [batch][12], valid [batch]): frame_last_->Tcw_ and poseExist_ per frame -- the seed of the
+ * motion model, and how a caller applies the local-BA refresh of :547-549.  One copy, one synchronisation.
+ * vo_tracker_end_frame(p): :80-128.  Valid after vo_tracker_track[_dev] and vo_tracker_track_first[_dev], with or without
+ * vo_tracker_track_local_map behind it; after any other route, or before any, VO_ERR_INVALID; max_features > max_last
+ * VO_ERR_CAPACITY; in both cases nothing is enqueued and nothing changes.  ENQUEUED on the tracker's stream, one workgroup per
+ * frame: no host synchronisation, no device-to-host copy, no allocation after the first call.  Per frame, slot i < n:
+ *  1 the slot's source: VO_TRACKER_ASSIGNED_LOCAL[i] >= 0 -> that local point (id: vo_tracker_set_local_map_ids' or -1; the local
+ *    point's descriptor); else VO_TRACKER_ASSIGNED_LAST[i] >= 0 and the slot non-null -> that last-frame entry (id: the last id or
+ *    -1; that entry's descriptor); else null.  observed = the tracker's per-slot mark (bit 1 of the source's flags); outlier =
+ *    VO_TRACKER_FEATURE_OUTLIER, 0 when the local-map stage did not run (the first stage has nulled its outliers already).
+ *  2 cullingTempMapPoints (:844-853): a non-null slot without the observed mark becomes null, its outlier flag 0.  SLOT_IDS,
+ *    SLOT_DESC are the slots as they stand now -- as the reference has them at createNewKeyFrame, BEFORE cullingOutliersOfFrame:
+ *    what vo_kfstore_create_keyframe*'s dev_slot_ids asks for.  The tracker's own per-slot arrays are not written.
+ *  3 ok = status == 0 && n_tracked >= min_tracked (<= 0: 30, :310; the 50 of :307 is the caller's through min_tracked).
+ *  4 FRAME_POSE = R, t of exp(pose) (the arithmetic of vo_se3_exp).  ok and the last pose valid: VELOCITY = FRAME_POSE *
+ *    last pose^-1 (csrc/handover_geom.h's operation order), MOTION_STATE = 1; else VELOCITY = identity, MOTION_STATE = 0
+ *    (:94-103, :115-118).  The last pose becomes FRAME_POSE, valid when ok.
+ *  5 cullingOutliersOfFrame (:888-895) and :128: the last-frame list becomes the frame.  Entry i is slot i, LAST_N =
+ *    max_features; flags bit 0 = non-null and no outlier, bit 1 = non-null and observed; point, id, descriptor the slot's (zeros,
+ *    -1 for a null slot); octave and angle the frame feature's.  Entries from n on: flags 0, id -1, zeros.  The list carries ids
+ *    from here on.  A lost frame's list is handed over too (:128); the caller picks the next route from MOTION_STATE.
+ * vo_tracker_begin_frame(p, dev_is_keyframe [batch] or NULL): valid after vo_tracker_end_frame with no track call and no
+ * last-frame setter in between (the depth and feature columns are read from the frame store's slots, not copied), else
+ * VO_ERR_INVALID.  ENQUEUED, one workgroup per frame:
+ *  1 updateLastFrame's temporary points (:555-592), skipped for a frame with dev_is_keyframe[f] != 0 (:552): the pairs (d, i)
+ *    with d > 0 ascending by d, then i; c_j = 1 where entry i has bit 0 or bit 1 clear; C_j the inclusive prefix; J the first j
+ *    with d_j > th_depth && C_j > 100, else the last pair; exactly the pairs j <= J with c_j = 1 get a point: position =
+ *    csrc/keyframe_geom.h's back-projection on the last pose, flags 1, id -1, the feature's own descriptor.  TEMP_COUNT = C_J.
+ *  2 Tcw (VO_TRACKER_TCW_START) = VELOCITY * last pose; VO_TRACKER_POSE_START = its se3 logarithm (:236).
+ *  3 with ids on the local map AND the last list: link[j] = the lowest last index with local point j's id and bit 0 set, or -1,
+ *    and the link is in force (:765).  Without ids on either side the link is left as it is.
+ * vo_tracker_handover_arrays: the device addresses of SLOT_IDS, FRAME_POSE, MOTION_STATE (any pointer may be NULL), stable for
+ * the tracker's life; no synchronisation.  vo_kfstore_keyframe_need_stats_dev / vo_kfstore_create_keyframe_from_frames take
+ * dev_slot_ids and dev_Tcw12 from here.
+ * Not built: recoverLastFrame (replaced points) and the Tlr * ref pose refresh of :547-549 need a store. */
+typedef struct {
+  float th_depth;      /* camera_->thDepth_ (:571) */
+  int32_t min_tracked; /* <= 0: 30 (:310); read by vo_tracker_end_frame only */
+} vo_tracker_handover_params;
+int vo_tracker_set_last_frame_ids(vo_tracker *t, int n, const int32_t *ids /*[batch][n]*/);
+int vo_tracker_set_last_pose(vo_tracker *t, const double *Tcw12 /*[batch][12]*/, const uint8_t *valid /*[batch]*/);
+int vo_tracker_end_frame(vo_tracker *t, const vo_tracker_handover_params *p);
+int vo_tracker_begin_frame(vo_tracker *t, const vo_tracker_handover_params *p, const uint8_t *dev_is_keyframe /*[batch] or NULL*/);
+int vo_tracker_handover_arrays(vo_tracker *t, const int32_t **dev_slot_ids, const double **dev_Tcw12, const int32_t **dev_state);
 int vo_tracker_sync(vo_tracker *t);
 /* HIP events on the launching streams around the six stages of every subsequent batch (bench.py):
  * 0 extraction, 1 frame post-processing, 2 search vs last frame, 3 pose solve + culling, 4 isInFrame +

@@ -54,6 +54,8 @@ SYMBOLS = [
     "vo_kfstore_set_bad", "vo_kfstore_update_points", "vo_tracker_relocalize_store", "vo_tracker_relocalize_store_dev",
     "vo_tracker_relocalize_db", "vo_tracker_relocalize_db_dev", "vo_tracker_get_reloc_timing",
     "vo_tracker_track_ref_keyframe_store", "vo_tracker_track_ref_keyframe_store_dev", "vo_tracker_set_local_map_ids",
+    "vo_tracker_set_last_frame_ids", "vo_tracker_set_last_pose", "vo_tracker_end_frame", "vo_tracker_begin_frame",
+    "vo_tracker_handover_arrays",
     "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
     "vo_kfstore_enable_connections", "vo_kfstore_update_connections", "vo_kfstore_update_connections_dev",
     "vo_kfstore_connections_status", "vo_kfstore_get_connections",
@@ -488,6 +490,10 @@ class RelocCandidate(C.Structure):
                 ("min_distance", C.c_void_p), ("max_distance", C.c_void_p)]
 
 
+class HandoverParams(C.Structure):
+    _fields_ = [("th_depth", C.c_float), ("min_tracked", C.c_int32)]
+
+
 class TrackerParams(C.Structure):
     _fields_ = [("radius", C.c_float), ("th_radius", C.c_float), ("ratio", C.c_float), ("direction", C.c_int32),
                 ("ref_ratio", C.c_float), ("no_retry", C.c_int32)]
@@ -502,7 +508,8 @@ class Tracker:
      RELOC_WINNER, RELOC_POINT_IDS, RELOC_BOW_MATCHES, RELOC_PNP_INLIERS, RELOC_OUTCOME, RELOC_PNP_MASK,
      RELOC_CANDIDATES, RELOC_N_CANDIDATES, LOCAL_KEYFRAMES, LOCAL_N_KEYFRAMES, LOCAL_N_POINTS, LOCAL_REF_KF, LOCAL_POINT_IDS,
      LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK,
-     POSE_START) = range(36)
+     POSE_START, SLOT_IDS, SLOT_DESC, FRAME_POSE, VELOCITY, MOTION_STATE, TEMP_COUNT, LAST_POINTS, LAST_FLAGS, LAST_OCTAVE,
+     LAST_ANGLE, LAST_DESC, LAST_IDS, LAST_N, TCW_START) = range(50)
     LOCAL_MAX_KEYFRAMES = 84
     RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
@@ -614,6 +621,37 @@ class Tracker:
         reports: track_local_map after relocalize* skips the local points whose id the frame already holds"""
         ids = np.ascontiguousarray(ids, np.int32)
         check(lib().vo_tracker_set_local_map_ids(self._h, int(ids.shape[1]), _p(ids)), "vo_tracker_set_local_map_ids")
+
+    def set_last_frame_ids(self, ids):
+        """map-point ids [B, n] of the last-frame list (n = its n), negative = none: the counterpart of set_local_map_ids.
+        set_last_frame forgets them"""
+        ids = np.ascontiguousarray(ids, np.int32)
+        check(lib().vo_tracker_set_last_frame_ids(self._h, int(ids.shape[1]), _p(ids)), "vo_tracker_set_last_frame_ids")
+
+    def set_last_pose(self, Tcw12, valid):
+        """frame_last_->Tcw_ [B, 12] and poseExist_ [B]: the seed of the motion model"""
+        T, v = np.ascontiguousarray(Tcw12, np.float64), np.ascontiguousarray(valid, np.uint8)
+        assert T.shape == (self.B, 12) and v.shape == (self.B,)
+        check(lib().vo_tracker_set_last_pose(self._h, _p(T), _p(v)), "vo_tracker_set_last_pose")
+
+    def end_frame(self, th_depth, min_tracked=0):
+        """vo_tracker_end_frame: the tracked frame becomes the last frame, on the device (visualOdometry.cpp:80-128).
+        Asynchronous; get(SLOT_IDS / SLOT_DESC / FRAME_POSE / VELOCITY / MOTION_STATE / LAST_*) after."""
+        pr = HandoverParams(float(th_depth), int(min_tracked))
+        check(lib().vo_tracker_end_frame(self._h, C.byref(pr)), "vo_tracker_end_frame")
+
+    def begin_frame(self, th_depth, is_keyframe=None):
+        """vo_tracker_begin_frame: updateLastFrame's temporary points, the motion-model start pose and the link by id
+        (visualOdometry.cpp:233-236).  is_keyframe: uint8 [B] DEVICE tensor or None.  Asynchronous."""
+        pr = HandoverParams(float(th_depth), 0)
+        check(lib().vo_tracker_begin_frame(self._h, C.byref(pr), _p(is_keyframe)), "vo_tracker_begin_frame")
+        self._is_keyframe_keep = is_keyframe  # the enqueued kernel reads it
+
+    def handover_arrays(self):
+        """device addresses (ints) of SLOT_IDS [B, max_features], FRAME_POSE [B, 12] and MOTION_STATE [B]"""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        check(lib().vo_tracker_handover_arrays(self._h, C.byref(a), C.byref(b), C.byref(c)), "vo_tracker_handover_arrays")
+        return a.value, b.value, c.value
 
     def track_local_map(self, th_radius=3.0, ratio=0.8):
         """trackLocalMap on the state the first stage left, against the local map set in between.  After relocalize /
@@ -777,7 +815,7 @@ class Tracker:
         return out
 
     def get(self, what):
-        B, cap, nl, mrc = self.B, self.cap, self.max_local, max(self.max_reloc_candidates, 1)
+        B, cap, nl, mrc, ml = self.B, self.cap, self.max_local, max(self.max_reloc_candidates, 1), self.max_last
         shape, dt = {
             self.ASSIGNED_LAST: ((B, cap), np.int32), self.ASSIGNED_LOCAL: ((B, cap), np.int32),
             self.POSE_FIRST: ((B, 6), np.float64), self.INLIERS_FIRST: ((B,), np.int32),
@@ -797,7 +835,12 @@ class Tracker:
             self.LOCAL_NORMALS: ((B, max(nl, 1), 3), np.float64), self.LOCAL_MIN_DISTANCE: ((B, max(nl, 1)), np.float32),
             self.LOCAL_MAX_DISTANCE: ((B, max(nl, 1)), np.float32), self.LOCAL_DESC: ((B, max(nl, 1), 32), np.uint8),
             self.LOCAL_MAP_FLAGS: ((B, max(nl, 1)), np.uint8), self.LOCAL_LINK: ((B, max(nl, 1)), np.int32),
-            self.POSE_START: ((B, 6), np.float64)}[what]
+            self.POSE_START: ((B, 6), np.float64),
+            self.SLOT_IDS: ((B, cap), np.int32), self.SLOT_DESC: ((B, cap, 32), np.uint8), self.FRAME_POSE: ((B, 12), np.float64),
+            self.VELOCITY: ((B, 12), np.float64), self.MOTION_STATE: ((B,), np.int32), self.TEMP_COUNT: ((B,), np.int32),
+            self.LAST_POINTS: ((B, ml, 3), np.float64), self.LAST_FLAGS: ((B, ml), np.uint8), self.LAST_OCTAVE: ((B, ml), np.int32),
+            self.LAST_ANGLE: ((B, ml), np.float32), self.LAST_DESC: ((B, ml, 32), np.uint8), self.LAST_IDS: ((B, ml), np.int32),
+            self.LAST_N: ((1,), np.int32), self.TCW_START: ((B, 12), np.float64)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out

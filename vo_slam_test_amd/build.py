@@ -25,6 +25,7 @@ SOURCES = [
     ("guided.hip", ["-ffp-contract=off"]),
     ("track.hip", ["-ffp-contract=off"]),
     ("tracker.hip", ["-ffp-contract=off"]),
+    ("handover.hip", ["-ffp-contract=off"]),
     ("reloc.hip", ["-ffp-contract=off"]),
     ("local_map.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-ffp-contract=fast"]),

@@ -1,4 +1,5 @@
-// block_sort.h -- a workgroup-wide sort of 64-bit keys (k_featvec in match.hip, k_reloc_local_ids in reloc.hip).
+// block_sort.h -- a workgroup-wide sort of 64-bit keys (k_featvec in match.hip, k_reloc_local_ids in reloc.hip) and the
+// workgroup-wide prefix count of the depth walks (keyframe_create.hip, handover.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,6 +21,25 @@ __device__ __forceinline__ void block_bitonic_sort(unsigned long long *keys, int
       }
     }
   __syncthreads();
+}
+
+// exclusive prefix of `flag` over the workgroup in thread order; *total = the workgroup's sum.  s_w: one int per
+// wavefront.  Two barriers.  (the depth walks of keyframe_create.hip and handover.hip)
+__device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = (int)blockDim.x >> 6;
+  const unsigned long long m = __ballot(flag);
+  const int below = __popcll(m & ((1ull << lane) - 1ull));
+  __syncthreads();
+  if (lane == 0) s_w[w] = __popcll(m);
+  __syncthreads();
+  int base = 0, sum = 0;
+  for (int i = 0; i < nw; i++) {
+    const int c = s_w[i];
+    if (i < w) base += c;
+    sum += c;
+  }
+  *total = sum;
+  return base + below;
 }
 
 __host__ __device__ __forceinline__ int pow2_ceil(int n) {

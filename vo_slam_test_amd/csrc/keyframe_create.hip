@@ -27,24 +27,7 @@ using namespace vo;
 
 constexpr int kSeq = 1024;  // threads of the one-workgroup kernels
 
-// exclusive prefix of `flag` over the workgroup in thread order; *total = the workgroup's sum.  s_w: one int per
-// wavefront.  Two barriers.
-__device__ __forceinline__ int block_rank(bool flag, int *s_w, int *total) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = (int)blockDim.x >> 6;
-  const unsigned long long m = __ballot(flag);
-  const int below = __popcll(m & ((1ull << lane) - 1ull));
-  __syncthreads();
-  if (lane == 0) s_w[w] = __popcll(m);
-  __syncthreads();
-  int base = 0, sum = 0;
-  for (int i = 0; i < nw; i++) {
-    const int c = s_w[i];
-    if (i < w) base += c;
-    sum += c;
-  }
-  *total = sum;
-  return base + below;
-}
+// (block_rank, the workgroup-wide exclusive prefix of a flag: block_sort.h)
 
 // the entry of id's first observation in a fresh index (its lowest key: the lowest non-erased key-frame that holds it, at
 // its lowest flagged feature), or -1 when no key-frame of the store holds it

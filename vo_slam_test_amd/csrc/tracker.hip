@@ -23,7 +23,7 @@
 // solves (two events order them).  Round 2 kept this sequence in Python (vo_slam_test_amd/tracking.py) without the
 // culling step and with the local-map projections fixed before the first solve; host code is now C++
 // throughout, as the reference's callers are.
-#include "kfstore.h"
+#include "tracker_state.h"
 
 #include <cmath>
 #include <new>
@@ -326,101 +326,6 @@ constexpr int kStages = VO_TRACKER_STAGES;
 
 }  // namespace
 
-struct RefKfHost {
-  int n = 0;
-  std::vector<uint8_t> valid, desc;
-  std::vector<float> angle;
-  std::vector<int32_t> node_id, start;
-  std::vector<uint32_t> feat;
-  vo_bow_view view{};
-};
-
-struct vo_tracker {
-  vo_tracker_config cfg{};
-  vo_orb *orb = nullptr;
-  vo_frames *frames = nullptr;
-  hipStream_t st = nullptr, est = nullptr;
-  bool own_st = false, own_est = false;
-  hipEvent_t ev_extract = nullptr, ev_build = nullptr;
-  // host-buffer calls: the depth image is first read BEHIND the extraction (vo_frames_build_dev), so its upload goes on a copy
-  // stream of its own, issued after the extraction has been enqueued: the key-points are being extracted while the host (pageable
-  // memory: the runtime stages it synchronously) and the copy engine move the depth -- two thirds of the bytes of a frame
-  hipStream_t cst = nullptr;
-  hipEvent_t ev_depth = nullptr;
-  const void *pend_depth = nullptr;
-  size_t pend_depth_bytes = 0;
-  bool have_build = false;
-  int B = 0, kcap = 0, cap = 0, n_levels = 0, n_last = 0, n_local = 0, nq_last = 0, nq_local = 0;
-  float sf[16] = {0};
-  // device state
-  // device state: every array below is sized from (B, kcap, cap, n_last, n_local) at creation and lives in one block (`mem`,
-  // laid out by layout()) except the extraction's output; the images and depth of the host-buffer calls grow with those calls
-  Arena mem;
-  struct Arrays {
-    vo_keypoint *kps;  // extraction: [B][kcap] key-points, descriptors, [B] counts
-    uint8_t *desc;
-    int *cnt;
-    uint8_t *q0_flags, *q0_desc, *pf0, *last_matched;  // the last frame's map points as queries [B][n_last]
-    float *q0_u, *q0_v, *q0_aux, *q0_angle;
-    int *q0_level;
-    double *p0;
-    uint8_t *q1_flags, *q1_desc, *pf1;  // the local map's [B][n_local]
-    float *q1_u, *q1_v, *q1_aux, *q1_viewcos, *mind1, *maxd1;
-    int *q1_level, *link1, *ids1;  // ids1: map-point ids of the local points (vo_tracker_set_local_map_ids)
-    double *p1, *nrm1;
-    double *Tcw, *pose0, *pose, *pose_first;  // Tcw: [B][12], then the intrinsics as doubles
-    uint8_t *resblk;                          // k_track_pack's block (72 bytes per frame + 2 flags)
-    int *retry_nq;                            // [B] query counts of the retry pass
-    int *store_err;                           // the store routes' sticky word (vo_common.h: kStoreErr*)
-    int *ref_kf;                              // [B] the key-frame numbers of the last trackRefKeyFrame from the store
-    int *assigned, *assigned_first, *nm, *nm_first, *ninl, *ninl_first, *nobs_first, *ntracked, *status;
-    double *fpoint, *pts, *obs, *isg;  // per-feature frame state [B][cap] and the pose problem gathered from it
-    uint8_t *fhas, *fobs, *foutl, *outlier;
-    int *ranges, *index;
-  } d{};
-  void layout(Arena &a);
-  OwnedDevBuf images, depth;
-  OwnedDevBuf kps, desc;  // d.kps, d.desc: allocations of their own -- inside the block the headline measured 0.4 % slower
-  OwnedPinnedBuf stage;
-  bool have_result = false;  // a call has written the result block
-  bool have_link = false;
-  bool have_local = false, have_ids = false;  // vo_tracker_set_local_map / _ids have been called (the ids belong to that local map)
-  bool last_reloc = false;                    // the last front ran a relocalisation route: track_local_map takes the hand-over
-  // vo_tracker_build_local_map: which slot ids the last front left (0: none; 1: a relocalisation from the store; 2:
-  // trackRefKeyFrame from the store, first stage only); its buffers, laid out by the first call for the store's max_keyframes
-  int ids_route = 0;
-  vo::Arena lm_mem;
-  int lm_max_kf = 0;
-  struct { int *votes, *lkf, *n_kf, *best, *n_pts; } lm{};
-  // a search's matches that the next solve_pose writes into the frame's slots (k_track_scatter_gather)
-  struct { const int32_t *assigned = nullptr; const double *qpoints = nullptr; const uint8_t *qflags = nullptr; int stride = 0; } pend;
-  int first_min_matches = 20;
-  // trackRefKeyFrame's reference key-frame per frame of the batch (host copies: the common-node walk is host work)
-  const vo_vocab *ref_vocab = nullptr;
-  std::vector<RefKfHost> ref_kf;
-  // the relocalisation route (reloc.hip); NULL: not configured (vo_tracker_config.max_reloc_candidates == 0)
-  vo::Reloc *reloc = nullptr;
-  const vo::RelocStoreArgs *store_args = nullptr;  // set for the duration of a vo_tracker_relocalize_store / _db call
-  // the store routes' BoW walk buffers (relocalisation and trackRefKeyFrame share them), sized by the first such call
-  vo::BowWalkBufs walk;
-  // trackRefKeyFrame from the store: the arguments of the call being enqueued; whether the last front ran that route
-  struct RefStoreArgs { const vo_kfstore *store; const vo_vocab *vocab; const int32_t *ref_kf; const double *Tcw12; };
-  const RefStoreArgs *ref_store_args = nullptr;
-  bool ref_store = false;
-  const char *store_call = "";                      // the entry point of the last store route (error texts)
-  hipEvent_t rtev[8] = {nullptr};                   // vo_tracker_get_reloc_timing: created by the first timed store route
-  bool rtimed = false;
-  // timing
-  bool timing = false;
-  // 2 events per stage and timed call, in a list that grows with the calls; they are read (after one synchronisation) only
-  // by vo_tracker_get_timing, never inside a track call: a timed call enqueues exactly like an untimed one
-  std::vector<hipEvent_t> tev;
-  int tissued = 0;   // timed calls whose events are recorded and not yet read
-  int tslot = -1;    // event set of the call being enqueued (-1: not timed)
-  double tms[kStages] = {0};
-  int tcalls = 0;
-};
-
 void vo_tracker::layout(vo::Arena &a) {
   const size_t B = this->B, nl = (size_t)n_last, nm = (size_t)n_local, cap = this->cap;
   a.take(d.cnt, B * 4 + 64);
@@ -545,9 +450,7 @@ int solve_pose(vo_tracker *t) {
                                        nullptr, t->st);
 }
 
-// What a call runs: the front (extraction + Frame::Frame), one of the two first stages -- trackWithMotion's projection
-// search (with its 2 x radius retry) or trackRefKeyFrame's vocabulary-node search --, and the local-map stage.
-enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u, kRunReloc = 16u, kRunRefStore = 32u };
+// (what a call runs: the kRun* bits of tracker_state.h)
 
 // the images and the depth of one call, in device memory (the host-buffer calls pass their uploaded copies)
 struct FrameInput {
@@ -973,6 +876,7 @@ void vo_tracker_destroy(vo_tracker *t) {
   if (t->ev_build) (void)hipEventDestroy(t->ev_build);
   if (t->ev_depth) (void)hipEventDestroy(t->ev_depth);
   if (t->reloc) vo::reloc_destroy(t->reloc);
+  vo::handover_destroy(t->ho);
   for (hipEvent_t e : t->rtev)
     if (e) (void)hipEventDestroy(e);
   if (t->frames) vo_frames_destroy(t->frames);
@@ -1015,6 +919,7 @@ int vo_tracker_set_last_frame(vo_tracker *t, int n, const double *Tcw12, const d
   VO_CHECK(put_rows(t, t->d.q0_angle, angle, n, t->n_last, 4));
   VO_CHECK(put_rows(t, t->d.q0_desc, desc, n, t->n_last, 32));
   t->nq_last = n;
+  t->have_last_ids = false, t->handed_over = false;  // (ids belong to the list they were set for)
   VO_HIP_CHECK(hipStreamSynchronize(t->st));  // the caller's arrays and the staging block are free again
   return VO_OK;
 }
@@ -1050,9 +955,16 @@ int vo_tracker_set_local_map_ids(vo_tracker *t, int n, const int32_t *ids) {
   return VO_OK;
 }
 
+// what vo_tracker_end_frame asks of the last track call: the stages it ran, all of them enqueued
+static int ran(vo_tracker *t, unsigned run, int rc) {
+  t->last_run = rc == VO_OK ? run : 0u;
+  t->handed_over = false;  // (the frame store's slots hold another frame now)
+  return rc;
+}
+
 static int track_dev(vo_tracker *t, const FrameInput &in, const vo_tracker_params *params, unsigned run) {
   if (!dev_input_ok(t, in)) return VO_ERR_INVALID;
-  return run_pipeline(t, in, params, run);
+  return ran(t, run, run_pipeline(t, in, params, run));
 }
 
 int vo_tracker_track_dev(vo_tracker *t, const uint8_t *dev_images, int image_pitch, size_t image_frame_stride,
@@ -1081,7 +993,7 @@ static int track_host(vo_tracker *t, const uint8_t *images, const void *depth, i
   size_t npx = 0, dsz = 0;
   VO_CHECK(upload_host_frames(t, images, depth, depth_kind, &npx, &dsz));
   const FrameInput in{t->images.as<uint8_t>(), t->cfg.width, npx, dsz ? t->depth.p : nullptr, depth_kind, npx * dsz, t->cfg.width * (int)dsz};
-  return run_pipeline(t, in, params, run);
+  return ran(t, run, run_pipeline(t, in, params, run));
 }
 
 int vo_tracker_track_first(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind, const vo_tracker_params *params) {
@@ -1112,7 +1024,9 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params) {
     t->pend.assigned = nullptr;
     return stage_local_reloc(t, P);
   }
-  return run_pipeline(t, FrameInput{}, params, kRunLocal);
+  const int rc = run_pipeline(t, FrameInput{}, params, kRunLocal);
+  t->last_run = rc == VO_OK ? (t->last_run | kRunLocal) : 0u;
+  return rc;
 }
 
 int vo_tracker_track_ref_keyframe(vo_tracker *t, const uint8_t *images, const void *depth, int depth_kind,
@@ -1192,6 +1106,7 @@ int vo_tracker_set_ref_keyframe(vo_tracker *t, const vo_vocab *vocab, int n, con
   t->ref_kf.swap(kfs);
   // the views point into the vectors' heap blocks, which the swap moved along with their owners
   t->nq_last = n;
+  t->have_last_ids = false, t->handed_over = false;
   return VO_OK;
 }
 
@@ -1229,6 +1144,7 @@ static void ref_store_commit(vo_tracker *t, const char *call, const vo_kfstore *
   // the rows hold max_features entries, flag 0 beyond a key-frame's own n (which only the device knows): a following
   // vo_tracker_track without vo_tracker_set_last_frame would project those dead queries too
   t->nq_last = vo::kfstore_view(store).NK;
+  t->have_last_ids = false, t->handed_over = false;
 }
 
 int vo_tracker_track_ref_keyframe_store(vo_tracker *t, const vo_kfstore *store, const vo_vocab *vocab, const int32_t *dev_ref_kf,
@@ -1517,6 +1433,12 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     VO_HIP_CHECK(hipStreamSynchronize(t->st));
     return VO_OK;
   }
+  if (what == VO_TRACKER_LAST_N) {  // (a host value: the last-frame list's n)
+    if (dst_bytes < 4) return VO_ERR_CAPACITY;
+    const int32_t n = t->nq_last;
+    memcpy(dst, &n, 4);
+    return VO_OK;
+  }
   switch (what) {
     case VO_TRACKER_ASSIGNED_LAST: b = t->d.assigned_first, bytes = B * cap * 4; break;
     case VO_TRACKER_ASSIGNED_LOCAL: b = t->d.assigned, bytes = B * cap * 4; break;
@@ -1546,10 +1468,19 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     case VO_TRACKER_LOCAL_MAP_FLAGS: b = t->d.pf1, bytes = B * (size_t)t->n_local; break;
     case VO_TRACKER_LOCAL_LINK: b = t->d.link1, bytes = B * (size_t)t->n_local * 4; break;
     case VO_TRACKER_POSE_START: b = t->d.pose0, bytes = B * 48; break;
-    default: return VO_ERR_INVALID;
+    case VO_TRACKER_LAST_POINTS: b = t->d.p0, bytes = B * (size_t)t->n_last * 24; break;
+    case VO_TRACKER_LAST_FLAGS: b = t->d.pf0, bytes = B * (size_t)t->n_last; break;
+    case VO_TRACKER_LAST_OCTAVE: b = t->d.q0_level, bytes = B * (size_t)t->n_last * 4; break;
+    case VO_TRACKER_LAST_ANGLE: b = t->d.q0_angle, bytes = B * (size_t)t->n_last * 4; break;
+    case VO_TRACKER_LAST_DESC: b = t->d.q0_desc, bytes = B * (size_t)t->n_last * 32; break;
+    case VO_TRACKER_TCW_START: b = t->d.Tcw, bytes = B * 96; break;
+    default:
+      if (what < VO_TRACKER_SLOT_IDS || what > VO_TRACKER_TCW_START) return VO_ERR_INVALID;
+      b = vo::handover_selector(t, what, &bytes);  // (the block of handover.hip)
   }
   if (!b) {
-    vo::set_error("vo_tracker_get(%d): vo_tracker_build_local_map has not run", what);
+    vo::set_error("vo_tracker_get(%d): %s has not run", what,
+                  what >= VO_TRACKER_SLOT_IDS ? "the hand-over (vo_tracker_end_frame, _set_last_pose, _set_last_frame_ids)" : "vo_tracker_build_local_map");
     return VO_ERR_INVALID;
   }
   if (dst_bytes < bytes) {
