@@ -1968,7 +1968,17 @@ int vo_tracker_track_ref_keyframe_store_dev(vo_tracker *t, const vo_kfstore *sto
  * order, VO_TRACKER_LOCAL_N_KEYFRAMES reports its true count and vo_tracker_results the sticky VO_ERR_CAPACITY (the best
  * key-frame is still taken over all voters).  (d) A frame with more distinct points than max_local keeps the first
  * max_local in order, VO_TRACKER_LOCAL_N_POINTS reports the true count: sticky VO_ERR_CAPACITY as well; every other
- * frame's outputs are valid.  The addVisible / addFound counters are not kept. */
+ * frame's outputs are valid.  The addVisible / addFound counters: vo_tracker_point_stats (below).
+ * The motion route: the call is also valid after vo_tracker_track_first[_dev] when the last-frame list it searched carries ids
+ * (after vo_tracker_end_frame or vo_tracker_set_last_frame_ids); without ids on the list, and after vo_tracker_track[_dev]
+ * (both stages in one call), it stays VO_ERR_INVALID.  The slot id of slot i < n is last_ids[VO_TRACKER_ASSIGNED_LAST[i]] where
+ * VO_TRACKER_FEATURE_HAS_POINT[i] is set after cullingOutliersBeforeLocalMap and the assignment is >= 0, else -1: a temporary
+ * point of updateLastFrame has no id, casts no vote and is not nulled.  One more launch in front gathers the ids
+ * (VO_TRACKER_FIRST_SLOT_IDS: these ids after step 1's nulling, which clears VO_TRACKER_FEATURE_HAS_POINT as above), one behind
+ * writes link[j] = the lowest last-list index with local point j's id and bit 0 set, or -1 -- step 3 of vo_tracker_begin_frame,
+ * the same code, over EVERY entry of the list (all n of a list the host set, up to max_last, also where max_last > max_features)
+ * -- and the link is in force, so that searchLocalMapPoints' skip (:753) acts in vo_tracker_track_local_map as on
+ * a local map the host set.  Deviations (a) - (d) apply unchanged; `store` is any store in the id space of the last ids. */
 #define VO_TRACKER_LOCAL_MAX_KEYFRAMES 84
 int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store);
 /* With vo_tracker_set_timing on, a store route records HIP events around its four new stages: 0 k_featvec, 1 the gather
@@ -2039,8 +2049,16 @@ enum {
   VO_TRACKER_LAST_DESC = 46,         /* uint8 [..][32] */
   VO_TRACKER_LAST_IDS = 47,          /* int32: map-point id per entry, -1 = none */
   VO_TRACKER_LAST_N = 48,            /* int32 [1]: the list's n */
-  VO_TRACKER_TCW_START = 49          /* double [batch][12]: the pose the last-frame points are projected with (Tcw12 of
+  VO_TRACKER_TCW_START = 49,         /* double [batch][12]: the pose the last-frame points are projected with (Tcw12 of
                                         vo_tracker_set_last_frame / _ref_keyframe, or VELOCITY * last pose of vo_tracker_begin_frame) */
+  /* the motion route from the key-frame store (vo_tracker_point_stats etc. below) */
+  VO_TRACKER_FIRST_SLOT_IDS = 50,    /* int32 [batch][max_features]: id of frame->mappoints_[i] when the local-map stage starts, as
+                                        vo_tracker_build_local_map gathered it from the last ids, after its nulling; -1 = null or temporary */
+  VO_TRACKER_STAT_IDS = 51,          /* int32 [batch][max_features + max_local]: vo_tracker_point_stats' rows */
+  VO_TRACKER_STAT_VISIBLE = 52,      /* int32, same shape */
+  VO_TRACKER_STAT_FOUND = 53,        /* int32, same shape */
+  VO_TRACKER_REF_TCR = 54,           /* double [batch][12]: TcrDB_ of the remembered reference key-frame */
+  VO_TRACKER_REF_KF = 55             /* int32 [batch]: that key-frame's number, -1: none */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 /* frame_last_ = frame_curr_ on the device: what VisualOdometry::run does between two frames
@@ -2089,7 +2107,8 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
  * vo_tracker_handover_arrays: the device addresses of SLOT_IDS, FRAME_POSE, MOTION_STATE (any pointer may be NULL), stable for
  * the tracker's life; no synchronisation.  vo_kfstore_keyframe_need_stats_dev / vo_kfstore_create_keyframe_from_frames take
  * dev_slot_ids and dev_Tcw12 from here.
- * Not built: recoverLastFrame (replaced points) and the Tlr * ref pose refresh of :547-549 need a store. */
+ * The Tlr * ref pose refresh of :547-549: vo_tracker_record_ref_pose / vo_tracker_refresh_last_pose (below).
+ * Not built: recoverLastFrame (replaced points), which needs a replacement log the store does not keep. */
 typedef struct {
   float th_depth;      /* camera_->thDepth_ (:571) */
   int32_t min_tracked; /* <= 0: 30 (:310); read by vo_tracker_end_frame only */
@@ -2099,6 +2118,47 @@ int vo_tracker_set_last_pose(vo_tracker *t, const double *Tcw12 /*[batch][12]*/,
 int vo_tracker_end_frame(vo_tracker *t, const vo_tracker_handover_params *p);
 int vo_tracker_begin_frame(vo_tracker *t, const vo_tracker_handover_params *p, const uint8_t *dev_is_keyframe /*[batch] or NULL*/);
 int vo_tracker_handover_arrays(vo_tracker *t, const int32_t **dev_slot_ids, const double **dev_Tcw12, const int32_t **dev_state);
+/* The motion route from the key-frame store: with vo_tracker_build_local_map after
+ * vo_tracker_track_first[_dev] (above), what a motion-tracked frame still took to the host -- the addVisible / addFound
+ * counters of trackLocalMap and the Tlr * ref pose refresh of updateLastFrame --, so that a frame is one chain of enqueued calls:
+ * begin_frame -> track_first_dev -> build_local_map(store) -> track_local_map -> point_stats -> end_frame -> record_ref_pose ->
+ * ... -> refresh_last_pose -> begin_frame.  Their state is ONE device block of its own, allocated by the first call that needs
+ * it (build_local_map on the motion route, or any of the four below): first slot ids 4 BF, a vote mask BF, three counter arrays
+ * 3 x 4 B(F + M), Tcr 96 B, the key-frame numbers 4 B, and 8 BP sort keys of the link only where P > 4096 (B = batch, F =
+ * max_features, M = max_local, P = the power of two >= max(F, max_last); every array rounded up to 4 KiB).  After that first call each is ENQUEUED on the tracker's stream: no allocation, no host synchronisation, no
+ * device-to-host copy; the pose calls are ordered against the store's stream by events.  Every refusal happens before anything
+ * is enqueued or any state changes.
+ * vo_tracker_point_stats(): valid after vo_tracker_track_first[_dev] + vo_tracker_track_local_map with ids on the local map
+ * (built, or vo_tracker_set_local_map_ids) and on the last-frame list; anything else VO_ERR_INVALID (the counters behind the
+ * relocalisation and reference-key-frame routes are not built).  One launch, a workgroup per frame, fills VO_TRACKER_STAT_IDS,
+ * _VISIBLE and _FOUND, int32 [batch][max_features + max_local]:
+ *  A entry i < max_features: p = the id slot i held when searchLocalMapPoints started -- VO_TRACKER_FIRST_SLOT_IDS[i] behind a
+ *    built map; behind a local map the host set the same gather on the state as it stands (a slot the local search claimed
+ *    counts as holding its last-frame entry, also where the first solve had culled it).  visible 1 (:738); found 1 iff the slot
+ *    still holds that point (VO_TRACKER_ASSIGNED_LOCAL[i] < 0) and VO_TRACKER_FEATURE_OUTLIER[i] == 0 (:295-297).  p < 0 or
+ *    i >= n: id -1, counts 0.  A map built on the motion route stays "the built map" of its frame until the next track call: a
+ *    caller who replaces it through vo_tracker_set_local_map / _ids before vo_tracker_track_local_map still gets segment A from
+ *    the build's FIRST_SLOT_IDS (its nulling has acted on the slots), and vo_tracker_results still reports the build's sticky word.
+ *  B entry max_features + j: id = VO_TRACKER_LOCAL_POINT_IDS[j]; visible = bit 0 of VO_TRACKER_LOCAL_FLAGS[j] (:750-760); found 1
+ *    iff the slot i with VO_TRACKER_ASSIGNED_LOCAL[i] == j has VO_TRACKER_FEATURE_OUTLIER[i] == 0.  Both counts 0: id -1.
+ * vo_tracker_point_stats_arrays: the device addresses of the three arrays and their row length (any pointer may be NULL), stable
+ * for the tracker's life; no synchronisation.  A frame's row goes straight into vo_kfstore_add_point_stats_dev(s, row_len, ...);
+ * that call's bound n <= max_recent + max_features is the caller's to meet: max_recent >= max_local.
+ * vo_tracker_record_ref_pose(store, dev_ref_kf [batch] or NULL) (:130-140): valid after vo_tracker_end_frame, before the next
+ * track call or last-frame setter; the store needs vo_kfstore_enable_mapping (the pose column); else VO_ERR_INVALID.  Per frame
+ * ref = dev_ref_kf[f] (NULL: VO_TRACKER_LOCAL_REF_KF[f]; VO_ERR_INVALID when no map was ever built) where it lies in [0, size) and
+ * its pose is set, else the key-frame the frame remembers (:692-696).  With the frame's last pose valid and such a ref:
+ * VO_TRACKER_REF_TCR = FRAME_POSE * pose(ref)^-1 and VO_TRACKER_REF_KF = ref; otherwise the previous pair stands (:138-139).
+ * vo_tracker_refresh_last_pose(store) (:547-549): valid between vo_tracker_end_frame and vo_tracker_begin_frame, same store
+ * condition; it is no last-frame setter: vo_tracker_begin_frame is accepted behind it.  A frame with a remembered pair: last
+ * pose = REF_TCR * pose(REF_KF), its validity byte untouched; other frames are left alone.  vo_tracker_begin_frame then builds
+ * the start pose and the temporary points on the refreshed pose (:549 before :581 and :236).  Inverse and product are
+ * csrc/handover_geom.h's, every operation rounded.  One launch each. */
+int vo_tracker_point_stats(vo_tracker *t);
+int vo_tracker_point_stats_arrays(vo_tracker *t, const int32_t **dev_ids, const int32_t **dev_visible, const int32_t **dev_found,
+                                  int32_t *row_len);
+int vo_tracker_record_ref_pose(vo_tracker *t, const vo_kfstore *store, const int32_t *dev_ref_kf /*[batch] or NULL*/);
+int vo_tracker_refresh_last_pose(vo_tracker *t, const vo_kfstore *store);
 int vo_tracker_sync(vo_tracker *t);
 /* HIP events on the launching streams around the six stages of every subsequent batch (bench.py):
  * 0 extraction, 1 frame post-processing, 2 search vs last frame, 3 pose solve + culling, 4 isInFrame +

@@ -56,6 +56,7 @@ SYMBOLS = [
     "vo_tracker_track_ref_keyframe_store", "vo_tracker_track_ref_keyframe_store_dev", "vo_tracker_set_local_map_ids",
     "vo_tracker_set_last_frame_ids", "vo_tracker_set_last_pose", "vo_tracker_end_frame", "vo_tracker_begin_frame",
     "vo_tracker_handover_arrays",
+    "vo_tracker_point_stats", "vo_tracker_point_stats_arrays", "vo_tracker_record_ref_pose", "vo_tracker_refresh_last_pose",
     "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
     "vo_kfstore_enable_connections", "vo_kfstore_update_connections", "vo_kfstore_update_connections_dev",
     "vo_kfstore_connections_status", "vo_kfstore_get_connections",
@@ -509,7 +510,7 @@ class Tracker:
      RELOC_CANDIDATES, RELOC_N_CANDIDATES, LOCAL_KEYFRAMES, LOCAL_N_KEYFRAMES, LOCAL_N_POINTS, LOCAL_REF_KF, LOCAL_POINT_IDS,
      LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK,
      POSE_START, SLOT_IDS, SLOT_DESC, FRAME_POSE, VELOCITY, MOTION_STATE, TEMP_COUNT, LAST_POINTS, LAST_FLAGS, LAST_OCTAVE,
-     LAST_ANGLE, LAST_DESC, LAST_IDS, LAST_N, TCW_START) = range(50)
+     LAST_ANGLE, LAST_DESC, LAST_IDS, LAST_N, TCW_START, FIRST_SLOT_IDS, STAT_IDS, STAT_VISIBLE, STAT_FOUND, REF_TCR, REF_KF) = range(56)
     LOCAL_MAX_KEYFRAMES = 84
     RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
@@ -616,6 +617,16 @@ class Tracker:
         pr = self._params(radius, 3.0, 0.8, direction, no_retry)
         check(lib().vo_tracker_track_first(self._h, _p(img), _p(dp), kind, C.byref(pr)), "vo_tracker_track_first")
 
+    def track_first_dev(self, images, depth=None, radius=15.0, direction=0, no_retry=False):
+        """trackWithMotion alone from device tensors (see track_dev).  Asynchronous."""
+        kind, fs, pitch = 0, 0, 0
+        if depth is not None:
+            kind = 1 if depth.element_size() == 4 else 2
+            fs, pitch = depth.stride(0) * depth.element_size(), depth.stride(1) * depth.element_size()
+        pr = self._params(radius, 3.0, 0.8, direction, no_retry)
+        check(lib().vo_tracker_track_first_dev(self._h, _p(images), int(images.stride(1)), C.c_size_t(images.stride(0)), _p(depth),
+                                               kind, C.c_size_t(fs), int(pitch), C.byref(pr)), "vo_tracker_track_first_dev")
+
     def set_local_map_ids(self, ids):
         """map-point ids [B, n] of the local points set by set_local_map (n = its n), in the id space get(RELOC_POINT_IDS)
         reports: track_local_map after relocalize* skips the local points whose id the frame already holds"""
@@ -652,6 +663,30 @@ class Tracker:
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         check(lib().vo_tracker_handover_arrays(self._h, C.byref(a), C.byref(b), C.byref(c)), "vo_tracker_handover_arrays")
         return a.value, b.value, c.value
+
+    def point_stats(self):
+        """vo_tracker_point_stats: addVisible / addFound of the frame as three rows per frame, on the device, after
+        track_first + track_local_map with ids on the local map and on the last list.  Asynchronous; get(STAT_IDS /
+        STAT_VISIBLE / STAT_FOUND) after."""
+        check(lib().vo_tracker_point_stats(self._h), "vo_tracker_point_stats")
+
+    def point_stats_arrays(self):
+        """device addresses (ints) of STAT_IDS, STAT_VISIBLE, STAT_FOUND [B, row_len] and row_len = max_features + max_local"""
+        a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
+        check(lib().vo_tracker_point_stats_arrays(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "vo_tracker_point_stats_arrays")
+        return a.value, b.value, c.value, n.value
+
+    def record_ref_pose(self, store, ref_kf=None):
+        """vo_tracker_record_ref_pose: Tcr = frame pose * pose(ref)^-1 per frame after end_frame (visualOdometry.cpp:130-140).
+        ref_kf: int32 [B] DEVICE tensor, or None: get(LOCAL_REF_KF).  Asynchronous; get(REF_TCR / REF_KF) after."""
+        check(lib().vo_tracker_record_ref_pose(self._h, store._h, _p(ref_kf)), "vo_tracker_record_ref_pose")
+        # the enqueued kernels read them: the last four calls' arguments stay alive (a frame records once), whatever else is called
+        self._record_keep = (getattr(self, "_record_keep", []) + [(store, ref_kf)])[-4:]
+
+    def refresh_last_pose(self, store):
+        """vo_tracker_refresh_last_pose: last pose = Tcr * pose(ref) between end_frame and begin_frame (:547-549).  Asynchronous."""
+        check(lib().vo_tracker_refresh_last_pose(self._h, store._h), "vo_tracker_refresh_last_pose")
+        self._refresh_keep = store  # the enqueued kernel reads it
 
     def track_local_map(self, th_radius=3.0, ratio=0.8):
         """trackLocalMap on the state the first stage left, against the local map set in between.  After relocalize /
@@ -840,7 +875,9 @@ class Tracker:
             self.VELOCITY: ((B, 12), np.float64), self.MOTION_STATE: ((B,), np.int32), self.TEMP_COUNT: ((B,), np.int32),
             self.LAST_POINTS: ((B, ml, 3), np.float64), self.LAST_FLAGS: ((B, ml), np.uint8), self.LAST_OCTAVE: ((B, ml), np.int32),
             self.LAST_ANGLE: ((B, ml), np.float32), self.LAST_DESC: ((B, ml, 32), np.uint8), self.LAST_IDS: ((B, ml), np.int32),
-            self.LAST_N: ((1,), np.int32), self.TCW_START: ((B, 12), np.float64)}[what]
+            self.LAST_N: ((1,), np.int32), self.TCW_START: ((B, 12), np.float64),
+            self.FIRST_SLOT_IDS: ((B, cap), np.int32), self.STAT_IDS: ((B, cap + nl), np.int32), self.STAT_VISIBLE: ((B, cap + nl), np.int32),
+            self.STAT_FOUND: ((B, cap + nl), np.int32), self.REF_TCR: ((B, 12), np.float64), self.REF_KF: ((B,), np.int32)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out

@@ -26,6 +26,7 @@ SOURCES = [
     ("track.hip", ["-ffp-contract=off"]),
     ("tracker.hip", ["-ffp-contract=off"]),
     ("handover.hip", ["-ffp-contract=off"]),
+    ("motion_store.hip", ["-ffp-contract=off"]),
     ("reloc.hip", ["-ffp-contract=off"]),
     ("local_map.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-ffp-contract=fast"]),

@@ -7,7 +7,7 @@
 //               (depth bits << 32 | feature) sorted by block_bitonic_sort in LDS (up to kHoLdsKeys keys, else in the block), the
 //               inclusive count C_j by wave ballots, the first j with d_j > th_depth && C_j > 100 --, the start pose
 //               Tcl_ * Tlw (:236) with its logarithm, and `link` by id: the last entries' (id << 32 | index) sorted, a lower
-//               bound per local point.
+//               bound per local point (handover_link.h, shared with motion_store.hip).
 // They write the arrays vo_tracker_set_last_frame fills from the host; the tracker's arena and every array the timed step
 // touches stay where they are, and the state of this file is one block of its own.  No atomic decides an order; no kernel waits
 // on another workgroup; every loop is bounded by a count read once.
@@ -15,20 +15,12 @@
 
 #include "block_sort.h"
 #include "handover_geom.h"
+#include "handover_link.h"
 
 #include <algorithm>
 #include <new>
 
 namespace vo {
-
-struct Handover {
-  Arena mem;
-  int P = 0;  // the power of two >= max_features: the keys of a frame
-  int *slot_ids = nullptr, *last_ids = nullptr, *motion_state = nullptr, *temp_count = nullptr;
-  uint8_t *slot_desc = nullptr, *slot_flags = nullptr, *last_valid = nullptr;
-  double *frame_pose = nullptr, *velocity = nullptr, *last_pose = nullptr;  // last_pose: [B][12], then last_valid [B]
-  unsigned long long *keys = nullptr;                                        // [B][P] where P > kHoLdsKeys, else unused
-};
 
 void handover_destroy(Handover *h) { delete h; }
 
@@ -37,8 +29,6 @@ void handover_destroy(Handover *h) { delete h; }
 namespace {
 
 using namespace vo;
-
-constexpr int kHoLdsKeys = 4096;
 
 struct EndArgs {
   int cap, n_last, n_local;
@@ -219,31 +209,7 @@ __global__ __launch_bounds__(256) void k_ho_begin(BeginArgs A) {
   // ---- link by id (:765)
   if (!A.ids1) return;
   __syncthreads();  // the temporary points' flags and ids are written (id -1: they link to nothing)
-  const int P = pow2_ceil(max(A.cap, 1));
-  for (int i = tid; i < P; i += 256) {
-    unsigned long long key = ~0ull;
-    if (i < A.cap && (A.pf0[lo + i] & 1)) {
-      const int id = A.last_ids[lo + i];
-      if (id >= 0) key = ((unsigned long long)(unsigned)id << 32) | (unsigned)i;
-    }
-    keys[i] = key;
-  }
-  block_bitonic_sort(keys, P);
-  for (int j = tid; j < A.nq_local; j += 256) {
-    const int id = A.ids1[mo + j];
-    int lk = -1;
-    if (id >= 0) {
-      const unsigned long long want = (unsigned long long)(unsigned)id << 32;
-      int lo_ = 0, hi = P;  // the first key >= want: the id's lowest index
-      while (lo_ < hi) {
-        const int mid = (lo_ + hi) >> 1;
-        if (keys[mid] < want) lo_ = mid + 1;
-        else hi = mid;
-      }
-      if (lo_ < P && keys[lo_] != ~0ull && (int)(keys[lo_] >> 32) == id) lk = (int)(keys[lo_] & 0xffffffffu);
-    }
-    A.link1[mo + j] = lk;
-  }
+  ho_link_by_id(keys, A.cap, A.pf0 + lo, A.last_ids + lo, A.ids1 + mo, A.link1 + mo, A.nq_local);
 }
 
 // the block, allocated by the first call of this file's API
@@ -368,7 +334,7 @@ int vo_tracker_end_frame(vo_tracker *t, const vo_tracker_handover_params *p) {
   hipLaunchKernelGGL(k_ho_end, dim3(t->B), dim3(256), 0, t->st, A);
   VO_HIP_CHECK(hipGetLastError());
   t->nq_last = t->cap;  // entry i is slot i
-  t->have_last_ids = true, t->handed_over = true;
+  t->have_last_ids = true, t->handed_over = true, t->begun = false;
   return VO_OK;
 }
 
@@ -394,6 +360,7 @@ int vo_tracker_begin_frame(vo_tracker *t, const vo_tracker_handover_params *p, c
   hipLaunchKernelGGL(k_ho_begin, dim3(t->B), dim3(256), 0, t->st, A);
   VO_HIP_CHECK(hipGetLastError());
   if (link) t->have_link = true;
+  t->begun = true;  // (vo_tracker_refresh_last_pose's window is closed)
   return VO_OK;
 }
 

@@ -877,6 +877,7 @@ void vo_tracker_destroy(vo_tracker *t) {
   if (t->ev_depth) (void)hipEventDestroy(t->ev_depth);
   if (t->reloc) vo::reloc_destroy(t->reloc);
   vo::handover_destroy(t->ho);
+  vo::motion_store_destroy(t->ms);
   for (hipEvent_t e : t->rtev)
     if (e) (void)hipEventDestroy(e);
   if (t->frames) vo_frames_destroy(t->frames);
@@ -959,6 +960,7 @@ int vo_tracker_set_local_map_ids(vo_tracker *t, int n, const int32_t *ids) {
 static int ran(vo_tracker *t, unsigned run, int rc) {
   t->last_run = rc == VO_OK ? run : 0u;
   t->handed_over = false;  // (the frame store's slots hold another frame now)
+  t->lm_motion = false, t->local_split = false;
   return rc;
 }
 
@@ -1026,6 +1028,7 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params) {
   }
   const int rc = run_pipeline(t, FrameInput{}, params, kRunLocal);
   t->last_run = rc == VO_OK ? (t->last_run | kRunLocal) : 0u;
+  t->local_split = rc == VO_OK;
   return rc;
 }
 
@@ -1289,9 +1292,12 @@ int vo_tracker_relocalize_db_dev(vo_tracker *t, vo_kfdb *db, const vo_kfstore *s
 int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store) {
   if (!t || !store) return VO_ERR_INVALID;
   // everything is checked before anything is enqueued
-  if (!t->have_result || t->ids_route == 0) {
-    vo::set_error("vo_tracker_build_local_map: the last route left no map-point ids (valid after vo_tracker_relocalize_store / _db and "
-                  "vo_tracker_track_ref_keyframe_store with first_stage_only = 1)");
+  // the motion route: the first stage alone has run, and the last-frame list it searched carries ids (section 4v)
+  const bool motion = t->have_result && t->ids_route == 0 && t->last_run == (kRunFront | kRunMotion) && t->have_last_ids;
+  if (!t->have_result || (t->ids_route == 0 && !motion)) {
+    vo::set_error("vo_tracker_build_local_map: the last route left no map-point ids (valid after vo_tracker_relocalize_store / _db, "
+                  "vo_tracker_track_ref_keyframe_store with first_stage_only = 1, and vo_tracker_track_first with ids on the "
+                  "last-frame list)");
     return VO_ERR_INVALID;
   }
   if (t->cfg.max_local < 1) {
@@ -1306,6 +1312,7 @@ int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store) {
   int *fid = nullptr;
   const int *winner = nullptr;
   if (t->ids_route == 1) VO_CHECK(vo::reloc_frame_ids(t->reloc, &fid, &winner));
+  if (motion) VO_CHECK(vo::motion_store_ensure(t));
   hipStream_t st = t->st;
   if (V.max_kf > t->lm_max_kf) {  // the first call, or a store of more key-frames than any before
     if (t->lm_max_kf) VO_HIP_CHECK(hipStreamSynchronize(st));  // (growing frees the block an enqueued call may still use)
@@ -1336,12 +1343,15 @@ int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store) {
   A.votes = t->lm.votes, A.lkf = t->lm.lkf, A.n_kf = t->lm.n_kf, A.best = t->lm.best, A.n_pts = t->lm.n_pts;
   A.err = d.store_err;
   A.p1 = d.p1, A.nrm1 = d.nrm1, A.mind1 = d.mind1, A.maxd1 = d.maxd1, A.pf1 = d.pf1, A.desc1 = d.q1_desc, A.link1 = d.link1, A.ids1 = d.ids1;
+  if (motion) VO_CHECK(vo::motion_store_slot_ids(t, &A, st));  // (the ids gathered from the last list: A.sid and its vote mask)
   VO_CHECK(vo::local_map_build(A, st));
+  if (motion) VO_CHECK(vo::motion_store_link(t, st));
   // the sticky word into the result block (its third flag), as the store routes leave it
   VO_HIP_CHECK(hipMemcpyAsync(d.resblk + (size_t)t->B * 72 + 8, d.store_err, 4, hipMemcpyDeviceToDevice, st));
   VO_CHECK(vo::kfstore_order_after(store, st));
   t->nq_local = t->cfg.max_local;
-  t->have_local = true, t->have_ids = true, t->have_link = t->ids_route == 2;
+  t->have_local = true, t->have_ids = true, t->have_link = t->ids_route == 2 || motion;
+  t->lm_motion = motion;
   return VO_OK;
 }
 
@@ -1386,7 +1396,8 @@ int vo_tracker_results(vo_tracker *t, double *poses6, double *Tcw12, int32_t *n_
       if (dst[k]) dst[k][f] = pi[k];
   }
   const int32_t *flags = reinterpret_cast<const int32_t *>(h + B * 72);
-  const int32_t store_err = (t->ref_store || vo::reloc_last_was_store(t->reloc)) ? flags[2] : 0;  // (the third word is the store routes' only)
+  // (the third word is the store routes' only -- and the motion route's once vo_tracker_build_local_map has run behind it)
+  const int32_t store_err = (t->ref_store || t->lm_motion || vo::reloc_last_was_store(t->reloc)) ? flags[2] : 0;
   if (flags[0] != 0 || flags[1] != 0) {
     // a sticky error flag of a stage is up (dropped key-points, exhausted candidate pools): report and clear it
     VO_CHECK(vo_orb_sync(t->orb));
@@ -1475,12 +1486,16 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     case VO_TRACKER_LAST_DESC: b = t->d.q0_desc, bytes = B * (size_t)t->n_last * 32; break;
     case VO_TRACKER_TCW_START: b = t->d.Tcw, bytes = B * 96; break;
     default:
-      if (what < VO_TRACKER_SLOT_IDS || what > VO_TRACKER_TCW_START) return VO_ERR_INVALID;
-      b = vo::handover_selector(t, what, &bytes);  // (the block of handover.hip)
+      if (what < VO_TRACKER_SLOT_IDS || what > VO_TRACKER_REF_KF) return VO_ERR_INVALID;
+      b = what >= VO_TRACKER_FIRST_SLOT_IDS ? vo::motion_store_selector(t, what, &bytes)  // (the block of motion_store.hip)
+                                            : vo::handover_selector(t, what, &bytes);     // (the block of handover.hip)
   }
   if (!b) {
     vo::set_error("vo_tracker_get(%d): %s has not run", what,
-                  what >= VO_TRACKER_SLOT_IDS ? "the hand-over (vo_tracker_end_frame, _set_last_pose, _set_last_frame_ids)" : "vo_tracker_build_local_map");
+                  what >= VO_TRACKER_FIRST_SLOT_IDS ? "the motion route from the store (vo_tracker_build_local_map after vo_tracker_track_first, "
+                                                      "vo_tracker_point_stats[_arrays], vo_tracker_record_ref_pose)"
+                  : what >= VO_TRACKER_SLOT_IDS     ? "the hand-over (vo_tracker_end_frame, _set_last_pose, _set_last_frame_ids)"
+                                                    : "vo_tracker_build_local_map");
     return VO_ERR_INVALID;
   }
   if (dst_bytes < bytes) {

@@ -1,5 +1,6 @@
 // tracker_state.h -- the tracker's handle as its own files see it (not part of the C-ABI): tracker.hip (the routes, the
-// setters, the getters) and handover.hip (frame_last_ = frame_curr_ on the device).
+// setters, the getters), handover.hip (frame_last_ = frame_curr_ on the device) and motion_store.hip (the
+// motion route's local map, point counters and pose refresh from the key-frame store, section 4v).
 #pragma once
 #include "kfstore.h"
 
@@ -11,11 +12,32 @@ namespace vo {
 // search (with its 2 x radius retry) or trackRefKeyFrame's vocabulary-node search --, and the local-map stage.
 enum : unsigned { kRunFront = 1u, kRunMotion = 2u, kRunRefKeyFrame = 4u, kRunLocal = 8u, kRunReloc = 16u, kRunRefStore = 32u };
 
-// handover.hip's device block and what tracker.hip needs of it
-struct Handover;
+// handover.hip's device block (motion_store.hip reads the last ids, the poses and the sort keys of it) and what tracker.hip
+// needs of it
+struct Handover {
+  Arena mem;
+  int P = 0;  // the power of two >= max_features: the keys of a frame
+  int *slot_ids = nullptr, *last_ids = nullptr, *motion_state = nullptr, *temp_count = nullptr;
+  uint8_t *slot_desc = nullptr, *slot_flags = nullptr, *last_valid = nullptr;
+  double *frame_pose = nullptr, *velocity = nullptr, *last_pose = nullptr;  // last_pose: [B][12], then last_valid [B]
+  unsigned long long *keys = nullptr;                                        // [B][P] where P > kHoLdsKeys, else unused
+};
+constexpr int kHoLdsKeys = 4096;
 void handover_destroy(Handover *h);
 // device array behind one of the selectors from VO_TRACKER_SLOT_IDS on (nullptr: not one of them, or not there yet)
 const void *handover_selector(const vo_tracker *t, int what, size_t *bytes);
+
+// motion_store.hip's device block and what tracker.hip needs of it.  vo_tracker_build_local_map on the
+// motion route: motion_store_ensure before anything is enqueued; motion_store_slot_ids enqueues the gather and points the
+// builder's arguments at the ids and at a vote mask of their own (a temporary point holds a point and no id: it must neither
+// vote nor be nulled); motion_store_link, behind the builder, takes the nulling over into the tracker's slots and writes `link`.
+struct MotionStore;
+void motion_store_destroy(MotionStore *m);
+int motion_store_ensure(vo_tracker *t);
+int motion_store_slot_ids(vo_tracker *t, LocalMapArgs *A, hipStream_t st);
+int motion_store_link(vo_tracker *t, hipStream_t st);
+// device array behind one of the selectors from VO_TRACKER_FIRST_SLOT_IDS on (nullptr: not one of them, or not there yet)
+const void *motion_store_selector(const vo_tracker *t, int what, size_t *bytes);
 
 }  // namespace vo
 
@@ -109,6 +131,12 @@ struct vo_tracker {
   unsigned last_run = 0;
   bool have_last_ids = false, handed_over = false;
   vo::Handover *ho = nullptr;
+  // the motion route from the store (motion_store.hip): the block; whether vo_tracker_build_local_map has built this frame's map
+  // from the last ids (VO_TRACKER_FIRST_SLOT_IDS is the frame's; vo_tracker_results reads the store routes' sticky word);
+  // whether the local-map stage ran as a call of its own (vo_tracker_track_local_map); whether vo_tracker_begin_frame has run
+  // since vo_tracker_end_frame (the window of vo_tracker_refresh_last_pose)
+  vo::MotionStore *ms = nullptr;
+  bool lm_motion = false, local_split = false, begun = false;
   // timing
   bool timing = false;
   // 2 events per stage and timed call, in a list that grows with the calls; they are read (after one synchronisation) only
