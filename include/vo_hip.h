@@ -2058,7 +2058,9 @@ enum {
   VO_TRACKER_STAT_VISIBLE = 52,      /* int32, same shape */
   VO_TRACKER_STAT_FOUND = 53,        /* int32, same shape */
   VO_TRACKER_REF_TCR = 54,           /* double [batch][12]: TcrDB_ of the remembered reference key-frame */
-  VO_TRACKER_REF_KF = 55             /* int32 [batch]: that key-frame's number, -1: none */
+  VO_TRACKER_REF_KF = 55,            /* int32 [batch]: that key-frame's number, -1: none */
+  VO_TRACKER_FEATURE_OBSERVED = 56   /* uint8 [batch][max_features]: the per-slot observed mark (bit 1 of the flags of the entry the
+                                        slot took its point from); read by vo_tracker_end_frame[_store]'s cullingTempMapPoints */
 };
 int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes);
 /* frame_last_ = frame_curr_ on the device: what VisualOdometry::run does between two frames
@@ -2130,7 +2132,7 @@ int vo_tracker_handover_arrays(vo_tracker *t, const int32_t **dev_slot_ids, cons
  * is enqueued or any state changes.
  * vo_tracker_point_stats(): valid after vo_tracker_track_first[_dev] + vo_tracker_track_local_map with ids on the local map
  * (built, or vo_tracker_set_local_map_ids) and on the last-frame list; anything else VO_ERR_INVALID (the counters behind the
- * relocalisation and reference-key-frame routes are not built).  One launch, a workgroup per frame, fills VO_TRACKER_STAT_IDS,
+ * relocalisation and reference-key-frame routes: vo_tracker_point_stats_store, below).  One launch, a workgroup per frame, fills VO_TRACKER_STAT_IDS,
  * _VISIBLE and _FOUND, int32 [batch][max_features + max_local]:
  *  A entry i < max_features: p = the id slot i held when searchLocalMapPoints started -- VO_TRACKER_FIRST_SLOT_IDS[i] behind a
  *    built map; behind a local map the host set the same gather on the state as it stands (a slot the local search claimed
@@ -2159,6 +2161,47 @@ int vo_tracker_point_stats_arrays(vo_tracker *t, const int32_t **dev_ids, const 
                                   int32_t *row_len);
 int vo_tracker_record_ref_pose(vo_tracker *t, const vo_kfstore *store, const int32_t *dev_ref_kf /*[batch] or NULL*/);
 int vo_tracker_refresh_last_pose(vo_tracker *t, const vo_kfstore *store);
+/* The hand-over and the counters behind the other two routes of VisualOdometry::run, which keep their
+ * slot ids in the key-frame store: all three routes end in the same two enqueued calls, and relocalise -> reference key-frame
+ * -> motion runs with no host array in between.  Both calls are valid only when ALL of these hold, else VO_ERR_INVALID:
+ *  - the last front was vo_tracker_relocalize_store[_dev] / _db[_dev], or vo_tracker_track_ref_keyframe_store[_dev] with
+ *    first_stage_only = 1;
+ *  - this frame's local map was built by vo_tracker_build_local_map(store) (a map or ids set from the host since: refused);
+ *  - vo_tracker_track_local_map has run behind the build.
+ * One call is one route for the whole batch.  vo_tracker_end_frame and vo_tracker_point_stats stay refused behind these routes.
+ * Each call is ONE launch, a workgroup per frame, ENQUEUED on the tracker's stream and ordered against the store's stream by
+ * events as vo_tracker_build_local_map is (the observation index is rebuilt on the store's stream when stale): no host
+ * synchronisation, no device-to-host copy, no allocation after the first call of the hand-over's / the counters' block.  They
+ * have no state of their own.  Every refusal happens before anything is enqueued or any state changes.
+ * vo_tracker_end_frame_store(store, p): max_features > max_last VO_ERR_CAPACITY.  Steps 2-5 and every output are
+ * vo_tracker_end_frame's (SLOT_IDS, SLOT_DESC, FRAME_POSE, VELOCITY, MOTION_STATE, the last pose and its validity, the
+ * rewritten last-frame list with ids, LAST_N = max_features); vo_tracker_begin_frame, _record_ref_pose, _refresh_last_pose,
+ * _handover_arrays and the key-frame creation calls follow it as they follow vo_tracker_end_frame.  Step 1, slot i < n:
+ *   relocalisation: a non-null slot (VO_TRACKER_FEATURE_HAS_POINT) carries VO_TRACKER_RELOC_POINT_IDS[i] (the local search's
+ *    claims are in it already).  A frame whose relocalisation failed (VO_TRACKER_RELOC_WINNER < 0): every slot null, ok = 0, an
+ *    empty list, the last pose invalid, MOTION_STATE 0 (:113-120, :128).
+ *   reference key-frame: VO_TRACKER_ASSIGNED_LOCAL[i] = a1 >= 0 -> VO_TRACKER_LOCAL_POINT_IDS[a1]; else
+ *    VO_TRACKER_ASSIGNED_LAST[i] = a0 >= 0 and the slot non-null -> the store's ids[ref_kf[f]][a0], the key-frame in [0, size)
+ *    and a0 below its feature count; else null.
+ *   both: an id < 0 is null.  observed = VO_TRACKER_FEATURE_OBSERVED[i], outlier = VO_TRACKER_FEATURE_OUTLIER[i], position =
+ *    VO_TRACKER_FEATURE_POINTS[i].  Descriptor (mp->descriptor_) = the store's point descriptor at the id's first key of the
+ *    observation index: the lowest (key-frame, feature) with flags bit 0 that holds the id, below size.
+ *   DEVIATION: an id that no key-frame holds any more is a bad point (the reference would still hand the pointer over and skip
+ *    it at its next use); the slot is handed over null.
+ *   status and n_tracked of step 3 are those vo_tracker_results reports (the result block: on the relocalisation route they
+ *    do not live in the tracker's own arrays); so is the pose of step 4.
+ * vo_tracker_point_stats_store(store): fills the rows of vo_tracker_point_stats (same block, same addresses, straight into
+ * vo_kfstore_add_point_stats_dev):
+ *  A entry i < n: a non-null slot the local search did not claim (VO_TRACKER_ASSIGNED_LOCAL[i] < 0) counts with the id of the
+ *    route's source above (RELOC_POINT_IDS[i], or the store's ids[ref_kf][a0]): visible 1 (:738), found 1 iff
+ *    VO_TRACKER_FEATURE_OUTLIER[i] == 0 (:295-297).  Anything else: id -1, counts 0.
+ *  B as vo_tracker_point_stats; VO_TRACKER_LOCAL_FLAGS are the flags isInFrame ran with on either route -- behind a
+ *    relocalisation a local point the frame already holds was skipped by id and is not visible (:753).
+ *  A frame whose relocalisation failed: a row of -1 / 0.
+ * Not built: the host forms of the two routes and the one-call form of track_ref_keyframe_store (their local map is set by the
+ * host); a batch whose frames take different routes (the caller groups streams); lastRelocateFrameId_; recoverLastFrame. */
+int vo_tracker_end_frame_store(vo_tracker *t, vo_kfstore *store, const vo_tracker_handover_params *p);
+int vo_tracker_point_stats_store(vo_tracker *t, vo_kfstore *store);
 int vo_tracker_sync(vo_tracker *t);
 /* HIP events on the launching streams around the six stages of every subsequent batch (bench.py):
  * 0 extraction, 1 frame post-processing, 2 search vs last frame, 3 pose solve + culling, 4 isInFrame +

@@ -57,6 +57,7 @@ SYMBOLS = [
     "vo_tracker_set_last_frame_ids", "vo_tracker_set_last_pose", "vo_tracker_end_frame", "vo_tracker_begin_frame",
     "vo_tracker_handover_arrays",
     "vo_tracker_point_stats", "vo_tracker_point_stats_arrays", "vo_tracker_record_ref_pose", "vo_tracker_refresh_last_pose",
+    "vo_tracker_end_frame_store", "vo_tracker_point_stats_store",
     "vo_kfstore_set_graph", "vo_kfstore_set_graph_batch", "vo_kfstore_set_normals", "vo_tracker_build_local_map",
     "vo_kfstore_enable_connections", "vo_kfstore_update_connections", "vo_kfstore_update_connections_dev",
     "vo_kfstore_connections_status", "vo_kfstore_get_connections",
@@ -510,7 +511,8 @@ class Tracker:
      RELOC_CANDIDATES, RELOC_N_CANDIDATES, LOCAL_KEYFRAMES, LOCAL_N_KEYFRAMES, LOCAL_N_POINTS, LOCAL_REF_KF, LOCAL_POINT_IDS,
      LOCAL_POINTS, LOCAL_NORMALS, LOCAL_MIN_DISTANCE, LOCAL_MAX_DISTANCE, LOCAL_DESC, LOCAL_MAP_FLAGS, LOCAL_LINK,
      POSE_START, SLOT_IDS, SLOT_DESC, FRAME_POSE, VELOCITY, MOTION_STATE, TEMP_COUNT, LAST_POINTS, LAST_FLAGS, LAST_OCTAVE,
-     LAST_ANGLE, LAST_DESC, LAST_IDS, LAST_N, TCW_START, FIRST_SLOT_IDS, STAT_IDS, STAT_VISIBLE, STAT_FOUND, REF_TCR, REF_KF) = range(56)
+     LAST_ANGLE, LAST_DESC, LAST_IDS, LAST_N, TCW_START, FIRST_SLOT_IDS, STAT_IDS, STAT_VISIBLE, STAT_FOUND, REF_TCR, REF_KF,
+     FEATURE_OBSERVED) = range(57)
     LOCAL_MAX_KEYFRAMES = 84
     RELOC_STAGES = ("featvec", "gather", "local_ids", "bow_walk")
     STAGES = ("extract", "frame_post", "match_last_frame", "pose_only_1", "match_local_map", "pose_only_2")
@@ -675,6 +677,20 @@ class Tracker:
         a, b, c, n = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_int32()
         check(lib().vo_tracker_point_stats_arrays(self._h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)), "vo_tracker_point_stats_arrays")
         return a.value, b.value, c.value, n.value
+
+    def end_frame_store(self, store, th_depth, min_tracked=0):
+        """vo_tracker_end_frame_store: end_frame behind relocalize_store / relocalize_db or track_ref_keyframe_store(first_stage_only=
+        True), each followed by build_local_map(store) + track_local_map: the slot ids and descriptors come from `store`.
+        Asynchronous; the outputs and the calls that may follow are end_frame's."""
+        pr = HandoverParams(float(th_depth), int(min_tracked))
+        check(lib().vo_tracker_end_frame_store(self._h, store._h, C.byref(pr)), "vo_tracker_end_frame_store")
+        self._end_store_keep = store  # the enqueued kernel reads it
+
+    def point_stats_store(self, store):
+        """vo_tracker_point_stats_store: point_stats' three rows per frame behind the same two routes.  Asynchronous;
+        get(STAT_IDS / STAT_VISIBLE / STAT_FOUND) after."""
+        check(lib().vo_tracker_point_stats_store(self._h, store._h), "vo_tracker_point_stats_store")
+        self._stats_store_keep = store  # the enqueued kernel reads it
 
     def record_ref_pose(self, store, ref_kf=None):
         """vo_tracker_record_ref_pose: Tcr = frame pose * pose(ref)^-1 per frame after end_frame (visualOdometry.cpp:130-140).
@@ -877,7 +893,8 @@ class Tracker:
             self.LAST_ANGLE: ((B, ml), np.float32), self.LAST_DESC: ((B, ml, 32), np.uint8), self.LAST_IDS: ((B, ml), np.int32),
             self.LAST_N: ((1,), np.int32), self.TCW_START: ((B, 12), np.float64),
             self.FIRST_SLOT_IDS: ((B, cap), np.int32), self.STAT_IDS: ((B, cap + nl), np.int32), self.STAT_VISIBLE: ((B, cap + nl), np.int32),
-            self.STAT_FOUND: ((B, cap + nl), np.int32), self.REF_TCR: ((B, 12), np.float64), self.REF_KF: ((B,), np.int32)}[what]
+            self.STAT_FOUND: ((B, cap + nl), np.int32), self.REF_TCR: ((B, 12), np.float64), self.REF_KF: ((B,), np.int32),
+            self.FEATURE_OBSERVED: ((B, cap), np.uint8)}[what]
         out = np.zeros(shape, dt)
         check(lib().vo_tracker_get(self._h, int(what), _p(out), C.c_size_t(out.nbytes)), "vo_tracker_get")
         return out

@@ -27,6 +27,7 @@ SOURCES = [
     ("tracker.hip", ["-ffp-contract=off"]),
     ("handover.hip", ["-ffp-contract=off"]),
     ("motion_store.hip", ["-ffp-contract=off"]),
+    ("handover_store.hip", ["-ffp-contract=off"]),
     ("reloc.hip", ["-ffp-contract=off"]),
     ("local_map.hip", ["-ffp-contract=off"]),
     ("ba.hip", ["-ffp-contract=fast"]),

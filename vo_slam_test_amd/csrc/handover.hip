@@ -2,7 +2,8 @@
 // frames (visualOdometry.cpp:80-128) and the preamble of trackWithMotion (:233-236), for every frame of a tracker's batch.
 //   k_ho_end    one workgroup per frame: the slot rule of examples/vo_run_hip.cpp:279-281 (local over last), cullingTempMapPoints
 //               (:844-853), the verdict, Tcl_ = Tcw * Tlw^-1 (:94-103, :115-118), then -- behind a barrier, the reads of the old
-//               list being done -- cullingOutliersOfFrame (:888-895) and the frame written as the last-frame list (:128).
+//               list being done -- cullingOutliersOfFrame (:888-895) and the frame written as the last-frame list (:128).  The pose
+//               side and the list rewrite are handover_end.h's, shared with handover_store.hip.
 //   k_ho_begin  one workgroup per frame: updateLastFrame's temporary points (:555-592) as k_kc_walk's walk -- the pairs
 //               (depth bits << 32 | feature) sorted by block_bitonic_sort in LDS (up to kHoLdsKeys keys, else in the block), the
 //               inclusive count C_j by wave ballots, the first j with d_j > th_depth && C_j > 100 --, the start pose
@@ -14,6 +15,7 @@
 #include "tracker_state.h"
 
 #include "block_sort.h"
+#include "handover_end.h"
 #include "handover_geom.h"
 #include "handover_link.h"
 
@@ -64,19 +66,9 @@ __global__ __launch_bounds__(256) void k_ho_end(EndArgs A) {
   const uint4 zero = make_uint4(0, 0, 0, 0);
   // ---- the pose side (:87-118)
   if (tid == 0) {
-    double T[12], V[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-    ho_pose12(ba::se3_exp(A.pose6 + 6 * (size_t)f), T);
     const bool ok = A.status[f] == 0 && A.ntracked[f] >= A.min_tracked;
-    double *L = A.last_pose + 12 * (size_t)f;
-    const bool moving = ok && A.last_valid[f] != 0;
-    if (moving) {
-      double Li[12];
-      ho_inverse(L, Li);
-      ho_compose(T, Li, V);
-    }
-    for (int k = 0; k < 12; k++) A.frame_pose[12 * (size_t)f + k] = T[k], A.velocity[12 * (size_t)f + k] = V[k], L[k] = T[k];
-    A.motion_state[f] = moving ? 1 : 0;
-    A.last_valid[f] = ok ? 1 : 0;
+    ho_end_pose(A.pose6 + 6 * (size_t)f, ok, A.frame_pose + 12 * (size_t)f, A.velocity + 12 * (size_t)f, A.last_pose + 12 * (size_t)f,
+                A.last_valid + f, A.motion_state + f);
   }
   // ---- the slots as createNewKeyFrame sees them (steps 1 and 2)
   for (int i = tid; i < A.cap; i += 256) {
@@ -107,26 +99,8 @@ __global__ __launch_bounds__(256) void k_ho_end(EndArgs A) {
   }
   __syncthreads();  // every read of the old list is done
   // ---- cullingOutliersOfFrame (:888-895) and frame_last_ = frame_curr_ (:128); a thread reads back the slots it wrote
-  for (int i = tid; i < A.n_last; i += 256) {
-    uint8_t flags = 0;
-    int id = -1, oct = 0;
-    float ang = 0.f;
-    double p[3] = {0, 0, 0};
-    uint4 d0 = zero, d1 = zero;
-    if (i < n) {
-      flags = A.slot_flags[o + i], oct = A.octave[o + i], ang = A.angle[o + i];
-      if (flags) {
-        id = A.slot_ids[o + i];
-        const uint4 *src = reinterpret_cast<const uint4 *>(A.slot_desc) + 2 * (o + i);
-        d0 = src[0], d1 = src[1];
-        for (int c = 0; c < 3; c++) p[c] = A.fpoint[3 * (o + i) + c];
-      }
-    }
-    A.pf0[lo + i] = flags, A.last_ids[lo + i] = id, A.q0_level[lo + i] = oct, A.q0_angle[lo + i] = ang;
-    for (int c = 0; c < 3; c++) A.p0[3 * (lo + i) + c] = p[c];
-    uint4 *dst = reinterpret_cast<uint4 *>(A.q0_desc) + 2 * (lo + i);
-    dst[0] = d0, dst[1] = d1;
-  }
+  ho_end_list(n, A.n_last, A.slot_flags + o, A.slot_ids + o, A.slot_desc + 32 * o, A.octave + o, A.angle + o, A.fpoint + 3 * o, A.p0 + 3 * lo,
+              A.pf0 + lo, A.q0_level + lo, A.q0_angle + lo, A.q0_desc + 32 * lo, A.last_ids + lo);
 }
 
 struct BeginArgs {
@@ -254,6 +228,8 @@ int ho_ensure(vo_tracker *t) {
 }
 
 }  // namespace
+
+int vo::handover_ensure(vo_tracker *t) { return ho_ensure(t); }
 
 const void *vo::handover_selector(const vo_tracker *t, int what, size_t *bytes) {
   const Handover *h = t->ho;

@@ -15,6 +15,7 @@
 
 #include "handover_geom.h"
 #include "handover_link.h"
+#include "point_stats_rows.h"
 
 #include <algorithm>
 #include <new>
@@ -111,21 +112,8 @@ __global__ __launch_bounds__(256) void k_ms_stats(StatArgs A) {
     A.ids[r + i] = p, A.visible[r + i] = p >= 0 ? 1 : 0;
     A.found[r + i] = (p >= 0 && A.assigned[o + i] < 0 && A.foutl[o + i] == 0) ? 1 : 0;
   }
-  // ---- segment B: the local points (:750-760); a local point is claimed by at most one slot: plain stores
-  for (int j = tid; j < A.max_local; j += 256) A.found[rb + j] = 0;
-  __syncthreads();
-  for (int i = tid; i < n; i += 256) {
-    const int a = A.assigned[o + i];
-    if (a >= 0 && a < A.max_local && A.foutl[o + i] == 0) A.found[rb + a] = 1;
-  }
-  __syncthreads();
-  for (int j = tid; j < A.max_local; j += 256) {
-    int id = j < A.nq_local ? A.ids1[mo + j] : -1;
-    int vis = 0, fnd = 0;
-    if (id >= 0) vis = A.q1_flags[mo + j] & 1, fnd = A.found[rb + j];
-    if (!vis && !fnd) id = -1;
-    A.ids[rb + j] = id, A.visible[rb + j] = vis, A.found[rb + j] = fnd;
-  }
+  // ---- segment B: the local points (:750-760)
+  ps_local_rows(n, A.nq_local, A.max_local, A.assigned + o, A.foutl + o, A.ids1 + mo, A.q1_flags + mo, A.ids + rb, A.visible + rb, A.found + rb);
 }
 
 struct PoseArgs {
@@ -248,6 +236,10 @@ int vo::motion_store_link(vo_tracker *t, hipStream_t st) {
   hipLaunchKernelGGL(k_ms_link, dim3(t->B), dim3(256), 0, st, slot_args(t));
   VO_HIP_CHECK(hipGetLastError());
   return VO_OK;
+}
+
+void vo::motion_store_stat_rows(const vo_tracker *t, int **ids, int **visible, int **found, int *row) {
+  *ids = t->ms->stat_ids, *visible = t->ms->stat_visible, *found = t->ms->stat_found, *row = t->ms->row;
 }
 
 const void *vo::motion_store_selector(const vo_tracker *t, int what, size_t *bytes) {

@@ -939,6 +939,7 @@ int vo_tracker_set_local_map(vo_tracker *t, int n, const double *points, const d
   if (link) VO_CHECK(put_rows(t, t->d.link1, link, n, t->n_local, 4));
   t->nq_local = n;
   t->have_local = true, t->have_ids = false;  // (ids belong to the local map they were set for)
+  t->lm_route = 0, t->local_ran = false;      // (a host-set map: vo_tracker_end_frame_store is refused)
   VO_HIP_CHECK(hipStreamSynchronize(t->st));
   return VO_OK;
 }
@@ -953,6 +954,7 @@ int vo_tracker_set_local_map_ids(vo_tracker *t, int n, const int32_t *ids) {
   VO_CHECK(put_rows(t, t->d.ids1, ids, n, t->n_local, 4));
   VO_HIP_CHECK(hipStreamSynchronize(t->st));
   t->have_ids = true;
+  t->lm_route = 0;  // (ids of the caller's, not the store's)
   return VO_OK;
 }
 
@@ -961,6 +963,7 @@ static int ran(vo_tracker *t, unsigned run, int rc) {
   t->last_run = rc == VO_OK ? run : 0u;
   t->handed_over = false;  // (the frame store's slots hold another frame now)
   t->lm_motion = false, t->local_split = false;
+  t->lm_route = 0, t->local_ran = false;
   return rc;
 }
 
@@ -1024,11 +1027,13 @@ int vo_tracker_track_local_map(vo_tracker *t, const vo_tracker_params *params) {
     if (params) P = *params;
     else P.radius = 15.f, P.th_radius = 5.f, P.ratio = 0.8f, P.direction = 0, P.no_retry = 0, P.ref_ratio = 0.7f;  // :768
     t->pend.assigned = nullptr;
-    return stage_local_reloc(t, P);
+    const int rc = stage_local_reloc(t, P);
+    t->local_ran = rc == VO_OK;
+    return rc;
   }
   const int rc = run_pipeline(t, FrameInput{}, params, kRunLocal);
   t->last_run = rc == VO_OK ? (t->last_run | kRunLocal) : 0u;
-  t->local_split = rc == VO_OK;
+  t->local_split = rc == VO_OK, t->local_ran = rc == VO_OK;
   return rc;
 }
 
@@ -1352,6 +1357,7 @@ int vo_tracker_build_local_map(vo_tracker *t, vo_kfstore *store) {
   t->nq_local = t->cfg.max_local;
   t->have_local = true, t->have_ids = true, t->have_link = t->ids_route == 2 || motion;
   t->lm_motion = motion;
+  t->lm_route = motion ? 0 : t->ids_route, t->local_ran = false;  // (vo_tracker_end_frame_store: this frame's map, no local stage yet)
   return VO_OK;
 }
 
@@ -1485,6 +1491,7 @@ int vo_tracker_get(vo_tracker *t, int what, void *dst, size_t dst_bytes) {
     case VO_TRACKER_LAST_ANGLE: b = t->d.q0_angle, bytes = B * (size_t)t->n_last * 4; break;
     case VO_TRACKER_LAST_DESC: b = t->d.q0_desc, bytes = B * (size_t)t->n_last * 32; break;
     case VO_TRACKER_TCW_START: b = t->d.Tcw, bytes = B * 96; break;
+    case VO_TRACKER_FEATURE_OBSERVED: b = t->d.fobs, bytes = B * cap; break;
     default:
       if (what < VO_TRACKER_SLOT_IDS || what > VO_TRACKER_REF_KF) return VO_ERR_INVALID;
       b = what >= VO_TRACKER_FIRST_SLOT_IDS ? vo::motion_store_selector(t, what, &bytes)  // (the block of motion_store.hip)

@@ -1,6 +1,7 @@
 // tracker_state.h -- the tracker's handle as its own files see it (not part of the C-ABI): tracker.hip (the routes, the
-// setters, the getters), handover.hip (frame_last_ = frame_curr_ on the device) and motion_store.hip (the
-// motion route's local map, point counters and pose refresh from the key-frame store, section 4v).
+// setters, the getters), handover.hip (frame_last_ = frame_curr_ on the device), motion_store.hip (the
+// motion route's local map, point counters and pose refresh from the key-frame store, section 4v) and handover_store.hip (the
+// hand-over and the counters behind the relocalisation and reference-key-frame routes from the store, section 4w).
 #pragma once
 #include "kfstore.h"
 
@@ -24,6 +25,7 @@ struct Handover {
 };
 constexpr int kHoLdsKeys = 4096;
 void handover_destroy(Handover *h);
+int handover_ensure(vo_tracker *t);  // the block, allocated and cleared by the first call that needs it
 // device array behind one of the selectors from VO_TRACKER_SLOT_IDS on (nullptr: not one of them, or not there yet)
 const void *handover_selector(const vo_tracker *t, int what, size_t *bytes);
 
@@ -38,6 +40,8 @@ int motion_store_slot_ids(vo_tracker *t, LocalMapArgs *A, hipStream_t st);
 int motion_store_link(vo_tracker *t, hipStream_t st);
 // device array behind one of the selectors from VO_TRACKER_FIRST_SLOT_IDS on (nullptr: not one of them, or not there yet)
 const void *motion_store_selector(const vo_tracker *t, int what, size_t *bytes);
+// the three counter arrays [B][row] of the block (handover_store.hip fills the rows vo_tracker_point_stats_arrays hands out)
+void motion_store_stat_rows(const vo_tracker *t, int **ids, int **visible, int **found, int *row);
 
 }  // namespace vo
 
@@ -137,6 +141,11 @@ struct vo_tracker {
   // since vo_tracker_end_frame (the window of vo_tracker_refresh_last_pose)
   vo::MotionStore *ms = nullptr;
   bool lm_motion = false, local_split = false, begun = false;
+  // the hand-over behind the store's other two routes (handover_store.hip, section 4w): the ids_route whose frame
+  // vo_tracker_build_local_map built the present local map for (0: none -- set by the host, or the motion route's); whether
+  // vo_tracker_track_local_map has run since (on either branch)
+  int lm_route = 0;
+  bool local_ran = false;
   // timing
   bool timing = false;
   // 2 events per stage and timed call, in a list that grows with the calls; they are read (after one synchronisation) only
